@@ -22,6 +22,19 @@ After the timed loop at N > 1 the ranks' results (node digest, DepthStat, counts
 job rebuilt on rank 0 by the atomic engine (`verified`; --no-verify skips it).  --backend gloo --one-gpu runs the same N-rank
 flows with all ranks on GPU 0 and host-staged collectives: a correctness rehearsal for one-GPU boxes, not a measurement.
 
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the outputs of the last timed
+step when --dump-outputs DIR is given, print the line (`verified` is null: nothing is checked).  Everything else described
+below -- the checks after the timed loop, the other form of the resident input, SURVEY 8(d)'s region from the first
+host-to-device copy, the in-run PMC traffic, the bandwidth probes, `also` and `cpu_baseline` -- runs with --full.
+
+--dump-outputs DIR (one process): after the timed loop, what its last step built, as DIR/<name>.npy (float64, float32 for
+the frequency table), under 64 MB in all: `stats` (total_reads, total_kmers, stored_kmers, count, polyA l_link / r_link,
+other_bytes), `digest` (the order-independent node digest as two 32-bit halves), `depth_stat` (DepthStat of the table) and
+`nodes_sample`, a fixed sample of the sorted nodes -- those whose key hashes (seeded) below a threshold set by the input's
+k-mer count, at most NODE_SAMPLE of them, in key order; a row is the key in 32-bit pieces, then l_link, r_link.  cfg4:
+`stats`, `counts_sample` (fixed seeded windows of the 4^k counters) and `counts_windows` (their first indices).  The inputs
+are synthetic and seeded: the same arguments give the same inputs in every run.
+
 Prints ONE JSON line on rank 0 (contract in the task description).  `roofline` is the WHOLE step:
 algorithmic bytes of the step (33.25 B per k-mer) / ms_per_step against the 8 TB/s
 spec peak (`frac`) and against the copy bandwidth measured in the same run (`frac_of_measured`: the best of the runtime's
@@ -51,6 +64,9 @@ B_ALG = 33.25          # algorithmic bytes per k-mer, k=31 L=150: 1.25 B bases +
 H2D_REPS = 5           # repetitions of the region "first host-to-device copy -> final table" (SURVEY 8(d)); the median is reported
 PROBE_BYTES = 2 << 30  # the copy-bandwidth probe moves this much per copy (far beyond the 256 MiB Infinity Cache)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_SEED = 0x5EED_D8A5_2026_1016   # --dump-outputs: seed of the node sample's key hash and of the counter windows
+NODE_SAMPLE = 1 << 20               # --dump-outputs: nodes in the sample at most (32 MB as float64 at k <= 32, 48 MB at k > 32)
+DUMP_LIMIT = 64 << 20               # --dump-outputs: bytes of all arrays together at most
 
 
 CONFIGS = {"cfg2": dict(reads_per_gpu=10_000_000, genome_per_gpu=50_000_000, table_slots=600_000_000, synth_cfg=2,
@@ -115,7 +131,7 @@ def parse_args():
                     help="form of the reads resident in HBM when the timed region starts: 2-bit packed blocks (default; what SURVEY 8(d)'s "
                          "region hands to the device) or ASCII bytes")
     ap.add_argument("--no-also", action="store_true", help="default cfg2 run at N = 1: skip the three-step runs of cfg3 / cfg4 / cfg5")
-    ap.add_argument("--brief", action="store_true", help="the timed loop and its check only (no H2D legs, probes, CPU baseline, also-runs)")
+    ap.add_argument("--brief", action="store_true", help="with --full: the timed loop and its check only (no H2D legs, probes, CPU baseline, also-runs)")
     ap.add_argument("--plan-only", action="store_true",
                     help="print the geometry `--gpus N` would run with -- global table, level-1 buckets and their owners, records and bytes per "
                          "rank -- as one JSON line and leave: no GPU, no process group (dbgk_plan_partition); what the first run on a real "
@@ -125,7 +141,15 @@ def parse_args():
                          "one step each); the committed profiles/traffic_r*.json is used instead")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="per-launch HBM bytes of the dominant kernel from a separate rocprofv3 --pmc run")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the timed steps: the checks of what they built, the other input form, the region from the "
+                         "first host-to-device copy, in-run PMC traffic, bandwidth probes, the other configs (`also`), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step built to DIR/<name>.npy (stats, digest, DepthStat, a fixed sample of the "
+                         "nodes; cfg4: stats and a fixed sample of the counters); one process only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded or "WORLD_SIZE" in os.environ and os.environ["WORLD_SIZE"] != "1"):
+        ap.error("--dump-outputs needs one process (--gpus 1, no --force-sharded)")
     for key in ("reads_per_gpu", "genome_per_gpu", "table_slots"):
         if getattr(args, key) is None:
             setattr(args, key, CONFIGS[args.config][key])
@@ -547,10 +571,12 @@ def run_kfreq(args, ctx, brief=False):
     ms_per_step = dt / args.steps * 1e3
     kmers_step = int(st.stored_kmers)
     distinct = int(st.count)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, kfreq_outputs(g, st))
     # after the timed region (N = 1): the same reads through the OTHER counting path (atomics on the byte table) must give the
     # same table -- both are pinned against the oracle at smaller sizes (tests/test_kfreq.py); here at full size
     verified = None
-    if not multi:
+    if args.full and not multi:
         ptr, n_counts = g.kfreq_device_counts()
         mine = wrap_device_memory(ptr, n_counts, device).view(torch.int64)
         sum_a = int(mine.sum().item()) & ((1 << 64) - 1)
@@ -566,7 +592,7 @@ def run_kfreq(args, ctx, brief=False):
         verified = ("the 4^%d-byte table of the last timed step == the table the atomic kernel builds from the same reads (ASCII input; byte for byte), "
                     "%d distinct canonical k-mers; both paths are pinned to the oracle in tests/test_kfreq.py" % (k, distinct))
         del mine, other
-    elif not args.no_verify:
+    elif args.full and not args.no_verify:
         # N > 1: after the reduce-scatter rank d owns the counters of the k-mer values [bounds[d], bounds[d+1]) of the WHOLE job.
         # Two 64-bit sums over the 8-byte words of every owned range (plain, and of a mixed word), added over the ranks, against
         # the same sums over the table rank 0 builds from ALL ranks' reads with the atomic kernel (no records, no exchange)
@@ -618,7 +644,7 @@ def run_kfreq(args, ctx, brief=False):
         own = {"k_extract_scatter_uniform": kmers_step * (base_bytes + (4.0 if blocks else 8.0)), "k_scatter_l2": kmers_step * (6.0 if blocks else 16.0),
                bname: kmers_step * (2.0 if blocks else 8.0) + (4.0 ** k if blocks else distinct * 1.0)}   # (blocks: 32-bit level-1 records, level 2 leaves 16-bit ones)
         ms = {"k_extract_scatter_uniform": l1_ms, "k_scatter_l2": l2_ms, bname: build_ms}
-        copy_bw = copy_bandwidth(ctx, g)
+        copy_bw = copy_bandwidth(ctx, g) if args.full else ctx.copy_bw
         own_total = sum(own.values()) + (0.0 if blocks else 2.0 * 4 ** k)   # hashed form: + zeroing the table at reset and the summary pass over it
         traffic = measured_traffic(args, 0, None)
         out = {"metric": "M k-mers/s counted (k=%d, 150 bp)" % k, "value": kmers_step * world / (dt / args.steps) / 1e6, "unit": "M k-mers/s",
@@ -715,6 +741,74 @@ def median(xs):
     return xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2])
 
 
+def mix64(x):
+    """splitmix64 finaliser of a uint64 array (a bijection; numpy wraps the products mod 2^64)"""
+    import numpy as np
+    x = x ^ (x >> np.uint64(30))
+    x *= np.uint64(0xBF58476D1CE4E5B9)
+    x ^= x >> np.uint64(27)
+    x *= np.uint64(0x94D049BB133111EB)
+    x ^= x >> np.uint64(31)
+    return x
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy (float32 / float64 only), DUMP_LIMIT bytes in all"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        sys.exit("bench.py: --dump-outputs would write %d bytes, more than %d" % (total, DUMP_LIMIT))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def stats_output(st):
+    import numpy as np
+    return np.array([st.total_reads, st.total_kmers, st.stored_kmers, st.count, st.polyA_l_link, st.polyA_r_link, st.other_bytes],
+                    dtype=np.float64)
+
+
+def graph_outputs(g, wide, kmers):
+    """what a finalized graph handle (one process) hands its caller, for --dump-outputs: the counters, the node digest, DepthStat,
+    and the nodes whose seeded key hash falls below a threshold that only the input's k-mer count `kmers` sets (about 4 *
+    NODE_SAMPLE / kmers of the nodes; the NODE_SAMPLE smallest hashes if more), in key order, every field split into exact
+    32-bit pieces"""
+    import numpy as np
+    lo32 = np.uint64(0xFFFFFFFF)
+    d = g.digest()
+    out = {"stats": stats_output(g.stats), "digest": np.array([d >> 32, d & 0xFFFFFFFF], dtype=np.float64),
+           "depth_stat": np.array([int(x) for x in g.link_stats(2).depth_stat], dtype=np.float64)}
+    nodes = g.wide_export_sorted() if wide else g.export_sorted()
+    seed = np.uint64(DUMP_SEED)
+    key = (nodes["kmer_lo"] ^ mix64(nodes["kmer_hi"] ^ seed)) if wide else nodes["kmer"]
+    h = mix64(key ^ seed)
+    del key
+    frac = min(1.0, 4.0 * NODE_SAMPLE / max(kmers, 1))
+    sel = np.flatnonzero(h < np.uint64(min(int(frac * 2.0 ** 64), 2 ** 64 - 1)))
+    if len(sel) > NODE_SAMPLE:
+        sel = np.sort(sel[np.argpartition(h[sel], NODE_SAMPLE - 1)[:NODE_SAMPLE]])
+    del h
+    s = nodes[sel]
+    del nodes
+    words = [s["kmer_hi"] >> np.uint64(32), s["kmer_hi"] & lo32, s["kmer_lo"] >> np.uint64(32), s["kmer_lo"] & lo32] if wide else \
+            [s["kmer"] >> np.uint64(32), s["kmer"] & lo32]
+    out["nodes_sample"] = np.stack([w.astype(np.float64) for w in words] + [s["l_link"].astype(np.float64), s["r_link"].astype(np.float64)], axis=1)
+    return out
+
+
+def kfreq_outputs(g, st, windows=64, width=1 << 16):
+    """--dump-outputs for the frequency table: the counters, and `windows` seeded windows of `width` counters each (float32), in
+    table order, with their first indices (`counts_windows`)"""
+    import numpy as np
+    n = 4 ** g.k
+    width = min(width, n)
+    starts = np.sort(np.random.default_rng(DUMP_SEED).choice(n // width, size=min(windows, n // width), replace=False)) * width
+    counts = np.concatenate([g.kfreq_counts(int(a), width) for a in starts]).astype(np.float32)
+    return {"stats": stats_output(st), "counts_sample": counts, "counts_windows": starts.astype(np.float64)}
+
+
 def run_graph(args, ctx, brief=False):
     """the graph configurations (cfg2, cfg3, cfg5): the timed loop, the check of what it built, the legs around it.  Returns the
     result record on rank 0."""
@@ -767,7 +861,7 @@ def run_graph(args, ctx, brief=False):
     debug_mode = int(os.environ.get("DBGK_DEBUG_MODE", "0"))  # kernel timing experiments: results are wrong
     debug_l2 = int(os.environ.get("DBGK_DEBUG_L2", "0")) or int(os.environ.get("DBGK_DEBUG_BUILD", "0"))
 
-    state = {"verify": True, "packed": packed_in}   # the first step run checksums what every rank sent against what its peers received
+    state = {"verify": args.full, "packed": packed_in}   # --full: the first step run checksums what every rank sent against what its peers received
 
     fixed_len = not CONFIGS[args.config].get("trimmed")   # reads of one length travel without offsets (dbgk_push_reads_packed_uniform*)
 
@@ -811,7 +905,7 @@ def run_graph(args, ctx, brief=False):
     for _ in range(args.warmup):
         step()
         state["verify"] = False
-    if not args.warmup and multi:   # no warm-up step: verify the exchange once, untimed
+    if not args.warmup and multi and args.full:   # no warm-up step: verify the exchange once, untimed
         step()
         state["verify"] = False
     g.sync()
@@ -835,10 +929,14 @@ def run_graph(args, ctx, brief=False):
     total_kmers = res["stored_kmers"]  # all ranks
     ms_per_step = dt / args.steps * 1e3
     value = total_kmers / (dt / args.steps) / 1e6
+    if args.dump_outputs:
+        if debug_mode or debug_l2:
+            sys.exit("bench.py: --dump-outputs and DBGK_DEBUG_* do not go together (the experiments' results are wrong by design)")
+        write_outputs(args.dump_outputs, graph_outputs(g, args.engine == capi.ENGINE_WIDE, int(round(n_reads * kpr))))
 
-    # ---- after the timed region: correctness of what was just measured, the H2D-inclusive rate ------
+    # ---- after the timed region (--full): correctness of what was just measured, the H2D-inclusive rate ------
     verified = None
-    gold = golden_cfg2(args, world, n_reads, genome_len) if not (debug_mode or debug_l2) else None
+    gold = golden_cfg2(args, world, n_reads, genome_len) if args.full and not (debug_mode or debug_l2) else None
     if gold is not None and not multi:
         got = (int(res["count"]), int(res["stored_kmers"]), g.digest(), [int(x) for x in g.link_stats(2).depth_stat])
         want = (gold["count"], gold["total_kmers"], gold["digest"], gold["depth_stat"])
@@ -847,9 +945,9 @@ def run_graph(args, ctx, brief=False):
                      "(count/kmers/digest %r, expected %r)" % (got[:3], want[:3]))
         verified = ("count, k-mer total, node digest and DepthStat of the last timed step == tests/golden/cfg2_full.json (full size; CPU oracle"
                     + (", confirmed by the real reference" if gold.get("confirmed_by") else "") + ")")
-    elif not multi and not args.no_verify and not (debug_mode or debug_l2):
+    elif args.full and not multi and not args.no_verify and not (debug_mode or debug_l2):
         verified = verify_single(args, ctx, g, res, d_bases, d_off, n_reads, nb, size)
-    if multi and not args.no_verify and not (debug_mode or debug_l2):
+    if args.full and multi and not args.no_verify and not (debug_mode or debug_l2):
         verified = verify_whole_job(args, torch, capi, g, res, P, world, rank, dev_index, device, n_reads, size, sharded)
 
     # ---- the other form of the resident input, three steps (N = 1) ----
@@ -1045,6 +1143,7 @@ def also_runs(args, ctx):
         a.kmer = CONFIGS[cfg].get("kmer", 31)
         a.engine = {"cfg5": 5, "cfg4": 3}.get(cfg, 2)
         a.steps, a.warmup = 3, 1
+        a.dump_outputs = None
         t0 = time.perf_counter()
         try:
             r = run_kfreq(a, ctx, brief=True) if cfg == "cfg4" else run_graph(a, ctx, brief=True)
@@ -1101,9 +1200,10 @@ def main():
     result_out = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
     ctx = setup_process(args)
-    out = run_kfreq(args, ctx, brief=args.brief) if args.config == "cfg4" else run_graph(args, ctx, brief=args.brief)
+    brief = args.brief or not args.full   # a plain run: the timed loop alone
+    out = run_kfreq(args, ctx, brief=brief) if args.config == "cfg4" else run_graph(args, ctx, brief=brief)
     if ctx.rank == 0:
-        if ctx.world == 1 and not ctx.multi and not args.brief:
+        if ctx.world == 1 and not ctx.multi and not brief:
             defaults = all(getattr(args, key) == CONFIGS["cfg2"][key] for key in ("reads_per_gpu", "genome_per_gpu", "table_slots"))
             if args.config == "cfg2" and defaults and args.engine == 2 and not args.no_also and not os.environ.get("DBGK_DEBUG_MODE"):
                 out["also"] = also_runs(args, ctx)

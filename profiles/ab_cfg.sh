@@ -4,7 +4,7 @@ CFG=$1; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for round in $(seq 1 ${ROUNDS:-2}); do
   for lib in "$@"; do
-    DBGK_LIB=$lib python3 $R/bench.py --config $CFG --steps ${STEPS:-10} --warmup 2 --brief 2>/dev/null | python3 -c "
+    DBGK_LIB=$lib python3 $R/bench.py --full --config $CFG --steps ${STEPS:-10} --warmup 2 --brief 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 p=j.get('phases_ms_per_step',{})

@@ -2,7 +2,7 @@
 # the region "first host-to-device copy -> final table" (bench.py value_from_first_h2d) for several batch sizes: profiles/ab_h2d.sh 0 134217728 ...
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for b in "$@"; do
-  DBGK_BENCH_BATCH_BASES=$b python3 $R/bench.py --steps 5 --warmup 2 --no-also --no-cpu-baseline 2>/dev/null | python3 -c "
+  DBGK_BENCH_BATCH_BASES=$b python3 $R/bench.py --full --steps 5 --warmup 2 --no-also --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 h=j['value_from_first_h2d']

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 for round in $(seq 1 ${ROUNDS:-2}); do
   for lib in "$@"; do
     for ch in 1 12; do
-    DBGK_OVERLAP_CHUNKS=$ch DBGK_LIB=$lib python3 $R/bench.py --steps ${STEPS:-10} --warmup 2 --brief 2>/dev/null | python3 -c "
+    DBGK_OVERLAP_CHUNKS=$ch DBGK_LIB=$lib python3 $R/bench.py --full --steps ${STEPS:-10} --warmup 2 --brief 2>/dev/null | python3 -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 p=j['phases_ms_per_step']

@@ -138,7 +138,7 @@ def test_bench_multi_gpu_code_path_rehearsal(extra):
     env = dict(os.environ, MASTER_PORT=str(_free_port()))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-sharded", "--reads-per-gpu", "300000",
                         "--genome-per-gpu", "2000000", "--table-slots", "80000000", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600, env=env)
+                        "--no-cpu-baseline", "--full"] + extra, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[:2000]
@@ -189,7 +189,7 @@ def test_wide_sharded_build_single_rank_nccl(n_passes):
 
 
 SMALL = ["--reads-per-gpu", "200000", "--genome-per-gpu", "1500000", "--table-slots", "40000000", "--steps", "2", "--warmup", "1",
-         "--no-cpu-baseline"]
+         "--no-cpu-baseline", "--full"]
 
 
 @pytest.mark.parametrize("extra", [
