@@ -84,6 +84,21 @@ class Timings(C.Structure):
                 ("uniform_launches", C.c_uint32), ("prefix_launches", C.c_uint32), ("reserved", C.c_uint64 * 1)]
 
 
+class CorrParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("min_high_region", C.c_int32), ("max_change", C.c_int32), ("further_trim", C.c_int32),
+                ("max_tree_nodes", C.c_int32), ("min_trimmed_len", C.c_int32)]
+
+
+CORR_REC_DTYPE = np.dtype([("one_base", "<u4"), ("tree", "<u4"), ("left_trim", "<u4"), ("right_trim", "<u4"),
+                           ("node_limit_hits", "<u4"), ("deleted", "u1"), ("path", "u1"), ("pad", "u1", (2,))])  # dbgk_corr_rec
+
+
+class CorrStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("by_classify", C.c_uint64), ("by_correct", C.c_uint64), ("by_overflow", C.c_uint64),
+                ("node_limit_hits", C.c_uint64), ("ms_classify", C.c_double), ("ms_correct", C.c_double),
+                ("ms_overflow", C.c_double)]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -185,6 +200,15 @@ SYMBOLS = [
     ("dbgk_measure_copy_bandwidth", _i, [_vp, C.c_size_t, _i, C.POINTER(C.c_double)]),
     ("dbgk_measure_copy_bandwidth2", _i, [_vp, C.c_size_t, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("dbgk_measure_gather_bandwidth", _i, [_vp, C.c_size_t, _u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("dbgk_corr_create", _i, [C.POINTER(CorrParams), _i, C.POINTER(_vp)]),
+    ("dbgk_corr_destroy", _i, [_vp]),
+    ("dbgk_corr_load_bits", _i, [_vp, _u64, _u64, _vp]),
+    ("dbgk_corr_seal", _i, [_vp]),
+    ("dbgk_corr_from_kfreq", _i, [_vp, _vp, C.c_uint32]),
+    ("dbgk_corr_table_stats", _i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    ("dbgk_corr_export_bits", _i, [_vp, _u64, _u64, _vp]),
+    ("dbgk_corr_reads", _i, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    ("dbgk_corr_batch_stats", _i, [_vp, C.POINTER(CorrStats)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -800,3 +824,78 @@ def plan_partition(table_slots, expected_kmers, shard_count=0, shard_index=0):
     info = PlanInfo()
     _chk(lib().dbgk_plan_partition(table_slots, expected_kmers, shard_count, shard_index, C.byref(info)), "dbgk_plan_partition")
     return info
+
+
+class Corrector:
+    """correct_error_reads on the GPU (CORRECT section of include/dbgk.h).  Defaults are the reference's: -m and -x are
+    17 whatever k is.  Build the table with load_file (a 1-bit .cz file: raw blocks, then the loader's mirror) or
+    from_kfreq (a finalized KFREQ Graph + cutoff), then correct(bases, offsets)."""
+
+    BLOCK_BYTES = 1 << 20  # one compressed block of the .cz file: 8 Mi k-mers
+
+    def __init__(self, k=17, m=17, c=2, x=17, n=5000000, r=75, device=0):
+        self.k = k
+        self._h = C.c_void_p()
+        _chk(lib().dbgk_corr_create(C.byref(CorrParams(k, m, c, x, n, r)), device, C.byref(self._h)), "dbgk_corr_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_corr_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def load_bits(self, first_byte, raw):
+        raw = np.ascontiguousarray(np.frombuffer(bytes(raw), dtype=np.uint8) if not isinstance(raw, np.ndarray) else raw, dtype=np.uint8)
+        _chk(lib().dbgk_corr_load_bits(self._h, first_byte, raw.size, raw.ctypes.data), "dbgk_corr_load_bits")
+
+    def seal(self):
+        _chk(lib().dbgk_corr_seal(self._h), "dbgk_corr_seal")
+
+    def load_file(self, path):
+        """a 1-bit .cz table (+ .cz.len) as kmerfreq -b 1 writes it, loaded like make_kmerFreq_1bit_table_from_1BitGz"""
+        import zlib
+        lens = [int(v) for v in open(path + ".len").read().split()]
+        table_bytes = max(4 ** self.k // 8, 1)
+        with open(path, "rb") as f:
+            for b, n in enumerate(lens):
+                blk = zlib.decompress(f.read(n))
+                at = b * self.BLOCK_BYTES
+                if at < table_bytes:
+                    self.load_bits(at, blk[:table_bytes - at])
+        self.seal()
+
+    def from_kfreq(self, graph, cutoff):
+        _chk(lib().dbgk_corr_from_kfreq(self._h, graph._h, cutoff), "dbgk_corr_from_kfreq")
+
+    def table_stats(self):
+        t, h = _u64(), _u64()
+        _chk(lib().dbgk_corr_table_stats(self._h, C.byref(t), C.byref(h)), "dbgk_corr_table_stats")
+        return int(t.value), int(h.value)
+
+    def export_bits(self, first_byte=0, n_bytes=None):
+        if n_bytes is None:
+            n_bytes = max(4 ** self.k // 8, 1) - first_byte
+        out = np.empty(n_bytes, dtype=np.uint8)
+        _chk(lib().dbgk_corr_export_bits(self._h, first_byte, n_bytes, out.ctypes.data), "dbgk_corr_export_bits")
+        return out
+
+    def correct(self, bases, offsets):
+        """-> (corrected bases: every read untrimmed at its input offset, records CORR_REC_DTYPE[n])"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        out = np.empty(max(bases.size, 1), dtype=np.uint8)
+        rec = np.zeros(max(n, 1), dtype=CORR_REC_DTYPE)
+        _chk(lib().dbgk_corr_reads(self._h, bases.ctypes.data, offsets.ctypes.data, n, out.ctypes.data, rec.ctypes.data),
+             "dbgk_corr_reads")
+        return out[:bases.size], rec[:n]
+
+    def batch_stats(self):
+        s = CorrStats()
+        _chk(lib().dbgk_corr_batch_stats(self._h, C.byref(s)), "dbgk_corr_batch_stats")
+        return {f: getattr(s, f) for f, _ in CorrStats._fields_}

@@ -1,0 +1,278 @@
+// CORRECT: host side of correct_error_reads on the GPU (include/dbgk.h, ABI 7; kernels in dbgk_correct.h)
+
+struct dbgk_corr {
+	dbgk_corr_params p{};
+	corr::CorrParams cp{};
+	int device = 0;
+	int n_cu = 256;
+	hipStream_t stream = nullptr;
+	uint32_t *tab = nullptr;      // the loaded table, ceil(4^k / 32) words
+	uint64_t tab_words = 0;
+	bool sealed = false;
+	uint64_t hifreq = 0;
+	// batch buffers, grown on demand
+	uint8_t *d_seq = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+	uint64_t *d_off = nullptr;
+	dbgk_corr_rec *d_rec = nullptr;
+	uint32_t *d_work = nullptr, *d_ovf = nullptr, *d_cnt = nullptr;
+	uint64_t cap_bytes = 0, cap_reads = 0, cap_scratch = 0;
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	dbgk_corr_stats last{};
+};
+
+static int corr_use(dbgk_corr *c)
+{
+	HIPCHK(hipSetDevice(c->device));
+	return DBGK_OK;
+}
+
+static void corr_free_batch(dbgk_corr *c)
+{
+	(void)hipFree(c->d_seq); (void)hipFree(c->d_out); (void)hipFree(c->d_off); (void)hipFree(c->d_rec);
+	(void)hipFree(c->d_work); (void)hipFree(c->d_ovf);
+	c->d_seq = c->d_out = nullptr; c->d_off = nullptr; c->d_rec = nullptr; c->d_work = c->d_ovf = nullptr;
+	c->cap_bytes = c->cap_reads = 0;
+}
+
+extern "C" int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr **out)
+{
+	if (!p || !out) return DBGK_ERR_ARG;
+	*out = nullptr;
+	if (p->k < 1 || p->k > 19 || p->min_high_region < 1 || p->max_change < 0 || p->further_trim < 0 ||
+	    p->max_tree_nodes < 1 || p->max_tree_nodes >= (1 << 26) || p->min_trimmed_len < 0 || device < 0)
+		return DBGK_ERR_ARG;
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
+		g_last_error = "no usable HIP device";
+		return DBGK_ERR_HIP;
+	}
+	dbgk_corr *c = new (std::nothrow) dbgk_corr;
+	if (!c) return DBGK_ERR_NOMEM;
+	c->p = *p;
+	c->device = device;
+	c->cp = corr::CorrParams{p->k, p->min_high_region, p->max_change, p->further_trim, p->max_tree_nodes, p->min_trimmed_len,
+	                         1ull << (2 * p->k)};
+	c->tab_words = (c->cp.total + 31) / 32;
+	int rc = corr_use(c);
+	hipDeviceProp_t prop;
+	if (!rc && hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
+	if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
+	for (int i = 0; !rc && i < 4; ++i)
+		if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (!rc && hipMalloc(&c->tab, c->tab_words * 4) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (!rc && hipMalloc(&c->d_cnt, 4 * sizeof(uint64_t)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (!rc && hipMemsetAsync(c->tab, 0, c->tab_words * 4, c->stream) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (rc) {
+		dbgk_corr_destroy(c);
+		return rc;
+	}
+	*out = c;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_destroy(dbgk_corr *c)
+{
+	if (!c) return DBGK_ERR_ARG;
+	(void)hipSetDevice(c->device);
+	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	corr_free_batch(c);
+	(void)hipFree(c->d_scratch);
+	(void)hipFree(c->tab);
+	(void)hipFree(c->d_cnt);
+	for (auto &e : c->ev)
+		if (e) (void)hipEventDestroy(e);
+	if (c->stream) (void)hipStreamDestroy(c->stream);
+	delete c;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_load_bits(dbgk_corr *c, uint64_t first_byte, uint64_t n_bytes, const uint8_t *host_bits)
+{
+	if (!c || (!host_bits && n_bytes)) return DBGK_ERR_ARG;
+	if (c->sealed) return DBGK_ERR_STATE;
+	const uint64_t bytes = c->tab_words * 4;
+	if (first_byte > bytes || n_bytes > bytes - first_byte) return DBGK_ERR_ARG;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	if (!n_bytes) return DBGK_OK;
+	HIPCHK(hipMemcpyAsync((uint8_t *)c->tab + first_byte, host_bits, n_bytes, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DBGK_OK;
+}
+
+static int corr_table_kernel_done(dbgk_corr *c, unsigned long long *d_hif)
+{
+	HIPCHK(hipGetLastError());
+	unsigned long long h = 0;
+	HIPCHK(hipMemcpyAsync(&h, d_hif, sizeof h, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	c->hifreq = h;
+	c->sealed = true;
+	return DBGK_OK;
+}
+
+static unsigned corr_table_grid(const dbgk_corr *c)
+{
+	const uint64_t want = (c->tab_words + 255) / 256;
+	return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)c->n_cu * 16));
+}
+
+extern "C" int dbgk_corr_seal(dbgk_corr *c)
+{
+	if (!c) return DBGK_ERR_ARG;
+	if (c->sealed) return DBGK_ERR_STATE;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	unsigned long long *d_hif = (unsigned long long *)c->d_cnt;
+	HIPCHK(hipMemsetAsync(d_hif, 0, sizeof *d_hif, c->stream));
+	hipLaunchKernelGGL(corr::k_corr_seal, dim3(corr_table_grid(c)), dim3(256), 0, c->stream, c->tab, c->tab_words, c->cp.total,
+	                   c->p.k, d_hif);
+	return corr_table_kernel_done(c, d_hif);
+}
+
+extern "C" int dbgk_corr_from_kfreq(dbgk_corr *c, dbgk_handle *h, uint32_t cutoff)
+{
+	if (!c || !h) return DBGK_ERR_ARG;
+	if (!h->kfreq || !h->finalized || c->sealed) return DBGK_ERR_STATE;
+	if (h->cfg.kmer_size != c->p.k || h->device != c->device || h->n_counts != c->cp.total) return DBGK_ERR_ARG;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(h->stream)); // the counts are final on the handle's stream
+	unsigned long long *d_hif = (unsigned long long *)c->d_cnt;
+	HIPCHK(hipMemsetAsync(d_hif, 0, sizeof *d_hif, c->stream));
+	hipLaunchKernelGGL(corr::k_corr_from_counts, dim3(corr_table_grid(c)), dim3(256), 0, c->stream, c->tab, c->tab_words,
+	                   c->cp.total, c->p.k, (const uint8_t *)h->counts, cutoff, d_hif);
+	return corr_table_kernel_done(c, d_hif);
+}
+
+extern "C" int dbgk_corr_table_stats(dbgk_corr *c, uint64_t *theory_total, uint64_t *hifreq)
+{
+	if (!c || !theory_total || !hifreq) return DBGK_ERR_ARG;
+	if (!c->sealed) return DBGK_ERR_STATE;
+	*theory_total = c->cp.total;
+	*hifreq = c->hifreq;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_export_bits(dbgk_corr *c, uint64_t first_byte, uint64_t n_bytes, uint8_t *host_out)
+{
+	if (!c || (!host_out && n_bytes)) return DBGK_ERR_ARG;
+	if (!c->sealed) return DBGK_ERR_STATE;
+	const uint64_t bytes = c->tab_words * 4;
+	if (first_byte > bytes || n_bytes > bytes - first_byte) return DBGK_ERR_ARG;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	if (!n_bytes) return DBGK_OK;
+	HIPCHK(hipMemcpyAsync(host_out, (const uint8_t *)c->tab + first_byte, n_bytes, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DBGK_OK;
+}
+
+// frontier bound of a tree over d cycles: a node is its path, and a path is fixed by its <= 2 edits (4 bases each)
+static uint64_t corr_frontier_bound(uint64_t d) { return 1 + 4 * d + 8 * d * (d > 0 ? d - 1 : 0); }
+
+extern "C" int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *offsets, uint64_t n, char *out_seq,
+                               dbgk_corr_rec *out_rec)
+{
+	if (!c || !offsets || (n && (!out_rec || !seq || !out_seq))) return DBGK_ERR_ARG;
+	if (!c->sealed) return DBGK_ERR_STATE;
+	if (offsets[0] != 0 || n >= (1ull << 32)) return DBGK_ERR_ARG;
+	uint64_t max_len = 0;
+	for (uint64_t i = 0; i < n; ++i) {
+		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
+		max_len = std::max<uint64_t>(max_len, offsets[i + 1] - offsets[i]);
+	}
+	if (max_len >= (1ull << 29)) return DBGK_ERR_ARG;
+	c->last = dbgk_corr_stats{};
+	c->last.reads = n;
+	if (!n) return DBGK_OK;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	const uint64_t nb = offsets[n];
+	if (nb + 16 > c->cap_bytes || n > c->cap_reads) {
+		corr_free_batch(c);
+		c->cap_bytes = std::max<uint64_t>(nb + 16, 1 << 20);
+		c->cap_reads = std::max<uint64_t>(n, 1 << 14);
+		if (hipMalloc(&c->d_seq, c->cap_bytes) != hipSuccess || hipMalloc(&c->d_out, c->cap_bytes) != hipSuccess ||
+		    hipMalloc(&c->d_off, (c->cap_reads + 1) * 8) != hipSuccess ||
+		    hipMalloc(&c->d_rec, c->cap_reads * sizeof(dbgk_corr_rec)) != hipSuccess ||
+		    hipMalloc(&c->d_work, c->cap_reads * 4) != hipSuccess || hipMalloc(&c->d_ovf, c->cap_reads * 4) != hipSuccess) {
+			corr_free_batch(c);
+			return DBGK_ERR_NOMEM;
+		}
+	}
+	uint32_t *cnt = (uint32_t *)(c->d_cnt + 2); // [0] work list length, [1] overflow list length
+	HIPCHK(hipMemcpyAsync(c->d_seq, seq, nb, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
+	const uint32_t nr = (uint32_t)n;
+	const unsigned grid_cls = (unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)c->n_cu * 32);
+	HIPCHK(hipEventRecord(c->ev[0], c->stream));
+	hipLaunchKernelGGL(corr::k_corr_classify, dim3(grid_cls), dim3(256), 0, c->stream, (const uint8_t *)c->d_seq, c->d_off, nr, c->cp,
+	                   c->tab, c->d_out, c->d_rec, c->d_work, cnt);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(c->ev[1], c->stream));
+	const unsigned grid_fix = (unsigned)std::min<uint64_t>(n, (uint64_t)c->n_cu * 32);
+	hipLaunchKernelGGL(corr::k_corr_fix, dim3(grid_fix), dim3(corr::kWave), 0, c->stream, (const uint8_t *)c->d_seq, c->d_off, c->cp,
+	                   c->tab, c->d_out, c->d_rec, c->d_work, c->d_ovf, cnt);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(c->ev[2], c->stream));
+	uint32_t h_cnt[2] = {0, 0};
+	HIPCHK(hipMemcpyAsync(h_cnt, cnt, 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+	c->last.ms_classify = ms;
+	HIPCHK(hipEventElapsedTime(&ms, c->ev[1], c->ev[2]));
+	c->last.ms_correct = ms;
+	if (h_cnt[1]) {
+		// the overflow reads: a slice of global memory per wave, frontier capacity sized from -n and the read length
+		std::vector<uint32_t> ids(h_cnt[1]);
+		HIPCHK(hipMemcpy(ids.data(), c->d_ovf, ids.size() * 4, hipMemcpyDeviceToHost));
+		uint64_t ol = 0;
+		for (uint32_t i : ids) ol = std::max<uint64_t>(ol, offsets[i + 1] - offsets[i]);
+		const uint64_t cap = std::min<uint64_t>((uint64_t)c->p.max_tree_nodes, corr_frontier_bound(ol));
+		const uint64_t slice = (2 * cap * sizeof(corr::TNode) + (ol / 64 + 1) * 8 + ol + 255) & ~255ull;
+		const uint64_t budget = 1ull << 30;
+		const uint64_t waves = std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)h_cnt[1], budget / slice, (uint64_t)c->n_cu * 8}));
+		if (waves * slice > c->cap_scratch) {
+			(void)hipFree(c->d_scratch);
+			c->d_scratch = nullptr;
+			c->cap_scratch = 0;
+			if (hipMalloc(&c->d_scratch, waves * slice) != hipSuccess) return DBGK_ERR_NOMEM;
+			c->cap_scratch = waves * slice;
+		}
+		HIPCHK(hipEventRecord(c->ev[2], c->stream));
+		hipLaunchKernelGGL(corr::k_corr_overflow, dim3((unsigned)waves), dim3(corr::kWave), 0, c->stream, (const uint8_t *)c->d_seq,
+		                   c->d_off, c->cp, c->tab, c->d_out, c->d_rec, c->d_ovf, h_cnt[1], c->d_scratch, slice, (uint32_t)ol, (uint32_t)cap);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(c->ev[3], c->stream));
+	}
+	HIPCHK(hipMemcpyAsync(out_seq, c->d_out, nb, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(out_rec, c->d_rec, n * sizeof(dbgk_corr_rec), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (h_cnt[1]) {
+		HIPCHK(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+		c->last.ms_overflow = ms;
+	}
+	for (uint64_t i = 0; i < n; ++i) {
+		const dbgk_corr_rec &r = out_rec[i];
+		if (r.path > 2) {
+			g_last_error = "correct_error_reads: a tree frontier outgrew its bound in the overflow kernel";
+			return DBGK_ERR_CAPACITY;
+		}
+		c->last.by_classify += r.path == 0;
+		c->last.by_correct += r.path == 1;
+		c->last.by_overflow += r.path == 2;
+		c->last.node_limit_hits += r.node_limit_hits;
+	}
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out)
+{
+	if (!c || !out) return DBGK_ERR_ARG;
+	*out = c->last;
+	return DBGK_OK;
+}

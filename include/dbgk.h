@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define DBGK_ABI_VERSION 6
+#define DBGK_ABI_VERSION 7
 
 /* status codes */
 #define DBGK_OK               0
@@ -551,6 +551,60 @@ int dbgk_measure_copy_bandwidth2(dbgk_handle *h, size_t bytes, int iters, double
 /* random 64-byte gather over a buffer of `bytes` (the practical random-access ceiling of the engines
  * that touch one random node per k-mer occurrence): n_accesses sectors fetched, GB/s and G sectors/s             */
 int dbgk_measure_gather_bandwidth(dbgk_handle *h, size_t bytes, uint64_t n_accesses, double *gbps, double *gaccesses_per_s);
+
+/* ---- CORRECT: correct_error_reads on the GPU (ABI 7) ------------------------------------------------------------------
+ * The reference's correct_error_reads (correct_error/main_parallel_senior.cpp + correct.cpp): every read is corrected
+ * against the loaded 1-bit k-mer table, output identical to the reference's for the same table, reads and options.
+ * The table is built on the device either from the raw bits of a 1-bit .cz file (dbgk_corr_load_bits, then
+ * dbgk_corr_seal applies the loader's mirror: bit v -> rc(v) when v <= rc(v)) or from a finalized KFREQ handle
+ * (dbgk_corr_from_kfreq: bit(v) = count[canonical(v)] > cutoff, what kmerfreq -b 1 -m cutoff writes, loaded).   */
+typedef struct dbgk_corr dbgk_corr;
+
+typedef struct dbgk_corr_params {
+	int32_t k;                  /* -k, 1..19 (4^19 bits = 32 GiB); 1..18 for dbgk_corr_from_kfreq                     */
+	int32_t min_high_region;    /* -m HighFreqRegLenCutoff, >= 1 (the reference's default is 17 whatever -k is)     */
+	int32_t max_change;         /* -c Max_change_in_one_read, >= 0 (default 2)                                      */
+	int32_t further_trim;       /* -x Further_trim_len, >= 0 (default 17 whatever -k is)                            */
+	int32_t max_tree_nodes;     /* -n Max_node_in_BB_tree, 1 .. 2^26 - 1 (TreeNode.pointer is 26 bits; default 5000000) */
+	int32_t min_trimmed_len;    /* -r Min_trimmed_read_len, >= 0 (default 75)                                       */
+} dbgk_corr_params;
+
+/* per read */
+typedef struct dbgk_corr_rec {
+	uint32_t one_base;          /* bases changed by the one-base fix (correct_one_base)                             */
+	uint32_t tree;              /* bases changed by the branch-and-bound trees                                      */
+	uint32_t left_trim;         /* LeftEndTrim / RightEndTrim as the reference prints them                          */
+	uint32_t right_trim;
+	uint32_t node_limit_hits;   /* trees that reached -n ("node_vec_pos exceed Max_node_in_BB_tree")              */
+	uint8_t deleted;            /* IsDeleted                                                                        */
+	uint8_t path;               /* finished by 0: the classify kernel, 1: the correct kernel, 2: the overflow kernel */
+	uint8_t pad[2];
+} dbgk_corr_rec;
+
+typedef struct dbgk_corr_stats {
+	uint64_t reads;
+	uint64_t by_classify;       /* reads whose k-mers were all high (or that have none)                             */
+	uint64_t by_correct;        /* reads corrected with read, mask and tree frontier in LDS                         */
+	uint64_t by_overflow;       /* reads whose frontier or length did not fit in LDS                                */
+	uint64_t node_limit_hits;
+	double ms_classify, ms_correct, ms_overflow;  /* device time of each kernel of the last batch                  */
+} dbgk_corr_stats;
+
+/* DBGK_ERR_ARG on a bad parameter, before any device work */
+int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr **out);
+int dbgk_corr_destroy(dbgk_corr *c);
+/* n_bytes raw bytes of the file's table (its decompressed blocks) at byte first_byte; then seal once */
+int dbgk_corr_load_bits(dbgk_corr *c, uint64_t first_byte, uint64_t n_bytes, const uint8_t *host_bits);
+int dbgk_corr_seal(dbgk_corr *c);
+int dbgk_corr_from_kfreq(dbgk_corr *c, dbgk_handle *kfreq, uint32_t cutoff);
+/* Kmer_theory_total (4^k) and Kmer_hifreq_num of the loader */
+int dbgk_corr_table_stats(dbgk_corr *c, uint64_t *theory_total, uint64_t *hifreq);
+/* n_bytes bytes of the loaded table at byte first_byte (bit v: byte v / 8, bit 128 >> v % 8) */
+int dbgk_corr_export_bits(dbgk_corr *c, uint64_t first_byte, uint64_t n_bytes, uint8_t *host_out);
+/* n reads, read i = seq[offsets[i], offsets[i+1]) (offsets[0] == 0, each read < 2^29 bytes).  out_seq (offsets[n]
+ * bytes): every read after correction, untrimmed, at its input offset; out_rec: n records.  Input order is kept. */
+int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *offsets, uint64_t n, char *out_seq, dbgk_corr_rec *out_rec);
+int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out);
 
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
