@@ -99,6 +99,20 @@ class CorrStats(C.Structure):
                 ("ms_overflow", C.c_double)]
 
 
+class MapParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("seed_kmers", C.c_int32), ("min_read_len", C.c_int32), ("second_alignment", C.c_int32),
+                ("min_identity", C.c_double)]
+
+
+MAP_HIT_DTYPE = np.dtype([("contig", "<i4"), ("read_start", "<i4"), ("read_end", "<i4"), ("contig_start", "<i4"),
+                          ("contig_end", "<i4"), ("mismatches", "<i4"), ("align_len", "<i4"), ("direct", "<i4")])  # dbgk_map_hit
+
+
+class MapStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("by_lds", C.c_uint64), ("by_long", C.c_uint64), ("skipped", C.c_uint64),
+                ("windows_probed", C.c_uint64), ("ms_map", C.c_double), ("ms_long", C.c_double)]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -209,6 +223,12 @@ SYMBOLS = [
     ("dbgk_corr_export_bits", _i, [_vp, _u64, _u64, _vp]),
     ("dbgk_corr_reads", _i, [_vp, _vp, _vp, _u64, _vp, _vp]),
     ("dbgk_corr_batch_stats", _i, [_vp, C.POINTER(CorrStats)]),
+    ("dbgk_map_create", _i, [C.POINTER(MapParams), _i, C.POINTER(_vp)]),
+    ("dbgk_map_destroy", _i, [_vp]),
+    ("dbgk_map_set_contigs", _i, [_vp, _vp, _vp, _u64]),
+    ("dbgk_map_set_ramp", _i, [_vp, C.c_uint32]),
+    ("dbgk_map_reads", _i, [_vp, _vp, _vp, _u64, _vp]),
+    ("dbgk_map_batch_stats", _i, [_vp, C.POINTER(MapStats)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -899,3 +919,61 @@ class Corrector:
         s = CorrStats()
         _chk(lib().dbgk_corr_batch_stats(self._h, C.byref(s)), "dbgk_corr_batch_stats")
         return {f: getattr(s, f) for f, _ in CorrStats._fields_}
+
+
+def concat_sequences(seqs):
+    """a list of bytes / str -> (uint8 bases back to back, uint64 offsets[n + 1])"""
+    seqs = [q.encode() if isinstance(q, str) else bytes(q) for q in seqs]
+    offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    if seqs:
+        offsets[1:] = np.cumsum([len(q) for q in seqs], dtype=np.uint64)
+    return np.frombuffer(b"".join(seqs), dtype=np.uint8), offsets
+
+
+class Mapper:
+    """map_reads / map_pair on the GPU (MAP section of include/dbgk.h).  Defaults are the reference's.  set_contigs builds the
+    seed index and keeps the contig text on the device; map(bases, offsets) returns two hits per read (the second one only
+    with second_alignment, the map_reads mode)."""
+
+    def __init__(self, k=31, s=5, r=250, identity=0.97, second_alignment=False, device=0):
+        self._h = C.c_void_p()
+        _chk(lib().dbgk_map_create(C.byref(MapParams(k, s, r, 1 if second_alignment else 0, identity)), device, C.byref(self._h)),
+             "dbgk_map_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_contigs(self, contigs):
+        """a list of sequences (bytes / str); empty ones keep their index"""
+        bases, offsets = concat_sequences(contigs)
+        _chk(lib().dbgk_map_set_contigs(self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1),
+             "dbgk_map_set_contigs")
+
+    def set_ramp(self, first_chunk):
+        _chk(lib().dbgk_map_set_ramp(self._h, first_chunk), "dbgk_map_set_ramp")
+
+    def map(self, bases, offsets):
+        """-> MAP_HIT_DTYPE[n, 2]"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        hits = np.zeros((max(n, 1), 2), dtype=MAP_HIT_DTYPE)
+        _chk(lib().dbgk_map_reads(self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, n, hits.ctypes.data),
+             "dbgk_map_reads")
+        return hits[:n]
+
+    def map_sequences(self, reads):
+        return self.map(*concat_sequences(reads))
+
+    def batch_stats(self):
+        s = MapStats()
+        _chk(lib().dbgk_map_batch_stats(self._h, C.byref(s)), "dbgk_map_batch_stats")
+        return {f: getattr(s, f) for f, _ in MapStats._fields_}

@@ -11,6 +11,7 @@
 #include <new>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <emmintrin.h>
 #include <string>
 #include <thread>
@@ -23,6 +24,7 @@
 #include "dbgk_wide_kernels.h"
 #include "dbgk_wide_partition.h"
 #include "dbgk_correct.h"
+#include "dbgk_map.h"
 
 // dbgk_sort.hip
 extern "C" int dbgk_internal_sort_pairs(uint64_t *d_keys, uint64_t *d_vals, uint64_t n, hipStream_t stream);
@@ -447,3 +449,4 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_misc.h"
 #include "dbgk_comm.h"
 #include "dbgk_host_correct.h"
+#include "dbgk_host_map.h"

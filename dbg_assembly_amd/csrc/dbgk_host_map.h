@@ -1,0 +1,273 @@
+// MAP: host side of map_reads / map_pair on the GPU (include/dbgk.h, MAP section; kernels in dbgk_map.h)
+
+struct dbgk_map {
+	dbgk_map_params p{};
+	int device = 0;
+	int n_cu = 256;
+	uint32_t chunk0 = 4;          // first chunk of the seed scan's ramp (dbgk_map_set_ramp; profiles/map_measure.json)
+	hipStream_t stream = nullptr;
+	dbgk_handle *index = nullptr; // the finalized SEEDIDX handle of the contigs
+	uint8_t *d_ctg = nullptr;     // contig text as written
+	uint64_t *d_ctg_off = nullptr;
+	uint64_t n_contigs = 0;
+	// identity: accept[align_len] = the largest mis_match the reference's float test lets through, -1 = none
+	std::vector<int32_t> accept;
+	int32_t *d_accept = nullptr;
+	uint64_t cap_accept = 0;
+	// batch buffers, grown on demand
+	uint8_t *d_seq = nullptr;
+	uint64_t *d_off = nullptr;
+	mapk::Hit *d_hits = nullptr;
+	uint32_t *d_long = nullptr;
+	mapk::MapCounters *d_ctr = nullptr;
+	uint64_t cap_bytes = 0, cap_reads = 0;
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	dbgk_map_stats last{};
+};
+
+static_assert(sizeof(dbgk_map_hit) == 32 && sizeof(mapk::Hit) == 32, "dbgk_map_hit is eight int32");
+static_assert(sizeof(dbgk_map_params) == 24, "dbgk_map_params layout");
+
+// is_prime / find_next_prime of link_scaffold/kmerSet.cpp:56-79 (the float square root and the `i < max` bound included)
+static uint64_t map_find_next_prime(uint64_t num)
+{
+	auto is_prime = [](uint64_t n) {
+		if (n < 4) return true;
+		if (n % 2 == 0) return false;
+		const uint64_t max = (uint64_t)sqrtf((float)n);
+		for (uint64_t i = 3; i < max; i += 2)
+			if (n % i == 0) return false;
+		return true;
+	};
+	if (num % 2 == 0) num++;
+	while (!is_prime(num)) num += 2;
+	return num;
+}
+
+// the decision of map_reads.cpp:472 / map_pair.cpp:288 with the reference's own expression (map_func.cpp:298)
+static bool map_accepts(int mis_match, int align_len, double min_identity)
+{
+	float identity = 1.0 - (float)mis_match / align_len;
+	return !(identity < min_identity);
+}
+
+static void map_free_batch(dbgk_map *m)
+{
+	(void)hipFree(m->d_seq); (void)hipFree(m->d_off); (void)hipFree(m->d_hits); (void)hipFree(m->d_long);
+	m->d_seq = nullptr; m->d_off = nullptr; m->d_hits = nullptr; m->d_long = nullptr;
+	m->cap_bytes = m->cap_reads = 0;
+}
+
+static void map_free_contigs(dbgk_map *m)
+{
+	if (m->index) (void)dbgk_destroy(m->index);
+	m->index = nullptr;
+	(void)hipSetDevice(m->device);
+	(void)hipFree(m->d_ctg); (void)hipFree(m->d_ctg_off);
+	m->d_ctg = nullptr; m->d_ctg_off = nullptr;
+	m->n_contigs = 0;
+}
+
+extern "C" int dbgk_map_create(const dbgk_map_params *p, int device, dbgk_map **out)
+{
+	if (!p || !out) return DBGK_ERR_ARG;
+	*out = nullptr;
+	if (p->k < 1 || p->k > 31 || p->seed_kmers < 1 || p->seed_kmers > (1 << 29) || p->min_read_len < 0 ||
+	    (p->second_alignment != 0 && p->second_alignment != 1) || p->min_identity != p->min_identity || device < 0)
+		return DBGK_ERR_ARG;
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
+		g_last_error = "no usable HIP device";
+		return DBGK_ERR_HIP;
+	}
+	dbgk_map *m = new (std::nothrow) dbgk_map;
+	if (!m) return DBGK_ERR_NOMEM;
+	m->p = *p;
+	m->device = device;
+	int rc = DBGK_OK;
+	hipDeviceProp_t prop;
+	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
+		rc = DBGK_ERR_HIP;
+	}
+	if (!rc) m->n_cu = prop.multiProcessorCount;
+	if (!rc && hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
+	for (int i = 0; !rc && i < 4; ++i)
+		if (hipEventCreate(&m->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (!rc && hipMalloc(&m->d_ctr, sizeof(mapk::MapCounters)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (rc) {
+		dbgk_map_destroy(m);
+		return rc;
+	}
+	*out = m;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_map_destroy(dbgk_map *m)
+{
+	if (!m) return DBGK_ERR_ARG;
+	(void)hipSetDevice(m->device);
+	if (m->stream) (void)hipStreamSynchronize(m->stream);
+	map_free_batch(m);
+	map_free_contigs(m);
+	(void)hipFree(m->d_accept);
+	(void)hipFree(m->d_ctr);
+	for (auto &e : m->ev)
+		if (e) (void)hipEventDestroy(e);
+	if (m->stream) (void)hipStreamDestroy(m->stream);
+	delete m;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_map_set_ramp(dbgk_map *m, uint32_t first_chunk)
+{
+	if (!m || first_chunk < 1 || first_chunk > 64) return DBGK_ERR_ARG;
+	m->chunk0 = first_chunk;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_map_set_contigs(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_contigs)
+{
+	if (!m || !offsets || offsets[0] != 0 || n_contigs >= (1ull << 31)) return DBGK_ERR_ARG;
+	uint64_t longest = 0;
+	for (uint64_t i = 0; i < n_contigs; ++i) {
+		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
+		longest = std::max<uint64_t>(longest, offsets[i + 1] - offsets[i]);
+	}
+	const uint64_t total = offsets[n_contigs];
+	if ((total && !bases) || longest >= (1ull << 30)) return DBGK_ERR_ARG; // pos is a 30-bit field of the index
+	map_free_contigs(m);
+	// the index: init_kmerset(total * 3) of map_pair.cpp:122-124 -- find_next_prime unless below 3
+	dbgk_config cfg{};
+	cfg.kmer_size = m->p.k;
+	cfg.max_read_len = 0x7FFFFFFF;
+	cfg.table_slots = total * 3 < 3 ? 3 : map_find_next_prime(total * 3);
+	cfg.device_id = m->device;
+	cfg.engine = DBGK_ENGINE_SEEDIDX;
+	cfg.max_batch_bases = std::max<uint64_t>(std::max<uint64_t>(std::min<uint64_t>(total, 256ull << 20), longest) + 64, 1ull << 20);
+	int rc = dbgk_create(&cfg, &m->index);
+	if (rc) return rc;
+	if (n_contigs) rc = dbgk_push_reads(m->index, bases, offsets, n_contigs);
+	dbgk_stats st;
+	if (!rc) rc = dbgk_finalize(m->index, &st);
+	if (rc) {
+		map_free_contigs(m);
+		return rc;
+	}
+	HIPCHK(hipSetDevice(m->device));
+	if (hipMalloc(&m->d_ctg, total + 16) != hipSuccess || hipMalloc(&m->d_ctg_off, (n_contigs + 1) * 8) != hipSuccess) {
+		map_free_contigs(m);
+		return DBGK_ERR_NOMEM;
+	}
+	if (total) HIPCHK(hipMemcpyAsync(m->d_ctg, bases, total, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipMemcpyAsync(m->d_ctg_off, offsets, (n_contigs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	m->n_contigs = n_contigs;
+	return DBGK_OK;
+}
+
+// accept[] through align_len = max_len, on the device
+static int map_ensure_accept(dbgk_map *m, uint64_t max_len)
+{
+	if (m->accept.size() > max_len) return DBGK_OK;
+	const uint64_t from = m->accept.size();
+	m->accept.resize(max_len + 1);
+	for (uint64_t len = from; len <= max_len; ++len) {
+		// the test is monotone in mis_match: bisect for the last accepted count
+		int64_t lo = -1, hi = (int64_t)len; // lo: accepted (or none), hi: upper end of the candidates
+		while (lo < hi) {
+			const int64_t mid = lo + (hi - lo + 1) / 2;
+			if (len && map_accepts((int)mid, (int)len, m->p.min_identity)) lo = mid; else hi = mid - 1;
+		}
+		m->accept[len] = (int32_t)lo;
+	}
+	if (m->accept.size() > m->cap_accept) {
+		(void)hipFree(m->d_accept);
+		m->d_accept = nullptr;
+		m->cap_accept = 0;
+		const uint64_t cap = std::max<uint64_t>(m->accept.size(), 4096);
+		if (hipMalloc(&m->d_accept, cap * 4) != hipSuccess) return DBGK_ERR_NOMEM;
+		m->cap_accept = cap;
+	}
+	HIPCHK(hipMemcpyAsync(m->d_accept, m->accept.data(), m->accept.size() * 4, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_reads, dbgk_map_hit *out)
+{
+	if (!m || !offsets || (n_reads && !out)) return DBGK_ERR_ARG;
+	if (offsets[0] != 0 || n_reads >= (1ull << 31)) return DBGK_ERR_ARG;
+	uint64_t max_len = 0;
+	for (uint64_t i = 0; i < n_reads; ++i) {
+		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
+		max_len = std::max<uint64_t>(max_len, offsets[i + 1] - offsets[i]);
+	}
+	if (max_len >= (1ull << 31) || (n_reads && offsets[n_reads] && !bases)) return DBGK_ERR_ARG;
+	if (!m->index) return DBGK_ERR_STATE;
+	m->last = dbgk_map_stats{};
+	m->last.reads = n_reads;
+	if (!n_reads) return DBGK_OK;
+	HIPCHK(hipSetDevice(m->device));
+	int rc = map_ensure_accept(m, max_len);
+	if (rc) return rc;
+	const uint64_t nb = offsets[n_reads];
+	if (nb + 16 > m->cap_bytes || n_reads > m->cap_reads) {
+		map_free_batch(m);
+		m->cap_bytes = std::max<uint64_t>(nb + 16, 1 << 20);
+		m->cap_reads = std::max<uint64_t>(n_reads, 1 << 14);
+		if (hipMalloc(&m->d_seq, m->cap_bytes) != hipSuccess || hipMalloc(&m->d_off, (m->cap_reads + 1) * 8) != hipSuccess ||
+		    hipMalloc(&m->d_hits, m->cap_reads * 2 * sizeof(mapk::Hit)) != hipSuccess ||
+		    hipMalloc(&m->d_long, m->cap_reads * 4) != hipSuccess) {
+			map_free_batch(m);
+			return DBGK_ERR_NOMEM;
+		}
+	}
+	if (nb) HIPCHK(hipMemcpyAsync(m->d_seq, bases, nb, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipMemcpyAsync(m->d_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipMemsetAsync(m->d_ctr, 0, sizeof(mapk::MapCounters), m->stream));
+	const mapk::MapParams P{m->p.k, m->p.seed_kmers, m->p.min_read_len, m->p.second_alignment, m->chunk0, (uint32_t)m->accept.size()};
+	const mapk::MapIndex X{m->index->tref(), m->index->h_ctr->polyA_links, m->d_ctg, m->d_ctg_off, (uint32_t)m->n_contigs};
+	const uint32_t nr = (uint32_t)n_reads;
+	const uint64_t groups = (n_reads + mapk::kMapWaves - 1) / mapk::kMapWaves;
+	const unsigned grid = (unsigned)std::min<uint64_t>(groups, (uint64_t)m->n_cu * 32);
+	HIPCHK(hipEventRecord(m->ev[0], m->stream));
+	hipLaunchKernelGGL(mapk::k_map_reads<false>, dim3(grid), dim3(mapk::kMapWaves * 64), 0, m->stream, m->d_seq, m->d_off, nr, P, X,
+	                   (const int32_t *)m->d_accept, m->d_hits, m->d_long, m->d_ctr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(m->ev[1], m->stream));
+	mapk::MapCounters hc{};
+	HIPCHK(hipMemcpyAsync(&hc, m->d_ctr, sizeof hc, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	if (hc.n_long) { // reads beyond the LDS slice: the same code out of global memory
+		const unsigned grid_long = (unsigned)std::min<uint64_t>((hc.n_long + mapk::kMapWaves - 1) / mapk::kMapWaves, (uint64_t)m->n_cu * 32);
+		HIPCHK(hipEventRecord(m->ev[2], m->stream));
+		hipLaunchKernelGGL(mapk::k_map_reads<true>, dim3(grid_long), dim3(mapk::kMapWaves * 64), 0, m->stream, m->d_seq, m->d_off, nr, P, X,
+		                   (const int32_t *)m->d_accept, m->d_hits, m->d_long, m->d_ctr);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(m->ev[3], m->stream));
+		HIPCHK(hipMemcpyAsync(&hc, m->d_ctr, sizeof hc, hipMemcpyDeviceToHost, m->stream));
+	}
+	HIPCHK(hipMemcpyAsync(out, m->d_hits, n_reads * 2 * sizeof(mapk::Hit), hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
+	m->last.ms_map = ms;
+	if (hc.n_long) {
+		HIPCHK(hipEventElapsedTime(&ms, m->ev[2], m->ev[3]));
+		m->last.ms_long = ms;
+	}
+	m->last.by_lds = hc.by_lds;
+	m->last.by_long = hc.by_long;
+	m->last.skipped = hc.skipped;
+	m->last.windows_probed = hc.windows;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_map_batch_stats(dbgk_map *m, dbgk_map_stats *out)
+{
+	if (!m || !out) return DBGK_ERR_ARG;
+	*out = m->last;
+	return DBGK_OK;
+}

@@ -1,0 +1,238 @@
+// map_common.h -- what bin/map_reads and bin/map_pair share: the reference's option variables, its input formats
+// (link_scaffold/map_func.cpp:33-116), gzip line input and output, the mapper on the GPU (MAP section of include/dbgk.h)
+// and the formatting of one alignment.
+#pragma once
+#include <sys/stat.h>
+#include <unistd.h>
+#include <zlib.h>
+#include <cerrno>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "dbgk.h"
+
+using namespace std;
+
+static int KmerSize = 31;
+static double MinMapIdentity = 0.97;
+static int SeedKmerNum = 5;
+static int MinReadLen = 250;
+static int MinCtgLen = 125;
+static int Input_file_format = 1;
+static string Output_prefix = "./";
+
+static const uint64_t BatchReads = 1 << 20;   // reads per device batch
+static const uint64_t BatchBases = 256 << 20; // ... or this many bases, whichever comes first
+
+static void die(const char *what, int rc)
+{
+	cerr << what << " failed: " << dbgk_strerror(rc);
+	if (rc == DBGK_ERR_HIP) cerr << " [" << dbgk_last_error() << "]";
+	cerr << endl;
+	exit(1);
+}
+
+// split (map_func.cpp:33-53)
+static void split(const string &line, vector<string> &tokens, const char *delim)
+{
+	size_t i = 0;
+	for (;;) {
+		i = line.find_first_not_of(delim, i);
+		if (i == string::npos) break;
+		const size_t j = line.find_first_of(delim, i);
+		tokens.push_back(line.substr(i, j == string::npos ? string::npos : j - i));
+		if (j == string::npos) break;
+		i = j;
+	}
+}
+
+// reading_lib_file (map_func.cpp:57-77): '#' lines and empty lines skipped, the first token taken
+static void reading_lib_file(const string &lib_file, vector<string> &read_files)
+{
+	ifstream infile(lib_file.c_str());
+	if (!infile) cerr << "fail to open input file" << lib_file << endl;
+	string line;
+	while (getline(infile, line, '\n')) {
+		if (!line.empty() && line[0] == '#') continue;
+		vector<string> vec_line;
+		split(line, vec_line, " \t\n");
+		if (vec_line.empty()) continue;
+		read_files.push_back(vec_line[0]);
+	}
+}
+
+// read_contig_file (map_func.cpp:81-116): the id is the first token behind '>', sequences may span lines, a record
+// without sequence in front of another header is dropped, the last record is always pushed
+static void read_contig_file(const string &contig_seq_file, vector<string> &contig_ids, vector<string> &contig_seqs)
+{
+	ifstream infile(contig_seq_file.c_str());
+	if (!infile) cerr << "fail to open input file " << contig_seq_file << endl;
+	string id, seq_str, line;
+	while (getline(infile, line, '\n')) {
+		if (!line.empty() && line[0] == '>') {
+			if (seq_str.size() > 0) {
+				contig_ids.push_back(id);
+				contig_seqs.push_back(seq_str);
+			}
+			vector<string> vec_line;
+			split(line, vec_line, "> \t");
+			id = vec_line.empty() ? string() : vec_line[0];
+			seq_str.clear();
+		} else if (line.size() > 0) {
+			seq_str += line;
+		}
+	}
+	contig_ids.push_back(id);
+	contig_seqs.push_back(seq_str);
+}
+
+// the read id both programs print: first token of the header, "-" + the second one when there is one
+static string make_read_id(const string &head, const char *delim)
+{
+	vector<string> vec_head;
+	split(head, vec_head, delim);
+	if (vec_head.empty()) return string();
+	return vec_head.size() > 1 ? vec_head[0] + "-" + vec_head[1] : vec_head[0];
+}
+
+// getline over a plain or gzip file (what igzstream + getline read)
+struct LineReader {
+	gzFile f = nullptr;
+	vector<char> buf = vector<char>(1 << 20);
+	size_t pos = 0, len = 0;
+	bool eof = false;
+	explicit LineReader(const string &path)
+	{
+		f = gzopen(path.c_str(), "rb");
+		if (!f) cerr << "fail to open input file " << path << endl;
+	}
+	~LineReader() { if (f) gzclose(f); }
+	bool getline(string &s)
+	{
+		s.clear();
+		bool any = false;
+		for (;;) {
+			if (pos == len) {
+				if (eof || !f) return any;
+				const int n = gzread(f, buf.data(), (unsigned)buf.size());
+				if (n <= 0) { eof = true; return any; }
+				pos = 0;
+				len = (size_t)n;
+			}
+			any = true;
+			const char *b = buf.data() + pos;
+			const char *nl = (const char *)memchr(b, '\n', len - pos);
+			if (nl) {
+				s.append(b, nl - b);
+				pos += (nl - b) + 1;
+				return true;
+			}
+			s.append(b, len - pos);
+			pos = len;
+		}
+	}
+};
+
+// what ogzstream writes
+struct GzWriter {
+	gzFile f = nullptr;
+	explicit GzWriter(const string &path)
+	{
+		f = gzopen(path.c_str(), "wb");
+		if (!f) cerr << "fail to open output file " << path << endl;
+	}
+	~GzWriter() { if (f) gzclose(f); }
+	void write(const string &s)
+	{
+		if (f && !s.empty()) gzwrite(f, s.data(), (unsigned)s.size());
+	}
+};
+
+static const char *HeaderOne = "#read_id\tread_length\talign_read_start\talign_read_end\tcontig_id\tcontig_length\talign_contig_start\talign_contig_end\talign_direct\talign_identity%";
+static const char *HeaderTwo = "\tread_id\tread_length\talign2_read_start\talign2_read_end\tcontig2_id\tcontig2_length\talign2_contig_start\talign2_contig_end\talign2_direct\talign2_identity%";
+
+// the contigs as the programs hold them (short ones emptied, main of both programs) and the mapper that owns their index
+struct Contigs {
+	vector<string> ids, seqs;
+	dbgk_map *mapper = nullptr;
+
+	void load(const string &file, int second_alignment)
+	{
+		read_contig_file(file, ids, seqs);
+		uint64_t total_contig_num = 0, total_contig_len = 0;
+		for (size_t i = 0; i < seqs.size(); i++) {
+			if (seqs[i].size() >= (size_t)MinCtgLen) {
+				total_contig_num++;
+				total_contig_len += seqs[i].size();
+			} else {
+				seqs[i] = "";
+			}
+		}
+		cerr << "\nInput contig sequence number: " << total_contig_num << endl;
+		cerr << "Total contig sequence length: " << total_contig_len << endl;
+		dbgk_map_params p{KmerSize, SeedKmerNum, MinReadLen, second_alignment, MinMapIdentity};
+		int rc = dbgk_map_create(&p, 0, &mapper);
+		if (rc) die("dbgk_map_create", rc);
+		string bases;
+		vector<uint64_t> offsets(1, 0);
+		bases.reserve(total_contig_len);
+		for (const string &s : seqs) {
+			bases += s;
+			offsets.push_back(bases.size());
+		}
+		rc = dbgk_map_set_contigs(mapper, bases.data(), offsets.data(), seqs.size());
+		if (rc) die("dbgk_map_set_contigs", rc);
+		cerr << "Build the kmer hash finished" << endl;
+	}
+	~Contigs() { if (mapper) dbgk_map_destroy(mapper); }
+
+	// one alignment as both programs print it; the identity is the reference's float expression (map_func.cpp:298)
+	void row(ostream &o, const string &read_id, size_t read_len, const dbgk_map_hit &h) const
+	{
+		float identity = 1.0 - (float)h.mismatches / h.align_len;
+		o << read_id << "\t" << read_len << "\t" << h.read_start << "\t" << h.read_end << "\t" << ids[h.contig] << "\t" << seqs[h.contig].size()
+		  << "\t" << h.contig_start << "\t" << h.contig_end << "\t" << (char)h.direct << "\t" << identity * 100 << "%";
+	}
+};
+
+// a batch of reads on its way to the device
+struct ReadBatch {
+	string bases;
+	vector<uint64_t> offsets = vector<uint64_t>(1, 0);
+	vector<dbgk_map_hit> hits;
+	void add(const string &read)
+	{
+		bases += read;
+		offsets.push_back(bases.size());
+	}
+	size_t size() const { return offsets.size() - 1; }
+	bool full() const { return size() >= BatchReads || bases.size() >= BatchBases; }
+	void map(dbgk_map *m)
+	{
+		hits.resize(2 * size() + 2);
+		const int rc = dbgk_map_reads(m, bases.data(), offsets.data(), size(), hits.data());
+		if (rc) die("dbgk_map_reads", rc);
+	}
+	void clear()
+	{
+		bases.clear();
+		offsets.assign(1, 0);
+	}
+};
+
+static void make_output_dir()
+{
+	if (mkdir(Output_prefix.c_str(), 0777) != 0 && errno != EEXIST) cerr << "fail to create " << Output_prefix << endl;
+}
+
+static string base_name(const string &path)
+{
+	const size_t pos = path.find_last_of('/');
+	return pos == string::npos ? path : path.substr(pos + 1);
+}

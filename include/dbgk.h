@@ -606,6 +606,54 @@ int dbgk_corr_export_bits(dbgk_corr *c, uint64_t first_byte, uint64_t n_bytes, u
 int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *offsets, uint64_t n, char *out_seq, dbgk_corr_rec *out_rec);
 int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out);
 
+/* ---- MAP: map_reads / map_pair of the link_scaffold module on the GPU (additions to ABI 7) ----------------------------------
+ * The reference maps every read onto the contigs with a seed search over the contig k-mer index (get_align_seed,
+ * link_scaffold/map_func.cpp:181-237) and a gap-free extension with a mismatch count (extend_align_region, :241-299).  A mapper
+ * owns the finalized seed index of its contigs (built through DBGK_ENGINE_SEEDIDX with find_next_prime(3 * total length) slots,
+ * map_pair.cpp:122), the contig text as written (the extension compares raw bytes) and staging for read batches.  Every hit
+ * equals the reference's for the same contigs, read and options; the identity test is bit-equal to its float expression.   */
+typedef struct dbgk_map dbgk_map;
+
+typedef struct dbgk_map_params {
+	int32_t k;                  /* -k KmerSize, 1..31                                                               */
+	int32_t seed_kmers;         /* -s SeedKmerNum, >= 1                                                             */
+	int32_t min_read_len;       /* -r MinReadLen, >= 0: shorter reads get two empty hits                            */
+	int32_t second_alignment;   /* 1: map_reads (the rest of a read behind an accepted alignment is mapped again,
+	                               map_reads.cpp:480-498), 0: map_pair (every mate is simply a read)                */
+	double  min_identity;       /* -i MinMapIdentity                                                                */
+} dbgk_map_params;
+
+/* coordinates 1-based inclusive, as the reference prints them.  No seed: contig -1, coordinates -1, direct 'N', align_len 0.
+ * Seed found but identity below min_identity: contig -1, everything else as computed.                                   */
+typedef struct dbgk_map_hit {
+	int32_t contig;
+	int32_t read_start, read_end, contig_start, contig_end;
+	int32_t mismatches, align_len;  /* identity = 1.0 - (float)mismatches / align_len (map_func.cpp:298)             */
+	int32_t direct;                 /* 'F' / 'R' / 'N'                                                               */
+} dbgk_map_hit;
+
+typedef struct dbgk_map_stats {
+	uint64_t reads;
+	uint64_t by_lds;            /* reads mapped out of LDS (up to 1024 bases)                                       */
+	uint64_t by_long;           /* longer reads, mapped out of global memory                                        */
+	uint64_t skipped;           /* reads shorter than min_read_len or than k + seed_kmers                           */
+	uint64_t windows_probed;    /* first k-mers of a seed looked up in the index, speculative ones included         */
+	double ms_map, ms_long;     /* device time of each kernel of the last batch                                     */
+} dbgk_map_stats;
+
+/* DBGK_ERR_ARG on a bad parameter, before any device work */
+int dbgk_map_create(const dbgk_map_params *p, int device, dbgk_map **out);
+int dbgk_map_destroy(dbgk_map *m);
+/* n_contigs sequences back to back, contig i = bases[offsets[i], offsets[i+1]) (offsets[0] == 0, each < 2^30 bytes; empty ones
+ * keep their index and match nothing).  Replaces the mapper's earlier contigs.                                            */
+int dbgk_map_set_contigs(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_contigs);
+/* the seed scan looks at first_chunk (1..64) windows of a read at once, then at 64 at a time (default 4)                  */
+int dbgk_map_set_ramp(dbgk_map *m, uint32_t first_chunk);
+/* n_reads reads laid out like the contigs (each < 2^31 bytes); out: 2 hits per read, the second one only ever set with
+ * second_alignment.  Input order is kept.                                                                                 */
+int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_reads, dbgk_map_hit *out);
+int dbgk_map_batch_stats(dbgk_map *m, dbgk_map_stats *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
