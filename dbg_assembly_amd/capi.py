@@ -113,6 +113,18 @@ class MapStats(C.Structure):
                 ("windows_probed", C.c_uint64), ("ms_map", C.c_double), ("ms_long", C.c_double)]
 
 
+ADAPTER_HIT_DTYPE = np.dtype([("adapter", "<i4"), ("score", "<i4"), ("read_start", "<i4"), ("read_end", "<i4"),
+                              ("adapter_start", "<i4"), ("adapter_end", "<i4")])  # dbgk_adapter_hit
+
+LOWQUAL_BLOCK_DTYPE = np.dtype([("error_sum", "<f8"), ("start", "<i4"), ("length", "<i4"), ("trimmed", "<i4"),
+                                ("reserved", "<i4")])  # dbgk_lowqual_block
+
+
+class CleanStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("by_lds", C.c_uint64), ("by_global", C.c_uint64), ("hits", C.c_uint64),
+                ("cells", C.c_uint64), ("ms_lds", C.c_double), ("ms_global", C.c_double), ("ms_lowqual", C.c_double)]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -229,6 +241,12 @@ SYMBOLS = [
     ("dbgk_map_set_ramp", _i, [_vp, C.c_uint32]),
     ("dbgk_map_reads", _i, [_vp, _vp, _vp, _u64, _vp]),
     ("dbgk_map_batch_stats", _i, [_vp, C.POINTER(MapStats)]),
+    ("dbgk_clean_create", _i, [_i, C.POINTER(_vp)]),
+    ("dbgk_clean_destroy", _i, [_vp]),
+    ("dbgk_clean_set_adapters", _i, [_vp, _vp, _vp, _u64, C.c_int32]),
+    ("dbgk_clean_adapter", _i, [_vp, _vp, _vp, _u64, _vp]),
+    ("dbgk_clean_lowqual", _i, [_vp, _vp, _vp, _vp, _u64, C.c_double, C.c_int32, _vp]),
+    ("dbgk_clean_batch_stats", _i, [_vp, C.POINTER(CleanStats)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -977,3 +995,92 @@ class Mapper:
         s = MapStats()
         _chk(lib().dbgk_map_batch_stats(self._h, C.byref(s)), "dbgk_map_batch_stats")
         return {f: getattr(s, f) for f, _ in MapStats._fields_}
+
+
+class Cleaner:
+    """clean_adapter / clean_lowqual on the GPU (CLEAN section of include/dbgk.h).  The device returns one hit / one block per
+    read; trim_adapter and trim_lowqual cut the records the way the two programs do."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        _chk(lib().dbgk_clean_create(device, C.byref(self._h)), "dbgk_clean_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_clean_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_adapters(self, adapters, score_cutoff=12):
+        """contaminant sequences (bytes / str) in the order they are tried"""
+        bases, offsets = concat_sequences(adapters)
+        _chk(lib().dbgk_clean_set_adapters(self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data,
+                                           len(offsets) - 1, score_cutoff), "dbgk_clean_set_adapters")
+
+    def adapter(self, bases, offsets):
+        """-> ADAPTER_HIT_DTYPE[n]"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        hits = np.zeros(max(n, 1), dtype=ADAPTER_HIT_DTYPE)
+        _chk(lib().dbgk_clean_adapter(self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, n, hits.ctypes.data),
+             "dbgk_clean_adapter")
+        return hits[:n]
+
+    def lowqual(self, bases, quals, offsets, error_rate_cutoff=0.001, quality_shift=33):
+        """bases and quals share the offsets -> LOWQUAL_BLOCK_DTYPE[n]"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if bases.size != quals.size:
+            raise ValueError("bases and quals differ in size")
+        n = len(offsets) - 1
+        blocks = np.zeros(max(n, 1), dtype=LOWQUAL_BLOCK_DTYPE)
+        _chk(lib().dbgk_clean_lowqual(self._h, bases.ctypes.data if bases.size else None, quals.ctypes.data if quals.size else None,
+                                      offsets.ctypes.data, n, error_rate_cutoff, quality_shift, blocks.ctypes.data), "dbgk_clean_lowqual")
+        return blocks[:n]
+
+    def batch_stats(self):
+        s = CleanStats()
+        _chk(lib().dbgk_clean_batch_stats(self._h, C.byref(s)), "dbgk_clean_batch_stats")
+        return {f: getattr(s, f) for f, _ in CleanStats._fields_}
+
+    def trim_adapter(self, records, adapter_ids, min_len=75):
+        """records: (head, read, qual) as str; adapter_ids: the names of the sequences given to set_adapters.
+        -> (records as bin/clean_adapter writes them, hits)"""
+        hits = self.adapter(*concat_sequences([r[1] for r in records]))
+        out = []
+        for (head, read, qual), h in zip(records, hits.tolist()):
+            a, score, rs, re, as_, ae = h
+            if a >= 0:
+                read, qual = read[:rs - 1], qual[:rs - 1]
+                head += "   Aligned to adapter %s,  reads_pos: %d-%d, adapter_pos: %d-%d,   score: %d" % (adapter_ids[a], rs, re, as_, ae, score)
+            if len(read) < min_len:
+                read, qual, head = "", "", head + "   RemoveShort"
+            out.append((head, read, qual))
+        return out, hits
+
+    def trim_lowqual(self, records, error_rate_cutoff=0.001, quality_shift=33, min_len=75):
+        """-> (records as bin/clean_lowqual writes them, blocks)"""
+        recs = [(h, s, q) if len(s) == len(q) else (h, "", "") for h, s, q in records]
+        bases, offsets = concat_sequences([r[1] for r in recs])
+        quals, _ = concat_sequences([r[2].encode("latin-1") for r in recs])
+        blocks = self.lowqual(bases, quals, offsets, error_rate_cutoff, quality_shift)
+        out = []
+        for (head, read, qual), b in zip(recs, blocks.tolist()):
+            err, start, length, trimmed, _ = b
+            n = len(read)
+            qual = "".join(chr(quality_shift) if c == "N" else q for c, q in zip(read, qual))
+            head += "    RQ: " + ("%.17g" % (err / n * 100) if n else "-nan") + "%"
+            if trimmed:
+                head += "  TrimLowQual"
+                read, qual = (read[start - 1:start - 1 + length], qual[start - 1:start - 1 + length]) if start else ("", "")
+            if len(read) < min_len:
+                read, qual, head = "", "", head + "  FilterShort"
+            out.append((head, read, qual))
+        return out, blocks

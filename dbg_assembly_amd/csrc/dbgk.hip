@@ -25,6 +25,7 @@
 #include "dbgk_wide_partition.h"
 #include "dbgk_correct.h"
 #include "dbgk_map.h"
+#include "dbgk_clean.h"
 
 // dbgk_sort.hip
 extern "C" int dbgk_internal_sort_pairs(uint64_t *d_keys, uint64_t *d_vals, uint64_t n, hipStream_t stream);
@@ -450,3 +451,4 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_comm.h"
 #include "dbgk_host_correct.h"
 #include "dbgk_host_map.h"
+#include "dbgk_host_clean.h"

@@ -654,6 +654,54 @@ int dbgk_map_set_ramp(dbgk_map *m, uint32_t first_chunk);
 int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_reads, dbgk_map_hit *out);
 int dbgk_map_batch_stats(dbgk_map *m, dbgk_map_stats *out);
 
+/* ---- CLEAN: clean_adapter / clean_lowqual of the clean_illumina module on the GPU (additions to ABI 7) -------------------------
+ * clean_adapter aligns every read against every contaminant sequence with an ungapped local dynamic programme (match +1,
+ * everything else -2, N against N included; local_ungapped_aligning, clean_illumina/clean_adapter.cpp:94-157) and cuts the read at
+ * the first contaminant whose best score reaches the cutoff (:189-206).  clean_lowqual sums the per-base error probabilities of a
+ * read and, when their mean exceeds the cutoff, keeps the first longest block between break points (clean_lowqual.cpp:84-160).
+ * The device returns the numbers; headers, cutting, the short-read filter, statistics and gzip are the caller's (bin/clean_adapter,
+ * bin/clean_lowqual, capi.Cleaner).  Every number equals the reference's for the same input and options, doubles bit for bit.  */
+typedef struct dbgk_clean dbgk_clean;
+
+/* 1-based, inclusive, exactly the numbers the reference prints.  No contaminant reaches the cutoff: adapter -1, the rest 0.     */
+typedef struct dbgk_adapter_hit {
+	int32_t adapter;            /* index of the FIRST contaminant whose best score reaches the cutoff (not the best of all)    */
+	int32_t score;              /* score of the first cell in row-major order that holds that contaminant's maximum            */
+	int32_t read_start, read_end, adapter_start, adapter_end;
+} dbgk_adapter_hit;
+
+typedef struct dbgk_lowqual_block {
+	double  error_sum;          /* sum of the per-base error probabilities over the whole read, added left to right            */
+	int32_t start, length;      /* 1-based start and length of what is kept: the first longest block when trimmed (start 0:
+	                               nothing kept), else the whole read (start 1, or 0 for an empty read)                        */
+	int32_t trimmed;            /* 1 when error_sum > cutoff * read_len                                                        */
+	int32_t reserved;
+} dbgk_lowqual_block;
+
+typedef struct dbgk_clean_stats {  /* of the last dbgk_clean_adapter / dbgk_clean_lowqual call                                  */
+	uint64_t reads;
+	uint64_t by_lds;            /* reads aligned out of LDS (up to 1024 bases, contaminant set of up to 4096 bases)            */
+	uint64_t by_global;         /* longer reads, or every read of a larger contaminant set: the same code out of global memory */
+	uint64_t hits;              /* reads with a contaminant at or above the cutoff                                             */
+	uint64_t cells;             /* read_len * contaminant_len summed over every pair that was aligned                          */
+	double ms_lds, ms_global;   /* device time of each form of the adapter kernel                                              */
+	double ms_lowqual;          /* device time of the low-quality kernel                                                       */
+} dbgk_clean_stats;
+
+/* DBGK_ERR_HIP without a usable gfx950 device: there is no host fall-back                                                      */
+int dbgk_clean_create(int device, dbgk_clean **out);
+int dbgk_clean_destroy(dbgk_clean *c);
+/* n contaminant sequences in the order they are tried, back to back, sequence i = bases[offsets[i], offsets[i+1]) (offsets[0] == 0);
+ * score_cutoff >= 1 (-s; below 1 the reference reports coordinates it never set).  Replaces the earlier set.                    */
+int dbgk_clean_set_adapters(dbgk_clean *c, const char *bases, const uint64_t *offsets, uint64_t n, int32_t score_cutoff);
+/* n_reads reads laid out the same way (each < 2^30 bytes); out: one hit per read, input order kept                              */
+int dbgk_clean_adapter(dbgk_clean *c, const char *bases, const uint64_t *offsets, uint64_t n_reads, dbgk_adapter_hit *out);
+/* bases and quals share the offsets (a record whose two strings differ in length is the caller's to empty first);
+ * quality_shift 0..127 (-q), error_rate_cutoff -e; out: one block per read                                                      */
+int dbgk_clean_lowqual(dbgk_clean *c, const char *bases, const char *quals, const uint64_t *offsets, uint64_t n_reads,
+                       double error_rate_cutoff, int32_t quality_shift, dbgk_lowqual_block *out);
+int dbgk_clean_batch_stats(dbgk_clean *c, dbgk_clean_stats *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
