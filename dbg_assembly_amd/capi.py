@@ -125,6 +125,29 @@ class CleanStats(C.Structure):
                 ("cells", C.c_uint64), ("ms_lds", C.c_double), ("ms_global", C.c_double), ("ms_lowqual", C.c_double)]
 
 
+class LinkParams(C.Structure):
+    _fields_ = [("mate_pair", C.c_int32), ("pair_num_cut", C.c_int32), ("insert_size", C.c_int32)]
+
+
+LINK_PAIR_DTYPE = np.dtype([("contig1", "<i4"), ("start1", "<i4"), ("end1", "<i4"), ("contig2", "<i4"), ("start2", "<i4"),
+                            ("end2", "<i4"), ("direct1", "u1"), ("direct2", "u1"), ("pad", "u1", (2,)), ("reserved", "<i4")])  # dbgk_link_pair
+LINK_ENTRY_DTYPE = np.dtype([("target", "<u4"), ("freq", "<u4"), ("size", "<i8")])  # dbgk_link_entry
+LINK_ITEM_DTYPE = np.dtype([("contig", "<i4"), ("value", "<i4")])  # dbgk_link_item
+
+
+class LinkCounters(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("fr", "rf", "ff", "rr", "wrong")]
+
+
+class LinkSummary(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("lowfreq", "interleave", "repeat_nodes", "deleted", "scaffolds", "items")]
+
+
+class LinkTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("records", "kept", "entries", "links", "emit_bytes")] + \
+               [(f, C.c_double) for f in ("ms_orient", "ms_sort", "ms_reduce", "ms_chain", "ms_emit")]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -247,6 +270,18 @@ SYMBOLS = [
     ("dbgk_clean_adapter", _i, [_vp, _vp, _vp, _u64, _vp]),
     ("dbgk_clean_lowqual", _i, [_vp, _vp, _vp, _vp, _u64, C.c_double, C.c_int32, _vp]),
     ("dbgk_clean_batch_stats", _i, [_vp, C.POINTER(CleanStats)]),
+    ("dbgk_link_create", _i, [C.POINTER(LinkParams), _i, C.POINTER(_vp)]),
+    ("dbgk_link_destroy", _i, [_vp]),
+    ("dbgk_link_set_contigs", _i, [_vp, _vp, _u64]),
+    ("dbgk_link_add_pairs", _i, [_vp, _vp, _u64]),
+    ("dbgk_link_add_hits", _i, [_vp, _vp, _vp, _u64]),
+    ("dbgk_link_build", _i, [_vp]),
+    ("dbgk_link_export", _i, [_vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(LinkCounters)]),
+    ("dbgk_link_resolve", _i, [_vp, C.POINTER(LinkSummary)]),
+    ("dbgk_link_snapshot", _i, [_vp, C.c_int32, _vp, _vp, _vp]),
+    ("dbgk_link_layout", _i, [_vp, _vp, _vp, _vp]),
+    ("dbgk_link_emit", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("dbgk_link_batch_stats", _i, [_vp, C.POINTER(LinkTiming)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1084,3 +1119,145 @@ class Cleaner:
                 read, qual, head = "", "", head + "  FilterShort"
             out.append((head, read, qual))
         return out, blocks
+
+
+class Scaffolder:
+    """link_scaffold on the GPU (LINK section of include/dbgk.h).  Defaults are the reference's.  Contig c is node 2c + 1, its
+    reverse strand node 2c + 2.  set_contigs(lengths), add_pairs / add_hits in file order, build(), then table() for the links,
+    resolve() for the reference's clean-up passes and walk, layout() and emit() for the scaffolds."""
+
+    def __init__(self, mate_pair=0, pair_num_cut=3, insert_size=400, device=0):
+        self._h = C.c_void_p()
+        self.n_contigs = 0
+        _chk(lib().dbgk_link_create(C.byref(LinkParams(mate_pair, pair_num_cut, insert_size)), device, C.byref(self._h)),
+             "dbgk_link_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_link_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_contigs(self, lengths):
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        _chk(lib().dbgk_link_set_contigs(self._h, lengths.ctypes.data if lengths.size else None, len(lengths)), "dbgk_link_set_contigs")
+        self.n_contigs = len(lengths)
+        self._lengths = lengths.tolist()
+
+    def add_pairs(self, recs):
+        """LINK_PAIR_DTYPE records (any structured array with its first eight fields), behind those added so far"""
+        if recs.dtype != LINK_PAIR_DTYPE:
+            r = np.zeros(len(recs), dtype=LINK_PAIR_DTYPE)
+            for f in LINK_PAIR_DTYPE.names[:8]:
+                r[f] = recs[f]
+            recs = r
+        recs = np.ascontiguousarray(recs)
+        _chk(lib().dbgk_link_add_pairs(self._h, recs.ctypes.data if len(recs) else None, len(recs)), "dbgk_link_add_pairs")
+
+    def add_hits(self, hits1, hits2):
+        """what Mapper.map returned for the first and for the second mates (MAP_HIT_DTYPE[n, 2], or [n]: the first hits)"""
+        h = []
+        for x in (hits1, hits2):
+            x = np.asarray(x, dtype=MAP_HIT_DTYPE)
+            h.append(np.ascontiguousarray(x[:, 0] if x.ndim == 2 else x))
+        if len(h[0]) != len(h[1]):
+            raise ValueError("as many first mates as second mates")
+        n = len(h[0])
+        _chk(lib().dbgk_link_add_hits(self._h, h[0].ctypes.data if n else None, h[1].ctypes.data if n else None, n), "dbgk_link_add_hits")
+
+    def build(self):
+        _chk(lib().dbgk_link_build(self._h), "dbgk_link_build")
+
+    def table(self):
+        """-> first[2n + 2] (links of node i: links[first[i]:first[i + 1]] in chain order), LINK_ENTRY_DTYPE links, counters"""
+        n, ctr = C.c_uint64(), LinkCounters()
+        _chk(lib().dbgk_link_export(self._h, None, None, 0, C.byref(n), C.byref(ctr)), "dbgk_link_export")
+        first = np.zeros(2 * self.n_contigs + 2, dtype=np.uint64)
+        links = np.zeros(max(n.value, 1), dtype=LINK_ENTRY_DTYPE)
+        _chk(lib().dbgk_link_export(self._h, first.ctypes.data, links.ctypes.data, len(links), C.byref(n), C.byref(ctr)), "dbgk_link_export")
+        return first, links[:n.value], {"FR": ctr.fr, "RF": ctr.rf, "FF": ctr.ff, "RR": ctr.rr, "wrong": ctr.wrong}
+
+    def resolve(self):
+        s = LinkSummary()
+        _chk(lib().dbgk_link_resolve(self._h, C.byref(s)), "dbgk_link_resolve")
+        return {f: getattr(s, f) for f, _ in LinkSummary._fields_}
+
+    def snapshot(self, stage):
+        """stage 0: links.all, 1: links.uniq -> inlink, link (uint8 per node), links (the table's shape, cleared entries zero)"""
+        first, links, _ = self.table()
+        inlink = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
+        link = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
+        e = np.zeros(max(len(links), 1), dtype=LINK_ENTRY_DTYPE)
+        _chk(lib().dbgk_link_snapshot(self._h, stage, inlink.ctypes.data, link.ctypes.data, e.ctypes.data), "dbgk_link_snapshot")
+        return inlink, link, e[:len(links)]
+
+    def links_text(self, stage):
+        """the text of *.scaffold.links.all (stage 0) / *.scaffold.links.uniq (stage 1)"""
+        first = self.table()[0].tolist()
+        inlink, link, e = self.snapshot(stage)
+        t, f, z = e["target"].tolist(), e["freq"].tolist(), e["size"].tolist()
+        out = ["ctg_id\tincoming_link_num\toutgoing_link_num\tlinked_id,pair_num,sum_size,avg_size;\n"]
+        for i in range(1, 2 * self.n_contigs + 1):
+            row = "%d\t%d\t%d" % (i, inlink[i], link[i])
+            for j in range(first[i], first[i + 1]):
+                if f[j] > 0:
+                    avg = abs(z[j]) // f[j]
+                    row += "\t%d,%d,%d,%d" % (t[j], f[j], z[j], -avg if z[j] < 0 else avg)
+            out.append(row + "\n")
+        return "".join(out)
+
+    def layout(self):
+        """-> scaf_first[scaffolds + 1], LINK_ITEM_DTYPE items, repeat contigs: in output order"""
+        s = self.resolve()
+        scaf_first = np.zeros(s["scaffolds"] + 1, dtype=np.uint64)
+        items = np.zeros(max(s["items"], 1), dtype=LINK_ITEM_DTYPE)
+        repeats = np.zeros(max(s["repeat_nodes"], 1), dtype=np.int32)
+        _chk(lib().dbgk_link_layout(self._h, scaf_first.ctypes.data, items.ctypes.data, repeats.ctypes.data), "dbgk_link_layout")
+        return scaf_first, items[:s["items"]], repeats[:s["repeat_nodes"]]
+
+    def pos_tabs(self, names):
+        """the texts of *.scaffold.pos.tab and *.scaffold_repeat.pos.tab"""
+        scaf_first, items, repeats = self.layout()
+        lens = self._lengths
+        pos, sid = [], -1
+        for s in range(len(scaf_first) - 1):
+            sid += 2
+            pos.append(">scf_%d\n" % sid)
+            at = 0
+            for c, v in items[int(scaf_first[s]):int(scaf_first[s + 1])].tolist():
+                size = lens[c] if c >= 0 else v
+                pos.append("\t%s\t%d\t%d\t%d\t%s\n" % (names[c] if c >= 0 else "gap", at + 1, at + size, size,
+                                                        "N" if c < 0 else "R" if v else "F"))
+                at += size
+        rep = []
+        for c in repeats.tolist():
+            sid += 2
+            rep.append(">scf_%d\n\t%s\t1\t%d\t%d\tF\n" % (sid, names[c], lens[c], lens[c]))
+        return "".join(pos), "".join(rep)
+
+    def emit(self, contigs, items):
+        """the items back to back (contig as it is / reverse-complemented / a run of N) -> uint8 array"""
+        bases, offsets = contigs if isinstance(contigs, tuple) else concat_sequences(contigs)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        items = np.ascontiguousarray(items, dtype=LINK_ITEM_DTYPE)
+        n = C.c_uint64()
+        args = (self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1,
+                items.ctypes.data if len(items) else None, len(items))
+        rc = lib().dbgk_link_emit(*args, None, 0, C.byref(n))
+        if rc not in (0, ERR_CAPACITY):
+            _chk(rc, "dbgk_link_emit")
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        if n.value:
+            _chk(lib().dbgk_link_emit(*args, out.ctypes.data, n.value, C.byref(n)), "dbgk_link_emit")
+        return out[:n.value]
+
+    def batch_stats(self):
+        s = LinkTiming()
+        _chk(lib().dbgk_link_batch_stats(self._h, C.byref(s)), "dbgk_link_batch_stats")
+        return {f: getattr(s, f) for f, _ in LinkTiming._fields_}

@@ -702,6 +702,105 @@ int dbgk_clean_lowqual(dbgk_clean *c, const char *bases, const char *quals, cons
                        double error_rate_cutoff, int32_t quality_shift, dbgk_lowqual_block *out);
 int dbgk_clean_batch_stats(dbgk_clean *c, dbgk_clean_stats *out);
 
+/* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
+ * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
+ * links between contigs and walks the unambiguous ones into scaffolds.  Contig c (0-based, in the order of the contig file) is node
+ * 2c + 1, its reverse strand node 2c + 2 (the reference takes the node from the number in the contig's name, ctgStr2Id,
+ * link_scaffold/link_func.h:130; names whose number is not 2c + 1 are undefined there and the caller's to refuse).  Every record
+ * is oriented and filtered by its estimated gap (link_func.cpp:262-321 for pair ends, :367-423 for mate pairs) into two directed
+ * entries; entries of one (source, target) become one link that counts and sums its first 1023 records (:458-463); a node's links
+ * keep first-seen order.  That table is built on the device.  The reference's clean-up passes (remove_lowfreq_link_and_stat,
+ * remove_interleaving_links, remove_repeat_nodes, remove_links_from_deleted_nodes) and its walk are serial and order-dependent
+ * and run on the host, in its order (dbgk_link_resolve).  The scaffold sequences are written on the device (dbgk_link_emit).
+ * Every number equals the reference's for the same records and options.                                                      */
+typedef struct dbgk_link dbgk_link;
+
+typedef struct dbgk_link_params {
+	int32_t mate_pair;          /* -m IsMatePair: 0 pair ends, 1 mate pairs                                               */
+	int32_t pair_num_cut;       /* -n PairNumCut, >= 0 (default 3)                                                        */
+	int32_t insert_size;        /* -i InsertSize, > 0 (default 400)                                                       */
+} dbgk_link_params;
+
+/* one line of a 2ctg file as the link stage reads it */
+typedef struct dbgk_link_pair {
+	int32_t contig1, start1, end1;  /* mate 1: contig index, align_contig_start, align_contig_end                         */
+	int32_t contig2, start2, end2;  /* mate 2                                                                             */
+	uint8_t direct1, direct2;       /* 'F' / 'R'; any other byte makes the record a wrong link (a direction field of more
+	                                   than one character is one as well: pass any such byte)                             */
+	uint8_t pad[2];
+	int32_t reserved;
+} dbgk_link_pair;
+
+typedef struct dbgk_link_entry {    /* CtgLink (link_func.h:32-37); a cleared entry is all zero                           */
+	uint32_t target;
+	uint32_t freq;                  /* <= 1023                                                                            */
+	int64_t  size;                  /* sum of the gaps of the records counted in freq                                     */
+} dbgk_link_entry;
+
+typedef struct dbgk_link_counters { /* counted before the gap filter                                                     */
+	uint64_t fr, rf, ff, rr, wrong;
+} dbgk_link_counters;
+
+/* contig >= 0: the contig, value 0 as it is, value 1 reverse-complemented (seqKmer.cpp:72-81).  contig -1: a gap of value N's.    */
+typedef struct dbgk_link_item {
+	int32_t contig, value;
+} dbgk_link_item;
+
+typedef struct dbgk_link_summary {
+	uint64_t lowfreq;           /* LowFreq_link_num                                                                       */
+	uint64_t interleave;        /* Interleave_link_num                                                                    */
+	uint64_t repeat_nodes;      /* repeat_nodes_vec.size() / 2                                                            */
+	uint64_t deleted;           /* Deleted_link_num                                                                       */
+	uint64_t scaffolds;         /* total_scaffold_num                                                                     */
+	uint64_t items;             /* contigs and gaps of all scaffolds (dbgk_link_layout)                                   */
+} dbgk_link_summary;
+
+typedef struct dbgk_link_timing {
+	uint64_t records;           /* records and hit pairs added                                                            */
+	uint64_t kept;              /* ... that passed the gap filter                                                         */
+	uint64_t entries;           /* directed entries sorted (2 * kept)                                                     */
+	uint64_t links;             /* links of the table                                                                     */
+	uint64_t emit_bytes;        /* bytes the last dbgk_link_emit wrote                                                    */
+	double ms_orient;           /* device time of the orient / filter kernel, summed over the batches                     */
+	double ms_sort;             /* wall time of the two radix sorts (rocPRIM), their temporary buffers included           */
+	double ms_reduce, ms_chain; /* device time of the capped segmented reduce and of the chain write-out                  */
+	double ms_emit;             /* device time of the emit kernel of the last dbgk_link_emit                              */
+} dbgk_link_timing;
+
+/* DBGK_ERR_ARG on a bad parameter, before any device work; DBGK_ERR_HIP without a usable gfx950 device: no host fall-back  */
+int dbgk_link_create(const dbgk_link_params *p, int device, dbgk_link **out);
+int dbgk_link_destroy(dbgk_link *l);
+/* lengths of the n_contigs contigs (each < 2^31); the link stage needs nothing else of them.  Before the first record.   */
+int dbgk_link_set_contigs(dbgk_link *l, const uint32_t *lengths, uint64_t n_contigs);
+/* n more records, behind those of earlier calls: record order over all calls is file order, and the table depends on it.
+ * A contig index outside the contigs is DBGK_ERR_ARG.  Not after dbgk_link_build.                                         */
+int dbgk_link_add_pairs(dbgk_link *l, const dbgk_link_pair *recs, uint64_t n);
+/* n_pairs more records straight from the mapper: hits1[i] / hits2[i] are the first dbgk_map_hit of mate 1 / mate 2 of pair i
+ * as dbgk_map_reads returned them for the same contigs.  Pairs map_pair would not have written to the 2ctg file (a mate
+ * unmapped, both on one contig: map_pair.cpp:315-323) are passed over; the table equals that of dbgk_link_add_pairs on the
+ * parsed text of the others.                                                                                              */
+int dbgk_link_add_hits(dbgk_link *l, const dbgk_map_hit *hits1, const dbgk_map_hit *hits2, uint64_t n_pairs);
+/* groups and reduces the entries on the device; once                                                                      */
+int dbgk_link_build(dbgk_link *l);
+/* the table: links of node i are links[first[i] .. first[i + 1]) in the order of the reference's list, i = 0 .. 2 * n_contigs
+ * (first: 2 * n_contigs + 2 values).  *n_links is always set; first, links and counters may be NULL.                       */
+int dbgk_link_export(dbgk_link *l, uint64_t *first, dbgk_link_entry *links, uint64_t capacity, uint64_t *n_links,
+                     dbgk_link_counters *counters);
+/* the reference's passes and walk over a copy of the table (the table itself stays as built)                              */
+int dbgk_link_resolve(dbgk_link *l, dbgk_link_summary *out);
+/* stage 0: what *.scaffold.links.all shows (after remove_lowfreq_link_and_stat), stage 1: *.scaffold.links.uniq (after every
+ * pass).  inlink / link: 2 * n_contigs + 1 bytes each; links: the table's shape, cleared entries zero.  Any may be NULL.    */
+int dbgk_link_snapshot(dbgk_link *l, int32_t stage, uint8_t *inlink, uint8_t *link, dbgk_link_entry *links);
+/* the scaffolds in output order (by length as the reference's sort leaves them): scaffold s is items[scaf_first[s] ..
+ * scaf_first[s + 1]) (summary.scaffolds + 1 and summary.items values), then the repeat contigs in output order
+ * (summary.repeat_nodes values).  Scaffold ids run scf_1, scf_3, ... through the scaffolds and on through the repeats.     */
+int dbgk_link_layout(dbgk_link *l, uint64_t *scaf_first, dbgk_link_item *items, int32_t *repeats);
+/* scaffold read-out on the device: the items back to back into out (contig i = bases[offsets[i], offsets[i + 1]), offsets[0]
+ * == 0).  *out_len is the length of the whole; DBGK_ERR_CAPACITY when capacity is below it.                                */
+int dbgk_link_emit(dbgk_link *l, const char *bases, const uint64_t *offsets, uint64_t n_contigs, const dbgk_link_item *items,
+                   uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len);
+int dbgk_link_batch_stats(dbgk_link *l, dbgk_link_timing *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
