@@ -148,6 +148,28 @@ class LinkTiming(C.Structure):
                [(f, C.c_double) for f in ("ms_orient", "ms_sort", "ms_reduce", "ms_chain", "ms_emit")]
 
 
+class FillParams(C.Structure):
+    _fields_ = [("pair_num_cut", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+FILL_RECORD_DTYPE = np.dtype([("read", "<i4"), ("read_len", "<i4"), ("align1_end", "<i4"), ("align2_start", "<i4"), ("contig1", "<i4"),
+                              ("contig2", "<i4"), ("direct1", "u1"), ("direct2", "u1"), ("pad", "u1", (2,)), ("reserved", "<i4")])  # dbgk_fill_record
+FILL_GAPSTAT_DTYPE = np.dtype([("contig_lo", "<i4"), ("contig_hi", "<i4"), ("mode", "<i4"), ("mode_freq", "<i4"), ("total_freq", "<i4"),
+                               ("variance", "<i4")])  # dbgk_fill_gapstat
+FILL_ITEM_DTYPE = np.dtype([("contig", "<i4"), ("reversed", "<i4"), ("length", "<u4"), ("gap", "<i4"), ("cons_off", "<u8")])  # dbgk_fill_item
+FILL_GAP_DTYPE = np.dtype([("mode", "<i4"), ("mode_freq", "<i4"), ("total_freq", "<i4"), ("variance", "<i4"), ("identity", "<f4"),
+                           ("host_path", "<i4")])  # dbgk_fill_gap
+
+
+class FillSummary(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("lowfreq", "repeat_nodes", "deleted", "scaffolds", "items", "gaps", "filled", "cons_bytes", "pairs")]
+
+
+class FillTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("records", "pooled", "links", "cons_bytes", "span_bytes", "emit_bytes")] + \
+               [(f, C.c_double) for f in ("ms_orient", "ms_sort", "ms_table", "ms_gapstat", "ms_consensus", "ms_emit")]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -282,6 +304,20 @@ SYMBOLS = [
     ("dbgk_link_layout", _i, [_vp, _vp, _vp, _vp]),
     ("dbgk_link_emit", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("dbgk_link_batch_stats", _i, [_vp, C.POINTER(LinkTiming)]),
+    ("dbgk_fill_create", _i, [C.POINTER(FillParams), _i, C.POINTER(_vp)]),
+    ("dbgk_fill_destroy", _i, [_vp]),
+    ("dbgk_fill_set_contigs", _i, [_vp, _vp, _u64]),
+    ("dbgk_fill_set_reads", _i, [_vp, _vp, _vp, _u64]),
+    ("dbgk_fill_add_records", _i, [_vp, _vp, _u64]),
+    ("dbgk_fill_add_hits", _i, [_vp, _vp, _u64, _u64]),
+    ("dbgk_fill_build", _i, [_vp]),
+    ("dbgk_fill_export", _i, [_vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(LinkCounters)]),
+    ("dbgk_fill_gap_stats", _i, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    ("dbgk_fill_resolve", _i, [_vp, C.POINTER(FillSummary)]),
+    ("dbgk_fill_snapshot", _i, [_vp, C.c_int32, _vp, _vp, _vp]),
+    ("dbgk_fill_layout", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    ("dbgk_fill_emit", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("dbgk_fill_batch_stats", _i, [_vp, C.POINTER(FillTiming)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1261,3 +1297,173 @@ class Scaffolder:
         s = LinkTiming()
         _chk(lib().dbgk_link_batch_stats(self._h, C.byref(s)), "dbgk_link_batch_stats")
         return {f: getattr(s, f) for f, _ in LinkTiming._fields_}
+
+
+def float9(x):
+    """boost::lexical_cast<string>(float): nine significant digits"""
+    return "%.9g" % float(np.float32(x))
+
+
+class GapFiller:
+    """link_contig on the GPU (FILL section of include/dbgk.h).  Contig c is node 2c + 1, its reverse strand node 2c + 2.
+    set_contigs(lengths), set_reads(reads), add_records / add_hits in file order, build(), then table() and gap_stats(),
+    resolve() for the passes, the walk and the gap consensus, layout() and emit() for the scafftigs."""
+
+    def __init__(self, pair_num_cut=3, device=0):
+        self._h = C.c_void_p()
+        self.n_contigs = 0
+        _chk(lib().dbgk_fill_create(C.byref(FillParams(pair_num_cut, (C.c_int32 * 3)(0, 0, 0))), device, C.byref(self._h)), "dbgk_fill_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_fill_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_contigs(self, lengths):
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        _chk(lib().dbgk_fill_set_contigs(self._h, lengths.ctypes.data if lengths.size else None, len(lengths)), "dbgk_fill_set_contigs")
+        self.n_contigs = len(lengths)
+        self._lengths = lengths.tolist()
+
+    def set_reads(self, reads):
+        """a list of sequences (bytes / str), or (bases, offsets): the reads the records' `read` fields index"""
+        bases, offsets = reads if isinstance(reads, tuple) else concat_sequences(reads)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        _chk(lib().dbgk_fill_set_reads(self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1),
+             "dbgk_fill_set_reads")
+
+    def add_records(self, recs):
+        """FILL_RECORD_DTYPE records (any structured array with its first eight fields), behind those added so far"""
+        if recs.dtype != FILL_RECORD_DTYPE:
+            r = np.zeros(len(recs), dtype=FILL_RECORD_DTYPE)
+            for f in FILL_RECORD_DTYPE.names[:8]:
+                r[f] = recs[f]
+            recs = r
+        recs = np.ascontiguousarray(recs)
+        _chk(lib().dbgk_fill_add_records(self._h, recs.ctypes.data if len(recs) else None, len(recs)), "dbgk_fill_add_records")
+
+    def add_hits(self, hits, first_read=0):
+        """what Mapper.map (second_alignment) returned for reads first_read, first_read + 1, ...: MAP_HIT_DTYPE[n, 2]"""
+        hits = np.ascontiguousarray(np.asarray(hits, dtype=MAP_HIT_DTYPE))
+        if hits.ndim != 2 or hits.shape[1] != 2:
+            raise ValueError("two hits per read")
+        n = len(hits)
+        _chk(lib().dbgk_fill_add_hits(self._h, hits.ctypes.data if n else None, n, first_read), "dbgk_fill_add_hits")
+
+    def build(self):
+        _chk(lib().dbgk_fill_build(self._h), "dbgk_fill_build")
+
+    def table(self):
+        """-> first[2n + 2], LINK_ENTRY_DTYPE links in chain order, counters (as Scaffolder.table)"""
+        n, ctr = C.c_uint64(), LinkCounters()
+        _chk(lib().dbgk_fill_export(self._h, None, None, 0, C.byref(n), C.byref(ctr)), "dbgk_fill_export")
+        first = np.zeros(2 * self.n_contigs + 2, dtype=np.uint64)
+        links = np.zeros(max(n.value, 1), dtype=LINK_ENTRY_DTYPE)
+        _chk(lib().dbgk_fill_export(self._h, first.ctypes.data, links.ctypes.data, len(links), C.byref(n), C.byref(ctr)), "dbgk_fill_export")
+        return first, links[:n.value], {"FR": ctr.fr, "RF": ctr.rf, "FF": ctr.ff, "RR": ctr.rr, "wrong": ctr.wrong}
+
+    def gap_stats(self):
+        """-> FILL_GAPSTAT_DTYPE per contig pair with a record, ascending by (contig_lo, contig_hi)"""
+        n = C.c_uint64()
+        _chk(lib().dbgk_fill_gap_stats(self._h, None, 0, C.byref(n)), "dbgk_fill_gap_stats")
+        out = np.zeros(max(n.value, 1), dtype=FILL_GAPSTAT_DTYPE)
+        _chk(lib().dbgk_fill_gap_stats(self._h, out.ctypes.data, len(out), C.byref(n)), "dbgk_fill_gap_stats")
+        return out[:n.value]
+
+    def resolve(self):
+        s = FillSummary()
+        _chk(lib().dbgk_fill_resolve(self._h, C.byref(s)), "dbgk_fill_resolve")
+        return {f: getattr(s, f) for f, _ in FillSummary._fields_}
+
+    def snapshot(self, stage):
+        first, links, _ = self.table()
+        inlink = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
+        link = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
+        e = np.zeros(max(len(links), 1), dtype=LINK_ENTRY_DTYPE)
+        _chk(lib().dbgk_fill_snapshot(self._h, stage, inlink.ctypes.data, link.ctypes.data, e.ctypes.data), "dbgk_fill_snapshot")
+        return inlink, link, e[:len(links)]
+
+    def links_text(self, stage):
+        """the text of *.contig_R.links.all (stage 0) / *.contig_R.links.uniq (stage 1)"""
+        first = self.table()[0].tolist()
+        inlink, link, e = self.snapshot(stage)
+        t, f, z = e["target"].tolist(), e["freq"].tolist(), e["size"].tolist()
+        out = ["ctg_id\tincoming_link_num\toutgoing_link_num\tlinked_id,pair_num,sum_size,avg_size;\n"]
+        for i in range(1, 2 * self.n_contigs + 1):
+            row = "%d\t%d\t%d" % (i, inlink[i], link[i])
+            for j in range(first[i], first[i + 1]):
+                if f[j] > 0:
+                    avg = abs(z[j]) // f[j]
+                    row += "\t%d,%d,%d,%d" % (t[j], f[j], z[j], -avg if z[j] < 0 else avg)
+            out.append(row + "\n")
+        return "".join(out)
+
+    def layout(self):
+        """-> scaf_first[scafftigs + 1], FILL_ITEM_DTYPE items, FILL_GAP_DTYPE gaps, repeat contigs, consensus bytes: in output order"""
+        s = self.resolve()
+        scaf_first = np.zeros(s["scaffolds"] + 1, dtype=np.uint64)
+        items = np.zeros(max(s["items"], 1), dtype=FILL_ITEM_DTYPE)
+        gaps = np.zeros(max(s["gaps"], 1), dtype=FILL_GAP_DTYPE)
+        repeats = np.zeros(max(s["repeat_nodes"], 1), dtype=np.int32)
+        cons = np.zeros(max(s["cons_bytes"], 1), dtype=np.uint8)
+        _chk(lib().dbgk_fill_layout(self._h, scaf_first.ctypes.data, items.ctypes.data, gaps.ctypes.data, repeats.ctypes.data, cons.ctypes.data),
+             "dbgk_fill_layout")
+        return scaf_first, items[:s["items"]], gaps[:s["gaps"]], repeats[:s["repeat_nodes"]], cons[:s["cons_bytes"]]
+
+    def pos_tabs(self, names):
+        """the texts of *.contig_R.pos.tab and *.contig_R.repeat.pos.tab"""
+        scaf_first, items, gaps, repeats, _ = self.layout()
+        lens = self._lengths
+        pos = ["#scafftig_id\tblock_id\tblock_start\tblock_end\tblock_size\tdirection\tgapsize_mode_freq\tgapsize_total_freq\t"
+               "gapsize_variance\tgapseq_identity\n"]
+        sid = -1
+        G = gaps.tolist()
+        for s in range(len(scaf_first) - 1):
+            sid += 2
+            pos.append(">sct_%d\n" % sid)
+            at = 0
+            for c, rev, length, g, _ in items[int(scaf_first[s]):int(scaf_first[s + 1])].tolist():
+                if c >= 0:
+                    pos.append("\t%s\t%d\t%d\t%d\t%s\n" % (names[c], at + 1, at + length, length, "R" if rev else "F"))
+                    at += length
+                else:
+                    mode, mf, tf, var, ident, _ = G[g]
+                    if mode <= 0:
+                        pos.append("\tgap\t%d\t%d\t%d\tN\t%d\t%d\t%d\n" % (at, at, mode, mf, tf, var))
+                    else:
+                        pos.append("\tgap\t%d\t%d\t%d\tN\t%d\t%d\t%d\t%s\n" % (at + 1, at + length, length, mf, tf, var, float9(ident)))
+                        at += length
+        rep = []
+        for c in repeats.tolist():
+            sid += 2
+            rep.append(">sct_%d\n\t%s\t1\t%d\t%d\tF\n" % (sid, names[c], lens[c], lens[c]))
+        return "".join(pos), "".join(rep)
+
+    def emit(self, contigs, items):
+        """the items back to back (contig or its reverse complement, possibly cut; consensus bytes of a gap) -> uint8 array"""
+        bases, offsets = contigs if isinstance(contigs, tuple) else concat_sequences(contigs)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        items = np.ascontiguousarray(items, dtype=FILL_ITEM_DTYPE)
+        n = C.c_uint64()
+        args = (self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1,
+                items.ctypes.data if len(items) else None, len(items))
+        rc = lib().dbgk_fill_emit(*args, None, 0, C.byref(n))
+        if rc not in (0, ERR_CAPACITY):
+            _chk(rc, "dbgk_fill_emit")
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        if n.value:
+            _chk(lib().dbgk_fill_emit(*args, out.ctypes.data, n.value, C.byref(n)), "dbgk_fill_emit")
+        return out[:n.value]
+
+    def timing(self):
+        s = FillTiming()
+        _chk(lib().dbgk_fill_batch_stats(self._h, C.byref(s)), "dbgk_fill_batch_stats")
+        return {f: getattr(s, f) for f, _ in FillTiming._fields_}

@@ -488,35 +488,47 @@ static void link_sort_by_len(std::vector<LenIdx> &v)
 
 } // namespace
 
+// the reference's passes over a copy of the table, the two snapshots, and its walk: per scaffold the combined list node, gap, node,
+// ... (read_out_scaffold, link_scaffold.cpp:317-357; read_out_scaffinfo, link_contig.cpp:676-726).  link_contig runs no
+// interleaving pass (interleave false).
+static void link_passes_and_walk(dbgk_link *l, bool interleave, LinkPasses &S, std::vector<std::vector<int>> &combs)
+{
+	S.remove_lowfreq_link_and_stat();
+	l->snap_links[0] = S.e; l->snap_link[0] = S.link; l->snap_inlink[0] = S.inlink;
+	if (interleave) S.remove_interleaving_links();
+	S.remove_repeat_nodes();
+	S.remove_links_from_deleted_nodes();
+	l->snap_links[1] = S.e; l->snap_link[1] = S.link; l->snap_inlink[1] = S.inlink;
+	for (uint64_t i = 1; i < S.n_nodes; i += 2) {
+		if (S.del[i] == 1) continue;
+		S.del[i] = 1;
+		S.del[i + 1] = 1;
+		std::vector<int> right, left, comb;
+		if (S.link[i] == 1) S.get_linear_seq((uint32_t)i, right);
+		if (S.link[i + 1] == 1) {
+			S.get_linear_seq((uint32_t)i + 1, left);
+			std::reverse(left.begin(), left.end());
+			for (size_t k = 0; k < left.size(); k += 2) left[k] = (int)LinkPasses::pair_id((uint32_t)left[k]);
+		}
+		comb = left;
+		comb.push_back((int)i);
+		comb.insert(comb.end(), right.begin(), right.end());
+		combs.push_back(std::move(comb));
+	}
+}
+
 extern "C" int dbgk_link_resolve(dbgk_link *l, dbgk_link_summary *out)
 {
 	if (!l || !out) return DBGK_ERR_ARG;
 	if (!l->built) return DBGK_ERR_STATE;
 	if (!l->resolved) {
 		LinkPasses S(l);
-		S.remove_lowfreq_link_and_stat();
-		l->snap_links[0] = S.e; l->snap_link[0] = S.link; l->snap_inlink[0] = S.inlink;
-		S.remove_interleaving_links();
-		S.remove_repeat_nodes();
-		S.remove_links_from_deleted_nodes();
-		l->snap_links[1] = S.e; l->snap_link[1] = S.link; l->snap_inlink[1] = S.inlink;
-		// read_out_scaffold (link_scaffold.cpp:317-357) and generate_scaffold (:427-463)
+		std::vector<std::vector<int>> combs;
+		link_passes_and_walk(l, true, S, combs);
+		// generate_scaffold (link_scaffold.cpp:427-463)
 		std::vector<std::vector<dbgk_link_item>> scaf;
 		std::vector<LenIdx> order;
-		for (uint64_t i = 1; i < S.n_nodes; i += 2) {
-			if (S.del[i] == 1) continue;
-			S.del[i] = 1;
-			S.del[i + 1] = 1;
-			std::vector<int> right, left, comb;
-			if (S.link[i] == 1) S.get_linear_seq((uint32_t)i, right);
-			if (S.link[i + 1] == 1) {
-				S.get_linear_seq((uint32_t)i + 1, left);
-				std::reverse(left.begin(), left.end());
-				for (size_t k = 0; k < left.size(); k += 2) left[k] = (int)LinkPasses::pair_id((uint32_t)left[k]);
-			}
-			comb = left;
-			comb.push_back((int)i);
-			comb.insert(comb.end(), right.begin(), right.end());
+		for (const std::vector<int> &comb : combs) {
 			std::vector<dbgk_link_item> items;
 			uint64_t len = 0;
 			for (size_t k = 0; k < comb.size(); ++k) {

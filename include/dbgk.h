@@ -801,6 +801,117 @@ int dbgk_link_emit(dbgk_link *l, const char *bases, const uint64_t *offsets, uin
                    uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len);
 int dbgk_link_batch_stats(dbgk_link *l, dbgk_link_timing *out);
 
+/* ---- FILL: link_contig of the link_scaffold module on the GPU (additions to ABI 7) ---------------------------------------------
+ * link_contig links contigs by single reads whose two ends map_reads placed on two different contigs (the lines of
+ * *.map_reads.2ctg.gz) and fills every gap with the consensus of the reads that span it (link_scaffold/link_contig.cpp).  The link
+ * table is the LINK one without a gap filter (parse_read_ends_map_file, link_func.cpp:141-220); of the passes only
+ * remove_lowfreq_link_and_stat, remove_repeat_nodes and remove_links_from_deleted_nodes run.  Per unordered contig pair the
+ * records of every direction, wrong ones included, are pooled into the gap statistics (decide_gap_size, link_contig.cpp:569-610);
+ * a gap of the layout whose mode is > 0 gets the per-column consensus of the reads whose own gap is the mode (:456-510), any
+ * other gap cuts the left contig (:437-454).  Table, statistics, consensus and read-out are computed on the device; passes and
+ * walk on the host.  Every number and byte equals the reference's for the same records, reads and options.                  */
+typedef struct dbgk_fill dbgk_fill;
+
+typedef struct dbgk_fill_params {
+	int32_t pair_num_cut;       /* -n PairNumCut, >= 0 (default 3)                                                        */
+	int32_t reserved[3];        /* 0                                                                                      */
+} dbgk_fill_params;
+
+/* one line of a map_reads 2ctg file as link_contig reads it; gap = align2_start - align1_end - 1 in int arithmetic */
+typedef struct dbgk_fill_record {
+	int32_t read;               /* index into the reads of dbgk_fill_set_reads                                            */
+	int32_t read_len;           /* field 1 as written (not used by the reference either)                                  */
+	int32_t align1_end;         /* field 3                                                                                */
+	int32_t align2_start;       /* field 12                                                                               */
+	int32_t contig1, contig2;   /* contig indices of fields 4 and 14                                                      */
+	uint8_t direct1, direct2;   /* fields 8 and 18: 'F' / 'R'; any other byte makes the record a wrong link (it adds no
+	                               entries to the table and still counts in the gap statistics)                           */
+	uint8_t pad[2];
+	int32_t reserved;
+} dbgk_fill_record;
+
+/* the statistics of one unordered contig pair (GapSize, link_contig.cpp:601-607) */
+typedef struct dbgk_fill_gapstat {
+	int32_t contig_lo, contig_hi;   /* contig_lo < contig_hi                                                              */
+	int32_t mode;                   /* most frequent gap, the smallest one on equal frequency                             */
+	int32_t mode_freq, total_freq;
+	int32_t variance;               /* sum |gap - mode| * freq / total_freq, int arithmetic                               */
+} dbgk_fill_gapstat;
+
+/* contig >= 0: the first `length` bases of the contig as it is (reversed 0) or of its reverse complement (reversed 1); length is
+ * the contig's unless the junction behind it cuts it.  contig -1: the junction behind a contig, gap = index into the gaps of
+ * dbgk_fill_layout, length consensus bytes at cons_off of the consensus buffer (length 0 for a mode <= 0).                  */
+typedef struct dbgk_fill_item {
+	int32_t  contig, reversed;
+	uint32_t length;
+	int32_t  gap;
+	uint64_t cons_off;
+} dbgk_fill_item;
+
+typedef struct dbgk_fill_gap {      /* one junction of the layout                                                         */
+	int32_t mode, mode_freq, total_freq, variance;
+	float   identity;               /* ConsensusSupportRate, summed in float column by column; 0 for a mode <= 0          */
+	int32_t host_path;              /* 1: a spanning slice held a byte other than A C G T N, the columns were counted on
+	                                   the host (same result)                                                             */
+} dbgk_fill_gap;
+
+typedef struct dbgk_fill_summary {
+	uint64_t lowfreq, repeat_nodes, deleted, scaffolds, items;   /* as dbgk_link_summary                                 */
+	uint64_t gaps;              /* junctions of the layout                                                                */
+	uint64_t filled;            /* ... with a mode > 0                                                                    */
+	uint64_t cons_bytes;        /* consensus bytes of all filled gaps                                                     */
+	uint64_t pairs;             /* contig pairs with statistics                                                           */
+} dbgk_fill_summary;
+
+typedef struct dbgk_fill_timing {
+	uint64_t records;           /* records and reads with hits added                                                      */
+	uint64_t pooled;            /* records in the gap statistics                                                          */
+	uint64_t links;
+	uint64_t cons_bytes, span_bytes;   /* consensus bytes written / slice bytes read by the consensus kernel             */
+	uint64_t emit_bytes;
+	double ms_orient;           /* device time of the orient kernel, summed over the batches                              */
+	double ms_sort;             /* wall time of all radix sorts (table and statistics)                                    */
+	double ms_table;            /* device time of reduce and chain                                                        */
+	double ms_gapstat;          /* device time of the gather and run-length / segmented-reduce kernels                    */
+	double ms_consensus;        /* device time of the consensus kernel                                                    */
+	double ms_emit;             /* device time of the emit kernel of the last dbgk_fill_emit                              */
+} dbgk_fill_timing;
+
+/* DBGK_ERR_ARG on a bad parameter, before any device work; DBGK_ERR_HIP without a usable gfx950 device: no host fall-back  */
+int dbgk_fill_create(const dbgk_fill_params *p, int device, dbgk_fill **out);
+int dbgk_fill_destroy(dbgk_fill *f);
+int dbgk_fill_set_contigs(dbgk_fill *f, const uint32_t *lengths, uint64_t n_contigs);
+/* the reads the records point into, read i = bases[offsets[i], offsets[i + 1]) (offsets[0] == 0); before dbgk_fill_resolve */
+int dbgk_fill_set_reads(dbgk_fill *f, const char *bases, const uint64_t *offsets, uint64_t n_reads);
+/* n more records behind those of earlier calls (record order over all calls is file order).  A contig index outside the contigs,
+ * contig1 == contig2 or a negative read index is DBGK_ERR_ARG.  Not after dbgk_fill_build.                                */
+int dbgk_fill_add_records(dbgk_fill *f, const dbgk_fill_record *recs, uint64_t n);
+/* n_reads more records straight from the mapper: hits[2 i], hits[2 i + 1] as dbgk_map_reads (second_alignment) returned them for
+ * read first_read + i of dbgk_fill_set_reads.  Reads map_reads would not have written to the 2ctg file (a hit with contig -1, both
+ * on one contig: map_reads.cpp:59-73) are passed over; table and statistics equal those of the parsed text of the others.   */
+int dbgk_fill_add_hits(dbgk_fill *f, const dbgk_map_hit *hits, uint64_t n_reads, uint64_t first_read);
+/* the link table and the gap statistics, on the device; once */
+int dbgk_fill_build(dbgk_fill *f);
+/* as dbgk_link_export */
+int dbgk_fill_export(dbgk_fill *f, uint64_t *first, dbgk_link_entry *links, uint64_t capacity, uint64_t *n_links,
+                     dbgk_link_counters *counters);
+/* the statistics of every contig pair with a record, ascending by (contig_lo, contig_hi).  *n_pairs is always set.          */
+int dbgk_fill_gap_stats(dbgk_fill *f, dbgk_fill_gapstat *out, uint64_t capacity, uint64_t *n_pairs);
+/* passes, walk, layout and the consensus of every filled gap.  A spanning read whose slice [align1_end, align1_end + gap) does
+ * not lie inside its read is DBGK_ERR_ARG (undefined in the reference); no byte of that gap is read on the device.          */
+int dbgk_fill_resolve(dbgk_fill *f, dbgk_fill_summary *out);
+/* as dbgk_link_snapshot: stage 0 *.contig_R.links.all, stage 1 *.contig_R.links.uniq */
+int dbgk_fill_snapshot(dbgk_fill *f, int32_t stage, uint8_t *inlink, uint8_t *link, dbgk_link_entry *links);
+/* scafftigs in output order: scaf_first (summary.scaffolds + 1), items (summary.items), gaps (summary.gaps), repeat contigs
+ * (summary.repeat_nodes), consensus (summary.cons_bytes bytes, copied from the device buffer).  Any may be NULL.  Ids run
+ * sct_1, sct_3, ... through the scafftigs and on through the repeats.                                                     */
+int dbgk_fill_layout(dbgk_fill *f, uint64_t *scaf_first, dbgk_fill_item *items, dbgk_fill_gap *gaps, int32_t *repeats, char *consensus);
+/* read-out on the device: the items back to back into out; gap items take their bytes from the consensus buffer of
+ * dbgk_fill_resolve on the device.  *out_len is the length of the whole; DBGK_ERR_CAPACITY when capacity is below it.      */
+int dbgk_fill_emit(dbgk_fill *f, const char *bases, const uint64_t *offsets, uint64_t n_contigs, const dbgk_fill_item *items,
+                   uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len);
+int dbgk_fill_batch_stats(dbgk_fill *f, dbgk_fill_timing *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
