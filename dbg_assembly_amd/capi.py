@@ -1157,20 +1157,23 @@ class Cleaner:
         return out, blocks
 
 
-class Scaffolder:
-    """link_scaffold on the GPU (LINK section of include/dbgk.h).  Defaults are the reference's.  Contig c is node 2c + 1, its
-    reverse strand node 2c + 2.  set_contigs(lengths), add_pairs / add_hits in file order, build(), then table() for the links,
-    resolve() for the reference's clean-up passes and walk, layout() and emit() for the scaffolds."""
+class _LinkTable:
+    """What Scaffolder and GapFiller share: the handle, the contigs, the link table and the emit of the C calls that start with
+    `_prefix` ("dbgk_link" / "dbgk_fill"); `_item_dtype` is the dtype of the items emit() takes."""
+    _prefix = None
+    _item_dtype = None
 
-    def __init__(self, mate_pair=0, pair_num_cut=3, insert_size=400, device=0):
-        self._h = C.c_void_p()
-        self.n_contigs = 0
-        _chk(lib().dbgk_link_create(C.byref(LinkParams(mate_pair, pair_num_cut, insert_size)), device, C.byref(self._h)),
-             "dbgk_link_create")
+    def _call(self, name, *args, ok=(0,)):
+        """lib().<_prefix>_<name>(handle, *args) -> its return code, checked under the C function's name unless it is in `ok`"""
+        what = "%s_%s" % (self._prefix, name)
+        rc = getattr(lib(), what)(self._h, *args)
+        if rc not in ok:
+            _chk(rc, what)
+        return rc
 
     def close(self):
         if self._h:
-            lib().dbgk_link_destroy(self._h)
+            getattr(lib(), self._prefix + "_destroy")(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -1181,9 +1184,72 @@ class Scaffolder:
 
     def set_contigs(self, lengths):
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
-        _chk(lib().dbgk_link_set_contigs(self._h, lengths.ctypes.data if lengths.size else None, len(lengths)), "dbgk_link_set_contigs")
+        self._call("set_contigs", lengths.ctypes.data if lengths.size else None, len(lengths))
         self.n_contigs = len(lengths)
         self._lengths = lengths.tolist()
+
+    def table(self):
+        """-> first[2n + 2] (links of node i: links[first[i]:first[i + 1]] in chain order), LINK_ENTRY_DTYPE links, counters"""
+        n, ctr = C.c_uint64(), LinkCounters()
+        self._call("export", None, None, 0, C.byref(n), C.byref(ctr))
+        first = np.zeros(2 * self.n_contigs + 2, dtype=np.uint64)
+        links = np.zeros(max(n.value, 1), dtype=LINK_ENTRY_DTYPE)
+        self._call("export", first.ctypes.data, links.ctypes.data, len(links), C.byref(n), C.byref(ctr))
+        return first, links[:n.value], {"FR": ctr.fr, "RF": ctr.rf, "FF": ctr.ff, "RR": ctr.rr, "wrong": ctr.wrong}
+
+    def snapshot(self, stage):
+        """stage 0: links.all, 1: links.uniq -> inlink, link (uint8 per node), links (the table's shape, cleared entries zero)"""
+        first, links, _ = self.table()
+        inlink = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
+        link = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
+        e = np.zeros(max(len(links), 1), dtype=LINK_ENTRY_DTYPE)
+        self._call("snapshot", stage, inlink.ctypes.data, link.ctypes.data, e.ctypes.data)
+        return inlink, link, e[:len(links)]
+
+    def links_text(self, stage):
+        """the text of the program's *.links.all (stage 0) / *.links.uniq (stage 1)"""
+        first = self.table()[0].tolist()
+        inlink, link, e = self.snapshot(stage)
+        t, f, z = e["target"].tolist(), e["freq"].tolist(), e["size"].tolist()
+        out = ["ctg_id\tincoming_link_num\toutgoing_link_num\tlinked_id,pair_num,sum_size,avg_size;\n"]
+        for i in range(1, 2 * self.n_contigs + 1):
+            row = "%d\t%d\t%d" % (i, inlink[i], link[i])
+            for j in range(first[i], first[i + 1]):
+                if f[j] > 0:
+                    avg = abs(z[j]) // f[j]
+                    row += "\t%d,%d,%d,%d" % (t[j], f[j], z[j], -avg if z[j] < 0 else avg)
+            out.append(row + "\n")
+        return "".join(out)
+
+    def emit(self, contigs, items):
+        """the items back to back -> uint8 array.  A Scaffolder's item is a contig as it is, reverse-complemented, or a run of N; a
+        GapFiller's a contig or its reverse complement, possibly cut, or the consensus bytes of a gap."""
+        bases, offsets = contigs if isinstance(contigs, tuple) else concat_sequences(contigs)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        items = np.ascontiguousarray(items, dtype=self._item_dtype)
+        n = C.c_uint64()
+        args = (bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1,
+                items.ctypes.data if len(items) else None, len(items))
+        self._call("emit", *args, None, 0, C.byref(n), ok=(0, ERR_CAPACITY))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        if n.value:
+            self._call("emit", *args, out.ctypes.data, n.value, C.byref(n))
+        return out[:n.value]
+
+
+class Scaffolder(_LinkTable):
+    """link_scaffold on the GPU (LINK section of include/dbgk.h).  Defaults are the reference's.  Contig c is node 2c + 1, its
+    reverse strand node 2c + 2.  set_contigs(lengths), add_pairs / add_hits in file order, build(), then table() for the links,
+    resolve() for the reference's clean-up passes and walk, layout() and emit() for the scaffolds."""
+    _prefix = "dbgk_link"
+    _item_dtype = LINK_ITEM_DTYPE
+
+    def __init__(self, mate_pair=0, pair_num_cut=3, insert_size=400, device=0):
+        self._h = C.c_void_p()
+        self.n_contigs = 0
+        _chk(lib().dbgk_link_create(C.byref(LinkParams(mate_pair, pair_num_cut, insert_size)), device, C.byref(self._h)),
+             "dbgk_link_create")
 
     def add_pairs(self, recs):
         """LINK_PAIR_DTYPE records (any structured array with its first eight fields), behind those added so far"""
@@ -1209,43 +1275,10 @@ class Scaffolder:
     def build(self):
         _chk(lib().dbgk_link_build(self._h), "dbgk_link_build")
 
-    def table(self):
-        """-> first[2n + 2] (links of node i: links[first[i]:first[i + 1]] in chain order), LINK_ENTRY_DTYPE links, counters"""
-        n, ctr = C.c_uint64(), LinkCounters()
-        _chk(lib().dbgk_link_export(self._h, None, None, 0, C.byref(n), C.byref(ctr)), "dbgk_link_export")
-        first = np.zeros(2 * self.n_contigs + 2, dtype=np.uint64)
-        links = np.zeros(max(n.value, 1), dtype=LINK_ENTRY_DTYPE)
-        _chk(lib().dbgk_link_export(self._h, first.ctypes.data, links.ctypes.data, len(links), C.byref(n), C.byref(ctr)), "dbgk_link_export")
-        return first, links[:n.value], {"FR": ctr.fr, "RF": ctr.rf, "FF": ctr.ff, "RR": ctr.rr, "wrong": ctr.wrong}
-
     def resolve(self):
         s = LinkSummary()
         _chk(lib().dbgk_link_resolve(self._h, C.byref(s)), "dbgk_link_resolve")
         return {f: getattr(s, f) for f, _ in LinkSummary._fields_}
-
-    def snapshot(self, stage):
-        """stage 0: links.all, 1: links.uniq -> inlink, link (uint8 per node), links (the table's shape, cleared entries zero)"""
-        first, links, _ = self.table()
-        inlink = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
-        link = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
-        e = np.zeros(max(len(links), 1), dtype=LINK_ENTRY_DTYPE)
-        _chk(lib().dbgk_link_snapshot(self._h, stage, inlink.ctypes.data, link.ctypes.data, e.ctypes.data), "dbgk_link_snapshot")
-        return inlink, link, e[:len(links)]
-
-    def links_text(self, stage):
-        """the text of *.scaffold.links.all (stage 0) / *.scaffold.links.uniq (stage 1)"""
-        first = self.table()[0].tolist()
-        inlink, link, e = self.snapshot(stage)
-        t, f, z = e["target"].tolist(), e["freq"].tolist(), e["size"].tolist()
-        out = ["ctg_id\tincoming_link_num\toutgoing_link_num\tlinked_id,pair_num,sum_size,avg_size;\n"]
-        for i in range(1, 2 * self.n_contigs + 1):
-            row = "%d\t%d\t%d" % (i, inlink[i], link[i])
-            for j in range(first[i], first[i + 1]):
-                if f[j] > 0:
-                    avg = abs(z[j]) // f[j]
-                    row += "\t%d,%d,%d,%d" % (t[j], f[j], z[j], -avg if z[j] < 0 else avg)
-            out.append(row + "\n")
-        return "".join(out)
 
     def layout(self):
         """-> scaf_first[scaffolds + 1], LINK_ITEM_DTYPE items, repeat contigs: in output order"""
@@ -1276,23 +1309,6 @@ class Scaffolder:
             rep.append(">scf_%d\n\t%s\t1\t%d\t%d\tF\n" % (sid, names[c], lens[c], lens[c]))
         return "".join(pos), "".join(rep)
 
-    def emit(self, contigs, items):
-        """the items back to back (contig as it is / reverse-complemented / a run of N) -> uint8 array"""
-        bases, offsets = contigs if isinstance(contigs, tuple) else concat_sequences(contigs)
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        items = np.ascontiguousarray(items, dtype=LINK_ITEM_DTYPE)
-        n = C.c_uint64()
-        args = (self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1,
-                items.ctypes.data if len(items) else None, len(items))
-        rc = lib().dbgk_link_emit(*args, None, 0, C.byref(n))
-        if rc not in (0, ERR_CAPACITY):
-            _chk(rc, "dbgk_link_emit")
-        out = np.zeros(max(n.value, 1), dtype=np.uint8)
-        if n.value:
-            _chk(lib().dbgk_link_emit(*args, out.ctypes.data, n.value, C.byref(n)), "dbgk_link_emit")
-        return out[:n.value]
-
     def batch_stats(self):
         s = LinkTiming()
         _chk(lib().dbgk_link_batch_stats(self._h, C.byref(s)), "dbgk_link_batch_stats")
@@ -1304,32 +1320,17 @@ def float9(x):
     return "%.9g" % float(np.float32(x))
 
 
-class GapFiller:
+class GapFiller(_LinkTable):
     """link_contig on the GPU (FILL section of include/dbgk.h).  Contig c is node 2c + 1, its reverse strand node 2c + 2.
     set_contigs(lengths), set_reads(reads), add_records / add_hits in file order, build(), then table() and gap_stats(),
     resolve() for the passes, the walk and the gap consensus, layout() and emit() for the scafftigs."""
+    _prefix = "dbgk_fill"
+    _item_dtype = FILL_ITEM_DTYPE
 
     def __init__(self, pair_num_cut=3, device=0):
         self._h = C.c_void_p()
         self.n_contigs = 0
         _chk(lib().dbgk_fill_create(C.byref(FillParams(pair_num_cut, (C.c_int32 * 3)(0, 0, 0))), device, C.byref(self._h)), "dbgk_fill_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_fill_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def set_contigs(self, lengths):
-        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
-        _chk(lib().dbgk_fill_set_contigs(self._h, lengths.ctypes.data if lengths.size else None, len(lengths)), "dbgk_fill_set_contigs")
-        self.n_contigs = len(lengths)
-        self._lengths = lengths.tolist()
 
     def set_reads(self, reads):
         """a list of sequences (bytes / str), or (bases, offsets): the reads the records' `read` fields index"""
@@ -1360,15 +1361,6 @@ class GapFiller:
     def build(self):
         _chk(lib().dbgk_fill_build(self._h), "dbgk_fill_build")
 
-    def table(self):
-        """-> first[2n + 2], LINK_ENTRY_DTYPE links in chain order, counters (as Scaffolder.table)"""
-        n, ctr = C.c_uint64(), LinkCounters()
-        _chk(lib().dbgk_fill_export(self._h, None, None, 0, C.byref(n), C.byref(ctr)), "dbgk_fill_export")
-        first = np.zeros(2 * self.n_contigs + 2, dtype=np.uint64)
-        links = np.zeros(max(n.value, 1), dtype=LINK_ENTRY_DTYPE)
-        _chk(lib().dbgk_fill_export(self._h, first.ctypes.data, links.ctypes.data, len(links), C.byref(n), C.byref(ctr)), "dbgk_fill_export")
-        return first, links[:n.value], {"FR": ctr.fr, "RF": ctr.rf, "FF": ctr.ff, "RR": ctr.rr, "wrong": ctr.wrong}
-
     def gap_stats(self):
         """-> FILL_GAPSTAT_DTYPE per contig pair with a record, ascending by (contig_lo, contig_hi)"""
         n = C.c_uint64()
@@ -1381,29 +1373,6 @@ class GapFiller:
         s = FillSummary()
         _chk(lib().dbgk_fill_resolve(self._h, C.byref(s)), "dbgk_fill_resolve")
         return {f: getattr(s, f) for f, _ in FillSummary._fields_}
-
-    def snapshot(self, stage):
-        first, links, _ = self.table()
-        inlink = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
-        link = np.zeros(2 * self.n_contigs + 1, dtype=np.uint8)
-        e = np.zeros(max(len(links), 1), dtype=LINK_ENTRY_DTYPE)
-        _chk(lib().dbgk_fill_snapshot(self._h, stage, inlink.ctypes.data, link.ctypes.data, e.ctypes.data), "dbgk_fill_snapshot")
-        return inlink, link, e[:len(links)]
-
-    def links_text(self, stage):
-        """the text of *.contig_R.links.all (stage 0) / *.contig_R.links.uniq (stage 1)"""
-        first = self.table()[0].tolist()
-        inlink, link, e = self.snapshot(stage)
-        t, f, z = e["target"].tolist(), e["freq"].tolist(), e["size"].tolist()
-        out = ["ctg_id\tincoming_link_num\toutgoing_link_num\tlinked_id,pair_num,sum_size,avg_size;\n"]
-        for i in range(1, 2 * self.n_contigs + 1):
-            row = "%d\t%d\t%d" % (i, inlink[i], link[i])
-            for j in range(first[i], first[i + 1]):
-                if f[j] > 0:
-                    avg = abs(z[j]) // f[j]
-                    row += "\t%d,%d,%d,%d" % (t[j], f[j], z[j], -avg if z[j] < 0 else avg)
-            out.append(row + "\n")
-        return "".join(out)
 
     def layout(self):
         """-> scaf_first[scafftigs + 1], FILL_ITEM_DTYPE items, FILL_GAP_DTYPE gaps, repeat contigs, consensus bytes: in output order"""
@@ -1445,23 +1414,6 @@ class GapFiller:
             sid += 2
             rep.append(">sct_%d\n\t%s\t1\t%d\t%d\tF\n" % (sid, names[c], lens[c], lens[c]))
         return "".join(pos), "".join(rep)
-
-    def emit(self, contigs, items):
-        """the items back to back (contig or its reverse complement, possibly cut; consensus bytes of a gap) -> uint8 array"""
-        bases, offsets = contigs if isinstance(contigs, tuple) else concat_sequences(contigs)
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        items = np.ascontiguousarray(items, dtype=FILL_ITEM_DTYPE)
-        n = C.c_uint64()
-        args = (self._h, bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1,
-                items.ctypes.data if len(items) else None, len(items))
-        rc = lib().dbgk_fill_emit(*args, None, 0, C.byref(n))
-        if rc not in (0, ERR_CAPACITY):
-            _chk(rc, "dbgk_fill_emit")
-        out = np.zeros(max(n.value, 1), dtype=np.uint8)
-        if n.value:
-            _chk(lib().dbgk_fill_emit(*args, out.ctypes.data, n.value, C.byref(n)), "dbgk_fill_emit")
-        return out[:n.value]
 
     def timing(self):
         s = FillTiming()

@@ -77,10 +77,7 @@ extern "C" int dbgk_fill_set_contigs(dbgk_fill *f, const uint32_t *lengths, uint
 
 extern "C" int dbgk_fill_set_reads(dbgk_fill *f, const char *bases, const uint64_t *offsets, uint64_t n_reads)
 {
-	if (!f || !offsets || offsets[0] != 0 || n_reads >= (1ull << 31)) return DBGK_ERR_ARG;
-	for (uint64_t i = 0; i < n_reads; ++i)
-		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
-	if (offsets[n_reads] && !bases) return DBGK_ERR_ARG;
+	if (!f || n_reads >= (1ull << 31) || !link_check_offsets(bases, offsets, n_reads)) return DBGK_ERR_ARG;
 	if (f->resolved) return DBGK_ERR_STATE;
 	dbgk_link *l = f->L;
 	HIPCHK(hipSetDevice(l->device));
@@ -430,7 +427,7 @@ extern "C" int dbgk_fill_resolve(dbgk_fill *f, dbgk_fill_summary *out)
 	}
 	f->cons_bytes = cons_bytes;
 
-	link_sort_by_len(order);
+	link_layout_order(l, S, order, f->repeats);
 	f->scaf_first.assign(1, 0);
 	f->items.clear();
 	f->gaps.clear();
@@ -444,12 +441,6 @@ extern "C" int dbgk_fill_resolve(dbgk_fill *f, dbgk_fill_summary *out)
 		}
 		f->scaf_first.push_back(f->items.size());
 	}
-	std::vector<LenIdx> rep;
-	for (int32_t id : S.repeat_nodes)
-		if (id % 2 == 1) rep.push_back(LenIdx{l->lens[id / 2], (uint64_t)(id / 2)});
-	link_sort_by_len(rep);
-	f->repeats.clear();
-	for (const LenIdx &r : rep) f->repeats.push_back((int32_t)r.idx);
 	f->summary = dbgk_fill_summary{S.s.lowfreq, S.s.repeat_nodes, S.s.deleted, scaf.size(), f->items.size(), f->gaps.size(), desc.size(), cons_bytes,
 	                               f->pairs.size()};
 	f->stats.cons_bytes = cons_bytes;
@@ -484,11 +475,8 @@ extern "C" int dbgk_fill_layout(dbgk_fill *f, uint64_t *scaf_first, dbgk_fill_it
 extern "C" int dbgk_fill_emit(dbgk_fill *f, const char *bases, const uint64_t *offsets, uint64_t n_contigs, const dbgk_fill_item *items,
                               uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len)
 {
-	if (!f || !offsets || offsets[0] != 0 || (n_items && !items) || !out_len || n_items >= (1ull << 31) || n_contigs >= (1ull << 30))
+	if (!f || (n_items && !items) || !out_len || n_items >= (1ull << 31) || n_contigs >= (1ull << 30) || !link_check_offsets(bases, offsets, n_contigs))
 		return DBGK_ERR_ARG;
-	for (uint64_t i = 0; i < n_contigs; ++i)
-		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
-	if (offsets[n_contigs] && !bases) return DBGK_ERR_ARG;
 	std::vector<uint64_t> item_off(n_items + 1, 0);
 	std::vector<fillk::EmitItem> dev_items(n_items);
 	for (uint64_t t = 0; t < n_items; ++t) {
@@ -513,34 +501,13 @@ extern "C" int dbgk_fill_emit(dbgk_fill *f, const char *bases, const uint64_t *o
 	if (!total) return DBGK_OK;
 	if (!out || capacity < total) return DBGK_ERR_CAPACITY;
 	dbgk_link *l = f->L;
-	HIPCHK(hipSetDevice(l->device));
-	uint8_t *d_bases = nullptr, *d_out = nullptr;
-	uint64_t *d_ioff = nullptr;
-	fillk::EmitItem *d_items = nullptr;
-	auto release = [&]() { (void)hipFree(d_bases); (void)hipFree(d_out); (void)hipFree(d_ioff); (void)hipFree(d_items); };
-	const uint64_t nb = offsets[n_contigs];
-	if (hipMalloc(&d_bases, nb + 16) != hipSuccess || hipMalloc(&d_out, ((total + 7) & ~7ull) + 16) != hipSuccess ||
-	    hipMalloc(&d_ioff, (n_items + 1) * 8) != hipSuccess || hipMalloc(&d_items, n_items * sizeof(fillk::EmitItem)) != hipSuccess) {
-		release();
-		return DBGK_ERR_NOMEM;
-	}
-	int rc = DBGK_OK;
-	auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, "dbgk_fill_emit", __LINE__); };
-	if (nb) step(hipMemcpyAsync(d_bases, bases, nb, hipMemcpyHostToDevice, l->stream));
-	step(hipMemcpyAsync(d_ioff, item_off.data(), (n_items + 1) * 8, hipMemcpyHostToDevice, l->stream));
-	step(hipMemcpyAsync(d_items, dev_items.data(), n_items * sizeof(fillk::EmitItem), hipMemcpyHostToDevice, l->stream));
-	step(hipEventRecord(l->ev[0], l->stream));
-	if (!rc) {
-		hipLaunchKernelGGL(fillk::k_fill_emit, dim3(link_grid(l, (total + 7) / 8)), dim3(fillk::kFillThreads), 0, l->stream, d_bases, f->d_cons, d_items,
-		                   d_ioff, (uint32_t)n_items, total, d_out);
-		step(hipGetLastError());
-	}
-	step(hipEventRecord(l->ev[1], l->stream));
-	step(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, l->stream));
-	step(hipStreamSynchronize(l->stream));
 	float ms = 0;
-	if (!rc) step(hipEventElapsedTime(&ms, l->ev[0], l->ev[1]));
-	release();
+	auto launch = [&](const uint8_t *d_bases, const uint64_t *, const void *d_items, const uint64_t *d_ioff, uint8_t *d_out) {
+		hipLaunchKernelGGL(fillk::k_fill_emit, dim3(link_grid(l, (total + 7) / 8)), dim3(fillk::kFillThreads), 0, l->stream, d_bases, f->d_cons,
+		                   static_cast<const fillk::EmitItem *>(d_items), d_ioff, (uint32_t)n_items, total, d_out);
+	};
+	const int rc = link_run_emit(l, "dbgk_fill_emit", bases, offsets, n_contigs, false, dev_items.data(), n_items * sizeof(fillk::EmitItem), item_off, out,
+	                             &ms, launch);
 	if (rc) return rc;
 	f->stats.ms_emit = ms;
 	f->stats.emit_bytes = total;

@@ -488,6 +488,28 @@ static void link_sort_by_len(std::vector<LenIdx> &v)
 
 } // namespace
 
+// n strings back to back, string i at bases[offsets[i] .. offsets[i + 1]): the offsets start at 0 and ascend, and bases is there
+// when they name any
+static bool link_check_offsets(const char *bases, const uint64_t *offsets, uint64_t n)
+{
+	if (!offsets || offsets[0] != 0) return false;
+	for (uint64_t i = 0; i < n; ++i)
+		if (offsets[i + 1] < offsets[i]) return false;
+	return !offsets[n] || bases;
+}
+
+// the order both programs write in: the scaffolds of `order` by length, and the repeat contigs by length
+static void link_layout_order(const dbgk_link *l, const LinkPasses &S, std::vector<LenIdx> &order, std::vector<int32_t> &repeats)
+{
+	link_sort_by_len(order);
+	std::vector<LenIdx> rep;
+	for (int32_t id : S.repeat_nodes)
+		if (id % 2 == 1) rep.push_back(LenIdx{l->lens[id / 2], (uint64_t)(id / 2)});
+	link_sort_by_len(rep);
+	repeats.clear();
+	for (const LenIdx &r : rep) repeats.push_back((int32_t)r.idx);
+}
+
 // the reference's passes over a copy of the table, the two snapshots, and its walk: per scaffold the combined list node, gap, node,
 // ... (read_out_scaffold, link_scaffold.cpp:317-357; read_out_scaffinfo, link_contig.cpp:676-726).  link_contig runs no
 // interleaving pass (interleave false).
@@ -547,19 +569,13 @@ extern "C" int dbgk_link_resolve(dbgk_link *l, dbgk_link_summary *out)
 			order.push_back(LenIdx{(uint64_t)(int64_t)(int)len, scaf.size()});
 			scaf.push_back(std::move(items));
 		}
-		link_sort_by_len(order);
+		link_layout_order(l, S, order, l->repeats);
 		l->scaf_first.assign(1, 0);
 		l->items.clear();
 		for (const LenIdx &o : order) {
 			l->items.insert(l->items.end(), scaf[o.idx].begin(), scaf[o.idx].end());
 			l->scaf_first.push_back(l->items.size());
 		}
-		std::vector<LenIdx> rep;
-		for (int32_t id : S.repeat_nodes)
-			if (id % 2 == 1) rep.push_back(LenIdx{l->lens[id / 2], (uint64_t)(id / 2)});
-		link_sort_by_len(rep);
-		l->repeats.clear();
-		for (const LenIdx &r : rep) l->repeats.push_back((int32_t)r.idx);
 		S.s.scaffolds = scaf.size();
 		S.s.items = l->items.size();
 		l->summary = S.s;
@@ -589,14 +605,50 @@ extern "C" int dbgk_link_layout(dbgk_link *l, uint64_t *scaf_first, dbgk_link_it
 	return DBGK_OK;
 }
 
+// the device side of dbgk_link_emit and dbgk_fill_emit (`who`) once the items are checked: the contig bases, the items as the
+// stage's kernel reads them (item_bytes of them) and their offsets in the output go up, the contig offsets too when the kernel reads
+// them (with_contig_off); launch(d_bases, d_contig_off, d_items, d_item_off, d_out) starts the kernel; the item_off.back() bytes
+// it writes come down into out, and ms takes its time.
+template <class Launch>
+static int link_run_emit(dbgk_link *l, const char *who, const char *bases, const uint64_t *offsets, uint64_t n_contigs, bool with_contig_off,
+                         const void *items, uint64_t item_bytes, const std::vector<uint64_t> &item_off, char *out, float *ms, Launch launch)
+{
+	const uint64_t nb = offsets[n_contigs], total = item_off.back();
+	HIPCHK(hipSetDevice(l->device));
+	uint8_t *d_bases = nullptr, *d_out = nullptr;
+	uint64_t *d_coff = nullptr, *d_ioff = nullptr;
+	void *d_items = nullptr;
+	auto release = [&]() { (void)hipFree(d_bases); (void)hipFree(d_out); (void)hipFree(d_coff); (void)hipFree(d_ioff); (void)hipFree(d_items); };
+	if (hipMalloc(&d_bases, nb + 16) != hipSuccess || hipMalloc(&d_out, ((total + 7) & ~7ull) + 16) != hipSuccess ||
+	    (with_contig_off && hipMalloc(&d_coff, (n_contigs + 1) * 8) != hipSuccess) || hipMalloc(&d_ioff, item_off.size() * 8) != hipSuccess ||
+	    hipMalloc(&d_items, item_bytes) != hipSuccess) {
+		release();
+		return DBGK_ERR_NOMEM;
+	}
+	int rc = DBGK_OK;
+	auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, who, __LINE__); };
+	if (nb) step(hipMemcpyAsync(d_bases, bases, nb, hipMemcpyHostToDevice, l->stream));
+	if (with_contig_off) step(hipMemcpyAsync(d_coff, offsets, (n_contigs + 1) * 8, hipMemcpyHostToDevice, l->stream));
+	step(hipMemcpyAsync(d_ioff, item_off.data(), item_off.size() * 8, hipMemcpyHostToDevice, l->stream));
+	step(hipMemcpyAsync(d_items, items, item_bytes, hipMemcpyHostToDevice, l->stream));
+	step(hipEventRecord(l->ev[0], l->stream));
+	if (!rc) {
+		launch(d_bases, d_coff, d_items, d_ioff, d_out);
+		step(hipGetLastError());
+	}
+	step(hipEventRecord(l->ev[1], l->stream));
+	step(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, l->stream));
+	step(hipStreamSynchronize(l->stream));
+	if (!rc) step(hipEventElapsedTime(ms, l->ev[0], l->ev[1]));
+	release();
+	return rc;
+}
+
 extern "C" int dbgk_link_emit(dbgk_link *l, const char *bases, const uint64_t *offsets, uint64_t n_contigs, const dbgk_link_item *items,
                               uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len)
 {
-	if (!l || !offsets || offsets[0] != 0 || (n_items && !items) || !out_len || n_items >= (1ull << 31) || n_contigs >= (1ull << 30))
+	if (!l || (n_items && !items) || !out_len || n_items >= (1ull << 31) || n_contigs >= (1ull << 30) || !link_check_offsets(bases, offsets, n_contigs))
 		return DBGK_ERR_ARG;
-	for (uint64_t i = 0; i < n_contigs; ++i)
-		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
-	if (offsets[n_contigs] && !bases) return DBGK_ERR_ARG;
 	std::vector<uint64_t> item_off(n_items + 1, 0);
 	for (uint64_t t = 0; t < n_items; ++t) {
 		uint64_t len;
@@ -613,36 +665,12 @@ extern "C" int dbgk_link_emit(dbgk_link *l, const char *bases, const uint64_t *o
 	*out_len = total;
 	if (!total) return DBGK_OK;
 	if (!out || capacity < total) return DBGK_ERR_CAPACITY;
-	HIPCHK(hipSetDevice(l->device));
-	uint8_t *d_bases = nullptr, *d_out = nullptr;
-	uint64_t *d_coff = nullptr, *d_ioff = nullptr;
-	linkk::Item *d_items = nullptr;
-	auto release = [&]() { (void)hipFree(d_bases); (void)hipFree(d_out); (void)hipFree(d_coff); (void)hipFree(d_ioff); (void)hipFree(d_items); };
-	const uint64_t nb = offsets[n_contigs];
-	if (hipMalloc(&d_bases, nb + 16) != hipSuccess || hipMalloc(&d_out, ((total + 7) & ~7ull) + 16) != hipSuccess ||
-	    hipMalloc(&d_coff, (n_contigs + 1) * 8) != hipSuccess || hipMalloc(&d_ioff, (n_items + 1) * 8) != hipSuccess ||
-	    hipMalloc(&d_items, n_items * 8) != hipSuccess) {
-		release();
-		return DBGK_ERR_NOMEM;
-	}
-	int rc = DBGK_OK;
-	auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, "dbgk_link_emit", __LINE__); };
-	if (nb) step(hipMemcpyAsync(d_bases, bases, nb, hipMemcpyHostToDevice, l->stream));
-	step(hipMemcpyAsync(d_coff, offsets, (n_contigs + 1) * 8, hipMemcpyHostToDevice, l->stream));
-	step(hipMemcpyAsync(d_ioff, item_off.data(), (n_items + 1) * 8, hipMemcpyHostToDevice, l->stream));
-	step(hipMemcpyAsync(d_items, items, n_items * 8, hipMemcpyHostToDevice, l->stream));
-	step(hipEventRecord(l->ev[0], l->stream));
-	if (!rc) {
-		hipLaunchKernelGGL(linkk::k_link_emit, dim3(link_grid(l, (total + 7) / 8)), dim3(linkk::kLinkThreads), 0, l->stream, d_bases, d_coff, d_items,
-		                   d_ioff, (uint32_t)n_items, total, d_out);
-		step(hipGetLastError());
-	}
-	step(hipEventRecord(l->ev[1], l->stream));
-	step(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, l->stream));
-	step(hipStreamSynchronize(l->stream));
 	float ms = 0;
-	if (!rc) step(hipEventElapsedTime(&ms, l->ev[0], l->ev[1]));
-	release();
+	auto launch = [&](const uint8_t *d_bases, const uint64_t *d_coff, const void *d_items, const uint64_t *d_ioff, uint8_t *d_out) {
+		hipLaunchKernelGGL(linkk::k_link_emit, dim3(link_grid(l, (total + 7) / 8)), dim3(linkk::kLinkThreads), 0, l->stream, d_bases, d_coff,
+		                   static_cast<const linkk::Item *>(d_items), d_ioff, (uint32_t)n_items, total, d_out);
+	};
+	const int rc = link_run_emit(l, "dbgk_link_emit", bases, offsets, n_contigs, true, items, n_items * 8, item_off, out, &ms, launch);
 	if (rc) return rc;
 	l->stats.ms_emit = ms;
 	l->stats.emit_bytes = total;

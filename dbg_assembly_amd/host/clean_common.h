@@ -1,85 +1,15 @@
-// clean_common.h -- what bin/clean_adapter and bin/clean_lowqual share: gzip line input and output, the FASTQ record loop of the
+// clean_common.h -- what bin/clean_adapter and bin/clean_lowqual share on top of cli_common.h: the FASTQ record loop of the
 // reference (clean_illumina/clean_adapter.cpp:376-387, the same in clean_lowqual.cpp) and a batch of records on its way to the
 // device (CLEAN section of include/dbgk.h).
 #pragma once
 #include <unistd.h>
-#include <zlib.h>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <ctime>
-#include <fstream>
-#include <iostream>
-#include <string>
-#include <vector>
 
-#include "dbgk.h"
-
-using namespace std;
+#include "cli_common.h"
 
 static const uint64_t BatchReads = 1 << 20;   // records per device batch
 static const uint64_t BatchBases = 256 << 20; // ... or this many bases, whichever comes first
-
-static void die(const char *what, int rc)
-{
-	cerr << what << " failed: " << dbgk_strerror(rc);
-	if (rc == DBGK_ERR_HIP) cerr << " [" << dbgk_last_error() << "]";
-	cerr << endl;
-	exit(1);
-}
-
-// getline over a plain or gzip file (what igzstream + getline read)
-struct LineReader {
-	gzFile f = nullptr;
-	vector<char> buf = vector<char>(1 << 20);
-	size_t pos = 0, len = 0;
-	bool eof = false;
-	explicit LineReader(const string &path)
-	{
-		f = gzopen(path.c_str(), "rb");
-		if (!f) cerr << "fail to open input file " << path << endl;
-	}
-	~LineReader() { if (f) gzclose(f); }
-	bool getline(string &s)
-	{
-		s.clear();
-		bool any = false;
-		for (;;) {
-			if (pos == len) {
-				if (eof || !f) return any;
-				const int n = gzread(f, buf.data(), (unsigned)buf.size());
-				if (n <= 0) { eof = true; return any; }
-				pos = 0;
-				len = (size_t)n;
-			}
-			any = true;
-			const char *b = buf.data() + pos;
-			const char *nl = (const char *)memchr(b, '\n', len - pos);
-			if (nl) {
-				s.append(b, nl - b);
-				pos += (nl - b) + 1;
-				return true;
-			}
-			s.append(b, len - pos);
-			pos = len;
-		}
-	}
-};
-
-// what ogzstream writes
-struct GzWriter {
-	gzFile f = nullptr;
-	explicit GzWriter(const string &path)
-	{
-		f = gzopen(path.c_str(), "wb");
-		if (!f) cerr << "fail to open output file " << path << endl;
-	}
-	~GzWriter() { if (f) gzclose(f); }
-	void write(const string &s)
-	{
-		if (f && !s.empty()) gzwrite(f, s.data(), (unsigned)s.size());
-	}
-};
 
 // a batch of records: heads, reads and qualities as read, and the reads (for clean_lowqual the qualities too) back to back
 struct RecordBatch {
@@ -127,13 +57,3 @@ struct RecordBatch {
 		out.write(text);
 	}
 };
-
-static void concat(const vector<string> &v, string &bases, vector<uint64_t> &offsets)
-{
-	bases.clear();
-	offsets.assign(1, 0);
-	for (const string &s : v) {
-		bases += s;
-		offsets.push_back(bases.size());
-	}
-}

@@ -31,20 +31,10 @@
 #include <thread>
 #include <vector>
 
-#include "dbgk.h"
+#include "cli_common.h"
 #include "reads_io.h"
 
-using namespace std;
-
 static const uint64_t kBlockKmers = 8ull * 1024 * 1024;  // SrcBlockSize, correct_error/main_parallel_senior.cpp:71
-
-static void die(const char *what, int rc)
-{
-	cerr << what << " failed: " << dbgk_strerror(rc);
-	if (rc == DBGK_ERR_HIP) cerr << " [" << dbgk_last_error() << "]";
-	cerr << endl;
-	exit(1);
-}
 
 int main(int argc, char **argv)
 {

@@ -1,23 +1,14 @@
-// map_common.h -- what bin/map_reads and bin/map_pair share: the reference's option variables, its input formats
-// (link_scaffold/map_func.cpp:33-116), gzip line input and output, the mapper on the GPU (MAP section of include/dbgk.h)
-// and the formatting of one alignment.
+// map_common.h -- what bin/map_reads and bin/map_pair share on top of cli_common.h: the reference's option variables, its contig
+// file format (link_scaffold/map_func.cpp:81-116), the mapper on the GPU (MAP section of include/dbgk.h), a batch of reads on
+// its way to it and the formatting of one alignment.
 #pragma once
 #include <sys/stat.h>
 #include <unistd.h>
-#include <zlib.h>
 #include <cerrno>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <iostream>
 #include <sstream>
-#include <string>
-#include <vector>
 
-#include "dbgk.h"
-
-using namespace std;
+#include "cli_common.h"
 
 static int KmerSize = 31;
 static double MinMapIdentity = 0.97;
@@ -29,43 +20,6 @@ static string Output_prefix = "./";
 
 static const uint64_t BatchReads = 1 << 20;   // reads per device batch
 static const uint64_t BatchBases = 256 << 20; // ... or this many bases, whichever comes first
-
-static void die(const char *what, int rc)
-{
-	cerr << what << " failed: " << dbgk_strerror(rc);
-	if (rc == DBGK_ERR_HIP) cerr << " [" << dbgk_last_error() << "]";
-	cerr << endl;
-	exit(1);
-}
-
-// split (map_func.cpp:33-53)
-static void split(const string &line, vector<string> &tokens, const char *delim)
-{
-	size_t i = 0;
-	for (;;) {
-		i = line.find_first_not_of(delim, i);
-		if (i == string::npos) break;
-		const size_t j = line.find_first_of(delim, i);
-		tokens.push_back(line.substr(i, j == string::npos ? string::npos : j - i));
-		if (j == string::npos) break;
-		i = j;
-	}
-}
-
-// reading_lib_file (map_func.cpp:57-77): '#' lines and empty lines skipped, the first token taken
-static void reading_lib_file(const string &lib_file, vector<string> &read_files)
-{
-	ifstream infile(lib_file.c_str());
-	if (!infile) cerr << "fail to open input file" << lib_file << endl;
-	string line;
-	while (getline(infile, line, '\n')) {
-		if (!line.empty() && line[0] == '#') continue;
-		vector<string> vec_line;
-		split(line, vec_line, " \t\n");
-		if (vec_line.empty()) continue;
-		read_files.push_back(vec_line[0]);
-	}
-}
 
 // read_contig_file (map_func.cpp:81-116): the id is the first token behind '>', sequences may span lines, a record
 // without sequence in front of another header is dropped, the last record is always pushed
@@ -101,59 +55,6 @@ static string make_read_id(const string &head, const char *delim)
 	return vec_head.size() > 1 ? vec_head[0] + "-" + vec_head[1] : vec_head[0];
 }
 
-// getline over a plain or gzip file (what igzstream + getline read)
-struct LineReader {
-	gzFile f = nullptr;
-	vector<char> buf = vector<char>(1 << 20);
-	size_t pos = 0, len = 0;
-	bool eof = false;
-	explicit LineReader(const string &path)
-	{
-		f = gzopen(path.c_str(), "rb");
-		if (!f) cerr << "fail to open input file " << path << endl;
-	}
-	~LineReader() { if (f) gzclose(f); }
-	bool getline(string &s)
-	{
-		s.clear();
-		bool any = false;
-		for (;;) {
-			if (pos == len) {
-				if (eof || !f) return any;
-				const int n = gzread(f, buf.data(), (unsigned)buf.size());
-				if (n <= 0) { eof = true; return any; }
-				pos = 0;
-				len = (size_t)n;
-			}
-			any = true;
-			const char *b = buf.data() + pos;
-			const char *nl = (const char *)memchr(b, '\n', len - pos);
-			if (nl) {
-				s.append(b, nl - b);
-				pos += (nl - b) + 1;
-				return true;
-			}
-			s.append(b, len - pos);
-			pos = len;
-		}
-	}
-};
-
-// what ogzstream writes
-struct GzWriter {
-	gzFile f = nullptr;
-	explicit GzWriter(const string &path)
-	{
-		f = gzopen(path.c_str(), "wb");
-		if (!f) cerr << "fail to open output file " << path << endl;
-	}
-	~GzWriter() { if (f) gzclose(f); }
-	void write(const string &s)
-	{
-		if (f && !s.empty()) gzwrite(f, s.data(), (unsigned)s.size());
-	}
-};
-
 static const char *HeaderOne = "#read_id\tread_length\talign_read_start\talign_read_end\tcontig_id\tcontig_length\talign_contig_start\talign_contig_end\talign_direct\talign_identity%";
 static const char *HeaderTwo = "\tread_id\tread_length\talign2_read_start\talign2_read_end\tcontig2_id\tcontig2_length\talign2_contig_start\talign2_contig_end\talign2_direct\talign2_identity%";
 
@@ -180,12 +81,8 @@ struct Contigs {
 		int rc = dbgk_map_create(&p, 0, &mapper);
 		if (rc) die("dbgk_map_create", rc);
 		string bases;
-		vector<uint64_t> offsets(1, 0);
-		bases.reserve(total_contig_len);
-		for (const string &s : seqs) {
-			bases += s;
-			offsets.push_back(bases.size());
-		}
+		vector<uint64_t> offsets;
+		concat(seqs, bases, offsets);
 		rc = dbgk_map_set_contigs(mapper, bases.data(), offsets.data(), seqs.size());
 		if (rc) die("dbgk_map_set_contigs", rc);
 		cerr << "Build the kmer hash finished" << endl;
