@@ -170,6 +170,30 @@ class FillTiming(C.Structure):
                [(f, C.c_double) for f in ("ms_orient", "ms_sort", "ms_table", "ms_gapstat", "ms_consensus", "ms_emit")]
 
 
+class SuperParams(C.Structure):
+    _fields_ = [("pair_num_cut", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+SUPER_GAPSTAT_DTYPE = np.dtype([("contig_lo", "<i4"), ("contig_hi", "<i4"), ("mean", "<i4"), ("min", "<i4"), ("max", "<i4"), ("total", "<i4"),
+                                ("variance", "<i4"), ("reserved", "<i4")])  # dbgk_super_gapstat
+SUPER_JUNCTION_DTYPE = np.dtype([("left_contig", "<i4"), ("right_contig", "<i4"), ("mean", "<i4"), ("min", "<i4"), ("max", "<i4"),
+                                 ("total", "<i4"), ("variance", "<i4"), ("n_written", "<i4"), ("gap_id", "<i4"), ("median", "<i4"),
+                                 ("first_slice", "<u8"), ("n_slices", "<u4"), ("n_kept", "<u4")])  # dbgk_super_junction
+SUPER_SLICE_DTYPE = np.dtype([("record", "<u8"), ("offset", "<u8"), ("length", "<u4"), ("reversed", "u1"), ("kept", "u1"),
+                              ("pad", "u1", (2,))])  # dbgk_super_slice
+
+
+class SuperSummary(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("lowfreq", "interleave", "repeat_nodes", "deleted", "scaffolds", "items", "junctions", "slices",
+                                          "lines", "slice_bytes", "pairs")] + \
+               [("bad_record", C.c_int64), ("bad_read", C.c_int64), ("bad_left", C.c_int32), ("bad_right", C.c_int32)]
+
+
+class SuperTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("records", "pooled", "links", "slice_bytes", "emit_bytes")] + \
+               [(f, C.c_double) for f in ("ms_orient", "ms_sort", "ms_table", "ms_gapstat", "ms_slices", "ms_emit")]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -318,6 +342,22 @@ SYMBOLS = [
     ("dbgk_fill_layout", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("dbgk_fill_emit", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("dbgk_fill_batch_stats", _i, [_vp, C.POINTER(FillTiming)]),
+    ("dbgk_super_create", _i, [C.POINTER(SuperParams), _i, C.POINTER(_vp)]),
+    ("dbgk_super_destroy", _i, [_vp]),
+    ("dbgk_super_set_contigs", _i, [_vp, _vp, _u64]),
+    ("dbgk_super_set_reads", _i, [_vp, _vp, _vp, _u64]),
+    ("dbgk_super_add_records", _i, [_vp, _vp, _u64]),
+    ("dbgk_super_add_hits", _i, [_vp, _vp, _u64, _u64]),
+    ("dbgk_super_build", _i, [_vp]),
+    ("dbgk_super_export", _i, [_vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(LinkCounters)]),
+    ("dbgk_super_gap_stats", _i, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    ("dbgk_super_resolve", _i, [_vp, C.POINTER(SuperSummary)]),
+    ("dbgk_super_snapshot", _i, [_vp, C.c_int32, _vp, _vp, _vp]),
+    ("dbgk_super_layout", _i, [_vp, _vp, _vp, _vp, _vp]),
+    ("dbgk_super_slices", _i, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    ("dbgk_super_slice_bytes", _i, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    ("dbgk_super_emit", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    ("dbgk_super_batch_stats", _i, [_vp, C.POINTER(SuperTiming)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1158,7 +1198,7 @@ class Cleaner:
 
 
 class _LinkTable:
-    """What Scaffolder and GapFiller share: the handle, the contigs, the link table and the emit of the C calls that start with
+    """What Scaffolder, GapFiller and SuperLinker share: the handle, the contigs, the link table and the emit of the C calls that start with
     `_prefix` ("dbgk_link" / "dbgk_fill"); `_item_dtype` is the dtype of the items emit() takes."""
     _prefix = None
     _item_dtype = None
@@ -1419,3 +1459,87 @@ class GapFiller(_LinkTable):
         s = FillTiming()
         _chk(lib().dbgk_fill_batch_stats(self._h, C.byref(s)), "dbgk_fill_batch_stats")
         return {f: getattr(s, f) for f, _ in FillTiming._fields_}
+
+
+class SuperLinker(_LinkTable):
+    """link_supertig on the GPU (SUPER section of include/dbgk.h).  Contig c is node 2c + 1, its reverse strand node 2c + 2.
+    set_contigs(lengths), set_reads(reads), add_records / add_hits in file order, build(), then table() and gap_stats(),
+    resolve() for the passes, the walk and the slices of every gap, layout(), slices() and emit() for the super-contigs."""
+    _prefix = "dbgk_super"
+    _item_dtype = LINK_ITEM_DTYPE
+
+    def __init__(self, pair_num_cut=3, device=0):
+        self._h = C.c_void_p()
+        self.n_contigs = 0
+        _chk(lib().dbgk_super_create(C.byref(SuperParams(pair_num_cut, (C.c_int32 * 3)(0, 0, 0))), device, C.byref(self._h)), "dbgk_super_create")
+
+    def set_reads(self, reads):
+        """a list of sequences (bytes / str), or (bases, offsets): the reads the records' `read` fields index"""
+        bases, offsets = reads if isinstance(reads, tuple) else concat_sequences(reads)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self._call("set_reads", bases.ctypes.data if bases.size else None, offsets.ctypes.data, len(offsets) - 1)
+
+    def add_records(self, recs):
+        """FILL_RECORD_DTYPE records (any structured array with its first eight fields), behind those added so far"""
+        if recs.dtype != FILL_RECORD_DTYPE:
+            r = np.zeros(len(recs), dtype=FILL_RECORD_DTYPE)
+            for f in FILL_RECORD_DTYPE.names[:8]:
+                r[f] = recs[f]
+            recs = r
+        recs = np.ascontiguousarray(recs)
+        self._call("add_records", recs.ctypes.data if len(recs) else None, len(recs))
+
+    def add_hits(self, hits, first_read=0):
+        """what Mapper.map (second_alignment) returned for reads first_read, first_read + 1, ...: MAP_HIT_DTYPE[n, 2]"""
+        hits = np.ascontiguousarray(np.asarray(hits, dtype=MAP_HIT_DTYPE))
+        if hits.ndim != 2 or hits.shape[1] != 2:
+            raise ValueError("two hits per read")
+        n = len(hits)
+        self._call("add_hits", hits.ctypes.data if n else None, n, first_read)
+
+    def build(self):
+        self._call("build")
+
+    def gap_stats(self):
+        """-> SUPER_GAPSTAT_DTYPE per contig pair with a record, ascending by (contig_lo, contig_hi)"""
+        n = C.c_uint64()
+        self._call("gap_stats", None, 0, C.byref(n))
+        out = np.zeros(max(n.value, 1), dtype=SUPER_GAPSTAT_DTYPE)
+        self._call("gap_stats", out.ctypes.data, len(out), C.byref(n))
+        return out[:n.value]
+
+    def resolve(self):
+        """-> the summary as a dict; a slice outside its read raises DbgkError (ERR_ARG) whose `bad` names record, read and contigs"""
+        s = SuperSummary()
+        rc = self._call("resolve", C.byref(s), ok=(0, ERR_ARG))
+        if rc:
+            e = DbgkError(rc, "dbgk_super_resolve")
+            e.bad = {f: getattr(s, f) for f in ("bad_record", "bad_read", "bad_left", "bad_right")}
+            raise e
+        return {f: getattr(s, f) for f, _ in SuperSummary._fields_}
+
+    def layout(self):
+        """-> scaf_first[super-contigs + 1], LINK_ITEM_DTYPE items, SUPER_JUNCTION_DTYPE junctions, repeat contigs: in output order"""
+        s = self.resolve()
+        scaf_first = np.zeros(s["scaffolds"] + 1, dtype=np.uint64)
+        items = np.zeros(max(s["items"], 1), dtype=LINK_ITEM_DTYPE)
+        junctions = np.zeros(max(s["junctions"], 1), dtype=SUPER_JUNCTION_DTYPE)
+        repeats = np.zeros(max(s["repeat_nodes"], 1), dtype=np.int32)
+        self._call("layout", scaf_first.ctypes.data, items.ctypes.data, junctions.ctypes.data, repeats.ctypes.data)
+        return scaf_first, items[:s["items"]], junctions[:s["junctions"]], repeats[:s["repeat_nodes"]]
+
+    def slices(self):
+        """-> SUPER_SLICE_DTYPE per slice (those of gap 1 first, per gap as sorted by length), and the bytes of the written ones"""
+        s = self.resolve()
+        n = C.c_uint64()
+        out = np.zeros(max(s["slices"], 1), dtype=SUPER_SLICE_DTYPE)
+        self._call("slices", out.ctypes.data, len(out), C.byref(n))
+        data = np.zeros(max(s["slice_bytes"], 1), dtype=np.uint8)
+        self._call("slice_bytes", data.ctypes.data, len(data), C.byref(n))
+        return out[:s["slices"]], data[:s["slice_bytes"]]
+
+    def timing(self):
+        s = SuperTiming()
+        self._call("batch_stats", C.byref(s))
+        return {f: getattr(s, f) for f, _ in SuperTiming._fields_}

@@ -172,9 +172,9 @@ extern "C" int dbgk_fill_add_hits(dbgk_fill *f, const dbgk_map_hit *hits, uint64
 	return fill_add(f, hits, n_reads, true, first_read);
 }
 
-extern "C" int dbgk_fill_build(dbgk_fill *f)
+// the link table of dbgk_fill_build and dbgk_super_build, and the number of records that take part in the gap statistics
+static int fill_build_table(dbgk_fill *f, fillk::Counters &fc)
 {
-	if (!f) return DBGK_ERR_ARG;
 	dbgk_link *l = f->L;
 	if (!l->contigs_set || l->built) return DBGK_ERR_STATE;
 	int rc = dbgk_link_build(l);
@@ -182,12 +182,21 @@ extern "C" int dbgk_fill_build(dbgk_fill *f)
 	f->stats.ms_sort = l->stats.ms_sort;
 	f->stats.ms_table = l->stats.ms_reduce + l->stats.ms_chain;
 	f->stats.links = l->stats.links;
-	// the gap statistics: stable sort by gap, then by pair (records map_reads would not have written sort behind the others)
-	fillk::Counters fc{};
 	HIPCHK(hipMemcpyAsync(&fc, f->d_fctr, sizeof fc, hipMemcpyDeviceToHost, l->stream));
 	HIPCHK(hipStreamSynchronize(l->stream));
 	f->n_pooled = fc.pooled;
 	f->stats.pooled = fc.pooled;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_fill_build(dbgk_fill *f)
+{
+	if (!f) return DBGK_ERR_ARG;
+	dbgk_link *l = f->L;
+	// the gap statistics: stable sort by gap, then by pair (records map_reads would not have written sort behind the others)
+	fillk::Counters fc{};
+	int rc = fill_build_table(f, fc);
+	if (rc) return rc;
 	f->pairs.clear();
 	const uint64_t n = f->n_records;
 	if (!fc.pooled) return DBGK_OK;

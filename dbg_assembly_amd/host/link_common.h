@@ -1,7 +1,8 @@
-// link_common.h -- what bin/link_scaffold and bin/link_contig share on top of cli_common.h: the option variables both have, the
-// reference's contig file format (link_scaffold/link_func.cpp:99-136) with the checks on the contig names, the checked part of
-// one 2ctg line, display_data_in_link, the reports on stderr both write, the two-call emit and the repeat-contig files.  The
-// handle differs (dbgk_link or dbgk_fill, LINK and FILL sections of include/dbgk.h), so the C calls come in as callables.
+// link_common.h -- what bin/link_scaffold, bin/link_contig and bin/link_supertig share on top of cli_common.h: the option variables
+// all three have, the reference's contig file format (link_scaffold/link_func.cpp:99-136) with the checks on the contig names, the
+// checked part of one 2ctg line, display_data_in_link, the reports on stderr they all write, the two-call emit and the
+// repeat-contig files.  The handle differs (dbgk_link, dbgk_fill or dbgk_super: LINK, FILL and SUPER sections of include/dbgk.h),
+// so the C calls come in as callables.
 #pragma once
 #include <unistd.h>
 #include <cstdio>
@@ -37,7 +38,7 @@ static void read_contig_file(const string &file, vector<string> &seqs, vector<st
 // ctgStr2Id (link_func.h:130)
 static int ctgStr2Id(const string &s) { return s.size() > 4 ? atoi(s.c_str() + 4) : 0; }
 
-// the contig file as both programs take it in, or exit(1)
+// the contig file as the three programs take it in, or exit(1)
 static void load_contigs(const char *prog, const string &file, vector<string> &ids, vector<string> &seqs, vector<uint32_t> &lens, uint64_t &total_len)
 {
 	read_contig_file(file, seqs, ids);
@@ -99,7 +100,8 @@ static void report_link_classes(const dbgk_link_counters &ctr)
 	cerr << "Wrong_link_num: " << ctr.wrong << endl;
 }
 
-// snapshot(stage, inlink, link, entries) is dbgk_link_snapshot or dbgk_fill_snapshot on the program's handle, die() included
+// snapshot(stage, inlink, link, entries) is dbgk_link_snapshot, dbgk_fill_snapshot or dbgk_super_snapshot on the program's handle,
+// die() included
 template <class Snapshot>
 static void report_3prime_links(Snapshot snapshot, size_t n_nodes)
 {
@@ -141,8 +143,8 @@ static void display_data_in_link(Snapshot snapshot, int stage, const vector<uint
 	fclose(out);
 }
 
-// the sequences of all scaffolds from one device call: emit(out, capacity, out_len) is dbgk_link_emit or dbgk_fill_emit (`what`) on the
-// program's contigs and items, called once for the size and once for the bytes
+// the sequences of all scaffolds from one device call: emit(out, capacity, out_len) is dbgk_link_emit, dbgk_fill_emit or
+// dbgk_super_emit (`what`) on the program's contigs and items, called once for the size and once for the bytes
 template <class Emit>
 static string emit_sequences(Emit emit, const char *what)
 {

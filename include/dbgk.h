@@ -912,6 +912,118 @@ int dbgk_fill_emit(dbgk_fill *f, const char *bases, const uint64_t *offsets, uin
                    uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len);
 int dbgk_fill_batch_stats(dbgk_fill *f, dbgk_fill_timing *out);
 
+/* ---- SUPER: link_supertig of the link_scaffold module on the GPU (additions to ABI 7) ------------------------------------------
+ * link_supertig links contigs or scafftigs by long reads whose two ends map_reads placed on two different sequences, writes every
+ * gap as N x the mean gap and lists, per gap, the slices of the reads that span it (link_scaffold/link_supertig.cpp).  The link
+ * table is FILL's; the passes are LINK's with the interleaving pass on.  Per unordered contig pair the records of every
+ * direction, wrong ones included, are pooled into mean, min, max, total and mean deviation (decide_gap_size, :561-605).  Per
+ * junction of the layout every record of its pair gives one slice of its read (:443-467); the slices are sorted by length with
+ * the reference's std::sort, the one at index n / 2 is the median, the others are kept when their length lies strictly inside
+ * 0.75 .. 1.25 x the median's (:469-495).  Table, statistics, slices and read-out are computed on the device; passes, walk and
+ * slice geometry on the host.  Every number and byte equals the reference's for the same records, reads and options.         */
+typedef struct dbgk_super dbgk_super;
+
+typedef struct dbgk_super_params {
+	int32_t pair_num_cut;       /* -n PairNumCut, >= 0 (default 3)                                                        */
+	int32_t reserved[3];        /* 0                                                                                      */
+} dbgk_super_params;
+
+/* the statistics of one unordered contig pair (GapSize, link_supertig.cpp:595-602) */
+typedef struct dbgk_super_gapstat {
+	int32_t contig_lo, contig_hi;   /* contig_lo < contig_hi                                                              */
+	int32_t mean;                   /* sum of the gaps / total, truncated toward zero                                     */
+	int32_t min, max, total;
+	int32_t variance;               /* sum |mean - gap| / total, truncated                                                */
+	int32_t reserved;
+} dbgk_super_gapstat;
+
+/* one junction of the layout: the statistics as *.supertig.pos.tab prints them, and its slices */
+typedef struct dbgk_super_junction {
+	int32_t left_contig, right_contig;
+	int32_t mean, min, max, total, variance;
+	int32_t n_written;              /* N's written: mean, or 1 for a mean <= 0                                            */
+	int32_t gap_id;                 /* 1, 2, ... in walk order: the id of *.supertig.gap.data and of the pos.tab line      */
+	int32_t median;                 /* index of the median among the junction's slices                                    */
+	uint64_t first_slice;           /* its slices are dbgk_super_slices [first_slice, first_slice + n_slices)             */
+	uint32_t n_slices;
+	uint32_t n_kept;                /* ... of which the median and n_kept - 1 others are written                          */
+} dbgk_super_junction;
+
+/* one slice; those of a junction come in the order the reference's sort by length leaves them */
+typedef struct dbgk_super_slice {
+	uint64_t record;                /* the record it comes from, counted over all dbgk_super_add_* calls                  */
+	uint64_t offset;                /* kept != 0: its bytes begin here in the slice bytes                                 */
+	uint32_t length;
+	uint8_t  reversed;              /* 1: the reverse complement of the read's bytes                                      */
+	uint8_t  kept;                  /* 2: the median (line Y), 1: written (line N), 0: dropped (Altert message)           */
+	uint8_t  pad[2];
+} dbgk_super_slice;
+
+typedef struct dbgk_super_summary {
+	uint64_t lowfreq, interleave, repeat_nodes, deleted, scaffolds, items;   /* as dbgk_link_summary                     */
+	uint64_t junctions;         /* junctions of the layout                                                                */
+	uint64_t slices;            /* slices of all junctions                                                                */
+	uint64_t lines;             /* ... that are written: the S ids of *.supertig.gap.data run 1 .. lines                  */
+	uint64_t slice_bytes;       /* bytes of the written slices                                                            */
+	uint64_t pairs;             /* contig pairs with statistics                                                           */
+	int64_t  bad_record;        /* DBGK_ERR_ARG from dbgk_super_resolve: the record whose slice does not lie in its read  */
+	int64_t  bad_read;          /* ... its read, and the junction's two contigs; -1 otherwise                             */
+	int32_t  bad_left, bad_right;
+} dbgk_super_summary;
+
+typedef struct dbgk_super_timing {
+	uint64_t records;           /* records and reads with hits added                                                      */
+	uint64_t pooled;            /* records in the gap statistics                                                          */
+	uint64_t links;
+	uint64_t slice_bytes;       /* bytes the slice kernel wrote (it read as many)                                         */
+	uint64_t emit_bytes;
+	double ms_orient;           /* device time of the orient kernel, summed over the batches                              */
+	double ms_sort;             /* wall time of all radix sorts (table and statistics)                                    */
+	double ms_table;            /* device time of reduce and chain                                                        */
+	double ms_gapstat;          /* device time of the two segmented-reduce passes and the pack kernel                     */
+	double ms_slices;           /* device time of the slice kernel                                                        */
+	double ms_emit;             /* device time of the emit kernel of the last dbgk_super_emit                             */
+} dbgk_super_timing;
+
+/* DBGK_ERR_ARG on a bad parameter, before any device work; DBGK_ERR_HIP without a usable gfx950 device: no host fall-back  */
+int dbgk_super_create(const dbgk_super_params *p, int device, dbgk_super **out);
+int dbgk_super_destroy(dbgk_super *s);
+int dbgk_super_set_contigs(dbgk_super *s, const uint32_t *lengths, uint64_t n_contigs);
+/* the reads the records point into, as dbgk_fill_set_reads; before dbgk_super_resolve.  A record may name a read index at or
+ * above n_reads (a read missing from the reads files): it counts in table and statistics and fails the junction it spans.  */
+int dbgk_super_set_reads(dbgk_super *s, const char *bases, const uint64_t *offsets, uint64_t n_reads);
+/* as dbgk_fill_add_records: the same fields of the same line */
+int dbgk_super_add_records(dbgk_super *s, const dbgk_fill_record *recs, uint64_t n);
+/* as dbgk_fill_add_hits */
+int dbgk_super_add_hits(dbgk_super *s, const dbgk_map_hit *hits, uint64_t n_reads, uint64_t first_read);
+/* the link table and the gap statistics, on the device; once.  A pair whose gap sum or deviation sum leaves int32 (undefined in
+ * the reference) is DBGK_ERR_ARG.                                                                                          */
+int dbgk_super_build(dbgk_super *s);
+/* as dbgk_link_export */
+int dbgk_super_export(dbgk_super *s, uint64_t *first, dbgk_link_entry *links, uint64_t capacity, uint64_t *n_links,
+                      dbgk_link_counters *counters);
+/* the statistics of every contig pair with a record, ascending by (contig_lo, contig_hi).  *n_pairs is always set.          */
+int dbgk_super_gap_stats(dbgk_super *s, dbgk_super_gapstat *out, uint64_t capacity, uint64_t *n_pairs);
+/* passes, walk, layout and the slices of every junction.  A slice that begins before its read's first byte or behind its last one,
+ * or a read index outside the reads (the reference throws out of substr), is DBGK_ERR_ARG with out->bad_* set; no byte of
+ * that junction is read on the device.                                                                                    */
+int dbgk_super_resolve(dbgk_super *s, dbgk_super_summary *out);
+/* as dbgk_link_snapshot: stage 0 *.supertig.links.all, stage 1 *.supertig.links.uniq */
+int dbgk_super_snapshot(dbgk_super *s, int32_t stage, uint8_t *inlink, uint8_t *link, dbgk_link_entry *links);
+/* super-contigs in output order: scaf_first (summary.scaffolds + 1), items (summary.items; the gap behind a contig is an item of
+ * n_written N's), junctions (summary.junctions, in the order of the gap items), repeat contigs (summary.repeat_nodes).  Any
+ * may be NULL.  Ids run spt_1, spt_3, ... through the super-contigs and on through the repeats.                            */
+int dbgk_super_layout(dbgk_super *s, uint64_t *scaf_first, dbgk_link_item *items, dbgk_super_junction *junctions, int32_t *repeats);
+/* the slices of all junctions, those of gap_id 1 first.  *n_slices is always set.                                          */
+int dbgk_super_slices(dbgk_super *s, dbgk_super_slice *out, uint64_t capacity, uint64_t *n_slices);
+/* the bytes of the written slices back to back in the order *.supertig.gap.data lists them (per junction the median, then the
+ * others as sorted), copied from the device buffer.  *n_bytes is always set.                                               */
+int dbgk_super_slice_bytes(dbgk_super *s, char *out, uint64_t capacity, uint64_t *n_bytes);
+/* as dbgk_link_emit */
+int dbgk_super_emit(dbgk_super *s, const char *bases, const uint64_t *offsets, uint64_t n_contigs, const dbgk_link_item *items,
+                    uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len);
+int dbgk_super_batch_stats(dbgk_super *s, dbgk_super_timing *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
