@@ -194,6 +194,27 @@ class SuperTiming(C.Structure):
                [(f, C.c_double) for f in ("ms_orient", "ms_sort", "ms_table", "ms_gapstat", "ms_slices", "ms_emit")]
 
 
+class ContigParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("kmer_freq_cutoff", C.c_int32), ("contig_len_cutoff", C.c_int32), ("reserved", C.c_int32)]
+
+
+CONTIG_RECORD_DTYPE = np.dtype([("anchor", "<u8"), ("left_end", "<u8"), ("right_end", "<u8"), ("left_len", "<u4"), ("right_len", "<u4"),
+                                ("left_depth", "<u4"), ("right_depth", "<u4"), ("left_mark", "u1"), ("right_mark", "u1"),
+                                ("left_repeat", "u1"), ("right_repeat", "u1"), ("host_walked", "u1"), ("mid_depth", "u1"),
+                                ("pad", "u1", (2,))])  # dbgk_contig_record
+
+
+class ContigSummary(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("contigs", "kernel_contigs", "host_contigs", "bytes", "linear_nodes", "host_nodes", "rounds",
+                                          "reserved")]
+
+
+class ContigTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("upload_bytes", "emit_bytes")] + \
+               [(f, C.c_double) for f in ("ms_upload", "ms_compact", "ms_successors", "ms_mutual", "ms_rank", "ms_place", "ms_scatter",
+                                          "ms_emit", "ms_host_walk")]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -358,6 +379,13 @@ SYMBOLS = [
     ("dbgk_super_slice_bytes", _i, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("dbgk_super_emit", _i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     ("dbgk_super_batch_stats", _i, [_vp, C.POINTER(SuperTiming)]),
+    ("dbgk_contig_create", _i, [C.POINTER(ContigParams), _i, C.POINTER(_vp)]),
+    ("dbgk_contig_destroy", _i, [_vp]),
+    ("dbgk_contig_set_table", _i, [_vp, _u64, _vp, _vp, _vp, _vp]),
+    ("dbgk_contig_read_out", _i, [_vp, C.POINTER(ContigSummary)]),
+    ("dbgk_contig_summary_get", _i, [_vp, C.POINTER(ContigSummary)]),
+    ("dbgk_contig_results", _i, [_vp, _vp, _vp, _vp, _vp]),
+    ("dbgk_contig_timing_get", _i, [_vp, C.POINTER(ContigTiming)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1543,3 +1571,61 @@ class SuperLinker(_LinkTable):
         s = SuperTiming()
         self._call("batch_stats", C.byref(s))
         return {f: getattr(s, f) for f, _ in SuperTiming._fields_}
+
+
+class ContigBuilder:
+    """The contig read-out on the GPU (CONTIG section of include/dbgk.h).  set_table(array, nul_flag, del_flag, klink) takes the
+    host-layout table after simplification: NODE_DTYPE array[size], the two flag arrays of size // 8 + 1 bytes (bit 128 >> (i % 8)
+    of byte i // 8), the 2-byte link records (bit 8 = linear).  read_out() -> bases, depths, offsets, records, summary: contigs in
+    the order the reference's scan finds them."""
+
+    def __init__(self, k, kmer_freq_cutoff=2, contig_len_cutoff=125, device=0):
+        self._h = C.c_void_p()
+        self._keep = None
+        _chk(lib().dbgk_contig_create(C.byref(ContigParams(k, kmer_freq_cutoff, contig_len_cutoff, 0)), device, C.byref(self._h)),
+             "dbgk_contig_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_contig_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_table(self, array, nul_flag, del_flag, klink):
+        array = np.ascontiguousarray(array, dtype=NODE_DTYPE)
+        size = len(array)
+        nul_flag = np.ascontiguousarray(nul_flag, dtype=np.uint8)
+        del_flag = np.ascontiguousarray(del_flag, dtype=np.uint8)
+        klink = np.ascontiguousarray(klink, dtype=np.uint16)
+        if len(nul_flag) != size // 8 + 1 or len(del_flag) != size // 8 + 1 or len(klink) != size:
+            raise ValueError("flag arrays of size // 8 + 1 bytes and one link record per slot")
+        self._keep = (array, nul_flag, del_flag, klink)   # the host walker reads them during read_out
+        _chk(lib().dbgk_contig_set_table(self._h, size, array.ctypes.data, nul_flag.ctypes.data, del_flag.ctypes.data, klink.ctypes.data),
+             "dbgk_contig_set_table")
+
+    def read_out(self):
+        """-> bases (uint8), depths (uint8), offsets (uint64, contigs + 1), records (CONTIG_RECORD_DTYPE), summary (dict)"""
+        s = ContigSummary()
+        _chk(lib().dbgk_contig_read_out(self._h, C.byref(s)), "dbgk_contig_read_out")
+        offsets = np.zeros(s.contigs + 1, dtype=np.uint64)
+        records = np.zeros(max(s.contigs, 1), dtype=CONTIG_RECORD_DTYPE)
+        bases = np.zeros(max(s.bytes, 1), dtype=np.uint8)
+        depths = np.zeros(max(s.bytes, 1), dtype=np.uint8)
+        _chk(lib().dbgk_contig_results(self._h, offsets.ctypes.data, records.ctypes.data, bases.ctypes.data, depths.ctypes.data),
+             "dbgk_contig_results")
+        return bases[:s.bytes], depths[:s.bytes], offsets, records[:s.contigs], self.summary()
+
+    def summary(self):
+        s = ContigSummary()
+        _chk(lib().dbgk_contig_summary_get(self._h, C.byref(s)), "dbgk_contig_summary_get")
+        return {f: getattr(s, f) for f, _ in ContigSummary._fields_ if f != "reserved"}
+
+    def timing(self):
+        s = ContigTiming()
+        _chk(lib().dbgk_contig_timing_get(self._h, C.byref(s)), "dbgk_contig_timing_get")
+        return {f: getattr(s, f) for f, _ in ContigTiming._fields_}

@@ -1,0 +1,512 @@
+// contig_stage.cpp -- the contig stage of debruijn_contig (see contig_stage.h).
+//
+// The three simplification passes run on the host in list order: each removal re-derives the links of the nodes at its ends
+// (recalculate_kmer_links, DBG_contig/contig.cpp:210-277) and so changes what later list entries see.  The read-out runs on the
+// GPU through the CONTIG section of include/dbgk.h; header strings, the sort by length, ids and the -M split are done here.
+// Line numbers name DBG_contig/contig.cpp unless another file is given.
+#include "contig_stage.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "DBGgraph.h"
+#include "dbgk.h"
+
+// the command line's options (defined in main.cpp)
+extern int KmerFreqCutoff, is_remove_tip, Tip_len_cutoff, is_remove_lowedge, LowCovEdge_len_cutoff, is_remove_bubble, Bubble_len_cutoff,
+    Contig_len_cutoff;
+extern double Tip_depth_cutoff, LowCovEdge_depth_cutoff, Bubble_len_diff_rate_cutoff, Bubble_base_diff_rate_cutoff;
+
+namespace {
+
+// the 2-byte link record of every slot, laid out as dbgk_export_host_table_links writes it (contig.h:31-42): l_link_num |
+// l_link_base << 2 | r_link_num << 4 | r_link_base << 6, bit 8 linear, bits 9..12 in_tip, in_bubble, in_lowedge, in_repeat
+uint16_t *klink = NULL;
+const uint32_t kClearBase[4] = {0x00FFFFFFu, 0xFF00FFFFu, 0xFFFF00FFu, 0xFFFFFF00u};   // BitMaskVal, :31
+enum { IN_TIP = 1 << 9, IN_BUBBLE = 1 << 10, IN_LOWEDGE = 1 << 11, IN_REPEAT = 1 << 12 };
+
+inline int l_num(uint64_t i) { return klink[i] & 3; }
+inline int l_base(uint64_t i) { return (klink[i] >> 2) & 3; }
+inline int r_num(uint64_t i) { return (klink[i] >> 4) & 3; }
+inline int r_base(uint64_t i) { return (klink[i] >> 6) & 3; }
+// "no such node" is slot kset->size; the reference looks at klink[kset->size] there (:810, :648), this build calls it not linear
+inline bool is_linear(uint64_t i) { return i != kset->size && (klink[i] & 0x100); }
+inline void set_flag(uint64_t i, int flag) { if (i != kset->size) klink[i] |= flag; }
+// array[kset->size].kmer, which the reference prints for an end without a node (:344, :1006): the word behind its table, 0 there
+inline uint64_t kmer_at(uint64_t i) { return i == kset->size ? 0 : kset->array[i].kmer; }
+
+inline uint64_t next_leftward(uint64_t kmer, int base) { return (kmer >> 2) + ((uint64_t)base << ((KmerSize - 1) * 2)); }   // contig.h:119-123
+inline uint64_t next_rightward(uint64_t kmer, int base) { return ((kmer << 2) | (uint64_t)base) & KmerHeadMaskVal; }        // contig.h:127-130
+
+double ms_since(const std::chrono::steady_clock::time_point &t0)
+{
+	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// canonical form of a neighbour k-mer; flipped says that it is the reverse complement
+uint64_t canonical(uint64_t kmer, bool &flipped)
+{
+	const uint64_t rc = get_rev_com_kbit(kmer, KmerSize);
+	flipped = !(kmer < rc);
+	return flipped ? rc : kmer;
+}
+
+// calculate_kmer_links (:107-181) on the host, for a table that did not get its link records from the device
+void first_pass_host(std::vector<uint64_t> &tips, std::vector<uint64_t> &branches)
+{
+	for (uint64_t i = 0; i < kset->size; i++) {
+		if (is_entity_null(kset->nul_flag, i)) continue;
+		int num[2] = {0, 0}, base[2] = {0, 0};
+		for (int side = 0; side < 2; side++) {
+			const uint32_t link = side ? kset->array[i].r_link : kset->array[i].l_link;
+			int max_depth = 0;
+			for (int j = 0; j < 4; j++) {
+				const int depth = get_next_kmer_depth(link, j);
+				if (depth > KmerFreqCutoff) {
+					if (num[side] < 3) num[side]++;
+					if (max_depth < depth) {
+						max_depth = depth;
+						base[side] = j;
+					}
+				}
+			}
+		}
+		klink[i] = (uint16_t)(num[0] | base[0] << 2 | num[1] << 4 | base[1] << 6 | ((num[0] == 1 && num[1] == 1) ? 0x100 : 0));
+		if (num[0] == 0 && num[1] == 0) set_entity_delete(kset->del_flag, i);
+		if (num[0] + num[1] == 1) tips.push_back(i);
+		if (num[0] > 1 || num[1] > 1) branches.push_back(i);
+	}
+}
+
+// recalculate_kmer_links, :210-277: a link whose neighbour is gone is cleared in the node itself
+void recalculate(uint64_t idx)
+{
+	if (idx == kset->size) return;
+	KmerNode &node = kset->array[idx];
+	int num[2] = {0, 0}, base[2] = {0, 0};
+	for (int side = 0; side < 2; side++) {
+		uint32_t &link = side ? node.r_link : node.l_link;
+		int max_depth = 0;
+		for (int j = 0; j < 4; j++) {
+			const int depth = get_next_kmer_depth(link, j);
+			if (depth <= KmerFreqCutoff) continue;
+			bool flipped;
+			const uint64_t key = canonical(side ? next_rightward(node.kmer, j) : next_leftward(node.kmer, j), flipped);
+			if (exist_kmerset(kset, key) != kset->size) {
+				if (num[side] < 3) num[side]++;
+				if (max_depth < depth) {
+					max_depth = depth;
+					base[side] = j;
+				}
+			} else {
+				link &= kClearBase[j];
+			}
+		}
+	}
+	klink[idx] = (uint16_t)((klink[idx] & 0xFE00) | num[0] | base[0] << 2 | num[1] << 4 | base[1] << 6 | ((num[0] == 1 && num[1] == 1) ? 0x100 : 0));
+}
+
+struct Path {                      // what get_linear_path returns
+	int len = 0, depth = 0;
+	std::vector<uint64_t> nodes;
+	std::string str;
+	uint64_t last = 0;
+	const char *mark = "linear";
+};
+
+// get_linear_path, :779-827: from idx along the strongest link until a node that is not linear, no node, or len_cutoff steps
+void linear_path(uint64_t idx, int direct, int len_cutoff, Path &p)
+{
+	const int original = direct;
+	for (;;) {
+		p.len++;
+		p.nodes.push_back(idx);
+		const KmerNode &node = kset->array[idx];
+		uint64_t next;
+		if (direct == 1) {
+			next = next_rightward(node.kmer, r_base(idx));
+			p.depth += get_next_kmer_depth(node.r_link, r_base(idx));
+			p.str.push_back(original == 1 ? bases[r_base(idx)] : c_bases[r_base(idx)]);
+		} else {
+			next = next_leftward(node.kmer, l_base(idx));
+			p.depth += get_next_kmer_depth(node.l_link, l_base(idx));
+			p.str.push_back(original == 1 ? c_bases[l_base(idx)] : bases[l_base(idx)]);
+		}
+		bool flipped;
+		const uint64_t key = canonical(next, flipped);
+		if (flipped) direct = -direct;
+		idx = exist_kmerset(kset, key);
+		if (!is_linear(idx) || p.len >= len_cutoff) {
+			p.last = idx;
+			if (idx == kset->size) p.mark = "break";
+			else p.mark = (l_num(idx) == 0 || r_num(idx) == 0) ? "break" : "branch";
+			return;
+		}
+	}
+}
+
+void delete_nodes(const std::vector<uint64_t> &nodes)
+{
+	for (uint64_t v : nodes) set_entity_delete(kset->del_flag, v);
+}
+
+// the path as it reads from left to right: k-mer of its first node in front of, or behind, the steps' bases (:335-342)
+std::string path_sequence(uint64_t first_node, int direct, std::string steps)
+{
+	const std::string kmer = bit2seq(kset->array[first_node].kmer, KmerSize);
+	if (direct == 1) return kmer + steps;
+	std::reverse(steps.begin(), steps.end());
+	return steps + kmer;
+}
+
+// remove_error_tips, :281-355
+void remove_tips(const std::vector<uint64_t> &tips)
+{
+	uint64_t total_num = 0, total_len = 0;
+	const string path = Output_prefix + ".contig.tip.fa";
+	ofstream out(path.c_str());
+	if (!out) cerr << "fail to open file " << path << endl;
+	for (uint64_t idx : tips) {
+		const int direct = (l_num(idx) == 1) ? -1 : 1;
+		Path p;
+		linear_path(idx, direct, Tip_len_cutoff, p);
+		const double avg = (double)p.depth / p.len;
+		if (!(avg <= Tip_depth_cutoff && p.len <= Tip_len_cutoff)) continue;
+		total_num++;
+		total_len += p.len;
+		delete_nodes(p.nodes);
+		recalculate(p.last);
+		set_flag(p.last, IN_TIP);
+		const uint64_t left_kmer = direct == 1 ? kset->array[idx].kmer : kmer_at(p.last), right_kmer = direct == 1 ? kmer_at(p.last) : kset->array[idx].kmer;
+		const char *left_mark = direct == 1 ? "break" : p.mark, *right_mark = direct == 1 ? p.mark : "break";
+		out << ">tip_" << total_num << "\tlength: " << p.len + KmerSize << "\tavgDepth: " << avg << "\tLeftEndKmer: " << left_kmer << " " << left_mark
+		    << "\tRightEndKmer: " << right_kmer << " " << right_mark << "\n" << path_sequence(idx, direct, p.str) << "\n";
+	}
+	out.close();
+	cerr << "\nremove total tip number:  " << total_num << endl;
+	cerr << "remove total tip length:  " << total_len << endl;
+}
+
+// get_branch_bases, :361-370
+void branch_bases(uint32_t link, std::vector<uint8_t> &vb, std::vector<uint8_t> &vd)
+{
+	for (int j = 0; j < 4; j++) {
+		const int depth = get_next_kmer_depth(link, j);
+		if (depth > KmerFreqCutoff) {
+			vb.push_back(j);
+			vd.push_back(depth);
+		}
+	}
+}
+
+// remove_lowCov_edges, :601-776: rightward edges of a branching node first, then its leftward ones (whose header line is spelt
+// differently, :763)
+void remove_low_edges(const std::vector<uint64_t> &branches)
+{
+	int total_num = 0, total_len = 0;
+	const string path = Output_prefix + ".contig.lowedge.fa";
+	ofstream out(path.c_str());
+	if (!out) cerr << "fail to open file " << path << endl;
+	for (uint64_t idx : branches) {
+		for (int direct = 1; direct >= -1; direct -= 2) {
+			if ((direct == 1 ? r_num(idx) : l_num(idx)) < 2) continue;
+			std::vector<uint8_t> vb, vd;
+			branch_bases(direct == 1 ? kset->array[idx].r_link : kset->array[idx].l_link, vb, vd);
+			for (size_t j = 0; j < vb.size(); j++) {
+				bool flipped;
+				const uint64_t key = canonical(direct == 1 ? next_rightward(kset->array[idx].kmer, vb[j]) : next_leftward(kset->array[idx].kmer, vb[j]), flipped);
+				const int direct1 = flipped ? -direct : direct;
+				const uint64_t idx1 = exist_kmerset(kset, key);
+				if (!is_linear(idx1)) continue;
+				Path p;
+				linear_path(idx1, direct1, LowCovEdge_len_cutoff, p);
+				const int len = p.len + 1, depth = p.depth + vd[j];
+				const double avg = (double)depth / len;
+				if (!(len <= LowCovEdge_len_cutoff && avg <= LowCovEdge_depth_cutoff && !is_linear(p.last))) continue;
+				total_num++;
+				total_len += len;
+				delete_nodes(p.nodes);
+				recalculate(p.last);
+				recalculate(idx);
+				set_flag(idx, IN_LOWEDGE);
+				set_flag(p.last, IN_LOWEDGE);
+				const std::string seq = path_sequence(idx1, direct1, p.str);
+				if (direct == 1)
+					out << ">lowedge_" << total_num << "\tlength: " << len + KmerSize << "\tavgDepth: " << avg << "\tLeftEndKmer: " << kset->array[idx].kmer
+					    << " branch" << "\tRightEndKmer: " << kmer_at(p.last) << " " << p.mark << "\n" << seq << "\n";
+				else
+					out << ">lowedge_" << total_num << "    length:" << len + KmerSize << "    avgDepth:" << avg << "\tLeftEndKmer: " << kmer_at(p.last) << " "
+					    << p.mark << "\tRightEndKmer: " << kset->array[idx].kmer << " branch" << "\n" << seq << "\n";
+			}
+		}
+	}
+	cerr << "\nremove total lowCovEdge number: " << total_num << endl;
+	cerr << "remove total lowCovEdge length: " << total_len << endl;
+	out.close();
+}
+
+// compare_two_seq_simple, :587-595: gap columns do not count
+int count_differences(const std::string &a, const std::string &b)
+{
+	int n = 0;
+	for (size_t i = 0; i < a.size(); i++)
+		if (a[i] != b[i] && a[i] != '-' && b[i] != '-') n++;
+	return n;
+}
+
+// global_aligning, global_aligning.cpp:98-182: Needleman-Wunsch with match 3, mismatch -5, gap -5; on equal scores a
+// substitution goes before a gap in the first sequence, that before a gap in the second (get_max_score, :20-35)
+void global_align(const std::string &si, const std::string &sj, std::string &ai, std::string &aj)
+{
+	const int gap = -5, ni = si.size(), nj = sj.size(), w = nj + 1;
+	std::vector<int> score((size_t)(ni + 1) * w), from((size_t)(ni + 1) * w);
+	score[0] = from[0] = 0;
+	for (int j = 1; j <= nj; j++) score[j] = gap * j, from[j] = 1;
+	for (int i = 1; i <= ni; i++) score[i * w] = gap * i, from[i * w] = 2;
+	for (int i = 1; i <= ni; i++)
+		for (int j = 1; j <= nj; j++) {
+			const char a = si[i - 1], b = sj[j - 1];   // A C G T only: paths are written from 2-bit codes
+			const int sub = score[(i - 1) * w + j - 1] + (a == b ? 3 : -5), gi = score[i * w + j - 1] + gap, gj = score[(i - 1) * w + j] + gap;
+			int best, dir;
+			if (sub >= gi && sub >= gj) best = sub, dir = 0;
+			else if (gi > sub && gi >= gj) best = gi, dir = 1;
+			else best = gj, dir = 2;
+			score[i * w + j] = best;
+			from[i * w + j] = dir;
+		}
+	int i = ni, j = nj;
+	do {                             // trace_back, global_aligning.cpp:39-68
+		const int dir = from[i * w + j];
+		if (dir == 0) ai.push_back(si[--i]), aj.push_back(sj[--j]);
+		else if (dir == 1) ai.push_back('-'), aj.push_back(sj[--j]);
+		else ai.push_back(si[--i]), aj.push_back('-');
+	} while (i > 0 || j > 0);
+	std::reverse(ai.begin(), ai.end());
+	std::reverse(aj.begin(), aj.end());
+}
+
+// remove_hetero_bubbles, :375-582
+void remove_bubbles(const std::vector<uint64_t> &branches)
+{
+	const string path = Output_prefix + ".contig.bubble.fa";
+	ofstream out(path.c_str());
+	if (!out) cerr << "fail to open file " << path << endl;
+	uint64_t total_num = 0, total_len = 0;
+	for (uint64_t idx : branches) {
+		int direct = 0;
+		std::vector<uint8_t> vb, vd;
+		if (l_num(idx) == 2 && r_num(idx) == 1) {
+			direct = -1;
+			branch_bases(kset->array[idx].l_link, vb, vd);
+		} else if (l_num(idx) == 1 && r_num(idx) == 2) {
+			direct = 1;
+			branch_bases(kset->array[idx].r_link, vb, vd);
+		} else {
+			continue;
+		}
+		uint64_t first[2];
+		int dir[2];
+		for (int e = 0; e < 2; e++) {
+			bool flipped;
+			const uint64_t key = canonical(direct == 1 ? next_rightward(kset->array[idx].kmer, vb[e]) : next_leftward(kset->array[idx].kmer, vb[e]), flipped);
+			dir[e] = flipped ? -direct : direct;
+			first[e] = exist_kmerset(kset, key);
+		}
+		if (!is_linear(first[0]) || !is_linear(first[1])) continue;
+		Path p[2];
+		linear_path(first[0], dir[0], Bubble_len_cutoff, p[0]);
+		linear_path(first[1], dir[1], Bubble_len_cutoff, p[1]);
+		const double avg1 = (double)p[0].depth / p[0].len, avg2 = (double)p[1].depth / p[1].len;
+		if (p[0].last != p[1].last) {
+			if (avg1 > LowCovEdge_depth_cutoff && avg2 > LowCovEdge_depth_cutoff) set_flag(idx, IN_REPEAT);   // a tiny repeat, no bubble (:471-473)
+			continue;
+		}
+		std::string s1 = path_sequence(first[0], dir[0], p[0].str), s2 = path_sequence(first[1], dir[1], p[1].str);
+		if (dir[0] != dir[1]) {      // :494-497
+			std::reverse(s1.begin(), s1.end());
+			complement_sequence(s1);
+		}
+		const int len1 = p[0].len + 1, len2 = p[1].len + 1;   // the branching base counts (:500-503)
+		double diff_rate = 0;
+		const char *type = "";
+		if (len1 == len2) {
+			diff_rate = (double)count_differences(s1, s2) / len1;
+			type = "SNP";
+		}
+		if (len1 != len2 || diff_rate > Bubble_base_diff_rate_cutoff) {
+			std::string a1, a2;
+			global_align(s1, s2, a1, a2);
+			s1 = a1;
+			s2 = a2;
+			diff_rate = (double)count_differences(s1, s2) / len1;
+			type = "INDEL";
+		}
+		if (!(diff_rate < Bubble_base_diff_rate_cutoff && abs(len1 - len2) < Bubble_len_cutoff * Bubble_len_diff_rate_cutoff &&
+		      (len1 <= Bubble_len_cutoff && len2 <= Bubble_len_cutoff)))
+			continue;
+		const int removed = avg1 < avg2 ? 1 : 2;            // the branch of lower depth goes (:531-551)
+		delete_nodes(p[removed - 1].nodes);
+		recalculate(p[removed - 1].last);
+		recalculate(idx);
+		total_num++;
+		total_len += removed == 1 ? len1 : len2;
+		const uint64_t left_kmer = direct == 1 ? kset->array[idx].kmer : kmer_at(p[0].last), right_kmer = direct == 1 ? kmer_at(p[0].last) : kset->array[idx].kmer;
+		const char *left_mark = direct == 1 ? "branch" : p[0].mark, *right_mark = direct == 1 ? p[0].mark : "branch";
+		out << ">bubble_" << total_num << "\ttype: " << type << "\tlength1: " << len1 + KmerSize << "\tavgDepth1: " << avg1 << "\tlength2: " << len2 + KmerSize
+		    << "\tavgDepth2: " << avg2 << "\tremoved: " << removed << "\tLeftEndKmer: " << left_kmer << " " << left_mark << "\tRightEndKmer: " << right_kmer
+		    << " " << right_mark << "\n" << s1 << "\n" << s2 << "\n";
+		set_flag(idx, IN_BUBBLE);
+		set_flag(p[0].last, IN_BUBBLE);
+	}
+	cerr << "\nremove total bubble number: " << total_num << endl;
+	cerr << "remove total bubble length: " << total_len << endl;
+	out.close();
+}
+
+// read_out_contig, :900-1046: the contigs come from the GPU in the order of the reference's scan
+int read_out(double &ms_gpu, double &ms_files)
+{
+	const string seq_path = Output_prefix + ".contig.seq.fa", depth_path = Output_prefix + ".contig.seq.depth";
+	ofstream seq_out(seq_path.c_str()), depth_out(depth_path.c_str());
+	if (!seq_out || !depth_out) cerr << "fail to open contig file " << seq_path << "\t" << depth_path << endl;
+	const string small_path = Output_prefix + ".contig.small.fa", small_depth_path = Output_prefix + ".contig.small.depth";
+	ofstream small_out(small_path.c_str()), small_depth_out(small_depth_path.c_str());
+	if (!small_out || !small_depth_out) cerr << "fail to open small file " << small_path << "\t" << small_depth_path << endl;
+
+	auto t0 = std::chrono::steady_clock::now();
+	dbgk_contig *h = NULL;
+	dbgk_contig_params prm = {KmerSize, KmerFreqCutoff < 0 ? 0 : KmerFreqCutoff, Contig_len_cutoff, 0};
+	const char *dev = getenv("DBGK_DEVICE");
+	dbgk_contig_summary sum;
+	int rc = dbgk_contig_create(&prm, dev ? atoi(dev) : 0, &h);
+	if (!rc) rc = dbgk_contig_set_table(h, kset->size, reinterpret_cast<const dbgk_node *>(kset->array), kset->nul_flag, kset->del_flag, klink);
+	if (!rc) rc = dbgk_contig_read_out(h, &sum);
+	if (rc) {
+		cerr << "contig read-out on the GPU failed: " << dbgk_strerror(rc) << " " << dbgk_last_error() << endl;
+		if (h) dbgk_contig_destroy(h);
+		return rc;
+	}
+	std::vector<uint64_t> off(sum.contigs + 1);
+	std::vector<dbgk_contig_record> rec(sum.contigs);
+	std::string seqs(sum.bytes, '\0'), depths(sum.bytes, '\0');
+	dbgk_contig_results(h, off.data(), rec.data(), &seqs[0], &depths[0]);
+	dbgk_contig_timing tm;
+	dbgk_contig_timing_get(h, &tm);
+	dbgk_contig_destroy(h);
+	ms_gpu = ms_since(t0);
+	if (getenv("DBGK_TIMINGS"))
+		cerr << "Contig read-out (ms): upload " << tm.ms_upload << " (" << tm.upload_bytes << " bytes) compact " << tm.ms_compact << " successors "
+		     << tm.ms_successors << " mutual " << tm.ms_mutual << " rank " << tm.ms_rank << " (" << sum.rounds << " rounds) place " << tm.ms_place
+		     << " scatter " << tm.ms_scatter << " emit " << tm.ms_emit << " host walk " << tm.ms_host_walk << "; contigs by kernels "
+		     << sum.kernel_contigs << ", by the host walker " << sum.host_contigs << endl;
+
+	t0 = std::chrono::steady_clock::now();
+	static const char *const kMark[2] = {"break", "branch"}, *const kRepeat[3] = {"Unknown", "Unique", "Repeat"};
+	uint64_t break_points = 0, branch_points = 0;
+	std::vector<std::string> header(sum.contigs);
+	std::vector<std::pair<uint64_t, uint64_t>> order(sum.contigs);   // (length, index in scan order)
+	for (uint64_t i = 0; i < sum.contigs; i++) {
+		const dbgk_contig_record &r = rec[i];
+		const int contig_len = (int)r.left_len + KmerSize + (int)r.right_len;
+		double avg = (int)r.left_depth + (int)r.right_depth;
+		avg /= (double)((int)r.left_len + (int)r.right_len);
+		(r.right_mark ? branch_points : break_points)++;
+		(r.left_mark ? branch_points : break_points)++;
+		char num[64];
+		snprintf(num, sizeof num, "%.17g", avg);       // boost::lexical_cast<string>(double), :1006
+		header[i] = "\tlength: " + std::to_string(contig_len) + "\tavgDepth: " + num + "\tLeftEndKmer: " + std::to_string(kmer_at(r.left_end)) + " " +
+		            kMark[r.left_mark] + "-" + kRepeat[r.left_repeat] + "\tRightEndKmer: " + std::to_string(kmer_at(r.right_end)) + " " + kMark[r.right_mark] +
+		            "-" + kRepeat[r.right_repeat] + "\t" + ((r.left_repeat == 2 && r.right_repeat == 2) ? "RepeatNode" : "") + "\n";
+		order[i] = std::make_pair(off[i + 1] - off[i], i);
+	}
+	// the reference sorts its records with std::sort and cmpSeqByLen (:48-50, :1014): the same algorithm with the same
+	// comparisons leaves equal lengths in the same places
+	std::sort(order.begin(), order.end(), [](std::pair<uint64_t, uint64_t> a, std::pair<uint64_t, uint64_t> b) { return b.first < a.first; });
+	uint64_t contig_num = 0, contig_len = 0, small_num = 0, small_len = 0, id = 1;
+	for (const auto &o : order) {
+		const uint64_t i = o.second, len = o.first;
+		const bool big = len >= (uint64_t)Contig_len_cutoff;
+		ofstream &fa = big ? seq_out : small_out, &dp = big ? depth_out : small_depth_out;
+		fa << ">ctg_" << id << header[i];
+		fa.write(&seqs[off[i]], len);
+		fa << "\n";
+		dp << ">ctg_" << id << "\n";
+		dp.write(&depths[off[i]], len);
+		dp << "\n";
+		(big ? contig_num : small_num)++;
+		(big ? contig_len : small_len) += len;
+		id += 2;
+	}
+	cerr << "\ncontig break-point number:     " << break_points << endl;
+	cerr << "contig branch-point number:    " << branch_points << endl;
+	cerr << "\nTotal contig number:   " << contig_num << endl;
+	cerr << "Total contig length:   " << contig_len << endl;
+	cerr << "\nTotal small edge number:   " << small_num << endl;
+	cerr << "Total small edge length:   " << small_len << endl;
+	ms_files = ms_since(t0);
+	return 0;
+}
+
+void finished(const char *word)
+{
+	time_end = clock();
+	cerr << word << " Run time: " << double(time_end - time_start) / CLOCKS_PER_SEC << endl;
+}
+
+} // namespace
+
+// build_contig_sequence, :54-102
+int run_contig_stage()
+{
+	double ms_first = 0, ms_tip = 0, ms_edge = 0, ms_bubble = 0, ms_gpu = 0, ms_files = 0;
+	cerr << "\nStart to calulate kmer links information!" << endl;
+	auto t0 = std::chrono::steady_clock::now();
+	std::vector<uint64_t> tips, branches;
+	if (DbgkKmerLinks) {             // the first pass came with the table, computed on the device (dbgk_export_host_table_links)
+		klink = DbgkKmerLinks;
+		tips.swap(DbgkTipNodes);
+		branches.swap(DbgkBranchNodes);
+	} else {                         // a table laid out on the host (DBGK_LAYOUT=ref): its slots are not the device table's, so the same pass here.
+		                                 // The records live until the program leaves (main.cpp leaves through _exit): never freed
+		klink = static_cast<uint16_t *>(calloc(kset->size, sizeof(uint16_t)));
+		if (!klink) return DBGK_ERR_NOMEM;
+		first_pass_host(tips, branches);
+	}
+	write_kmer_freq_file(Output_prefix + ".contig.kmer.freq", KmerFreqCutoff);   // the five counts and the file, :186-203
+	ms_first = ms_since(t0);
+	finished("Finished!");
+
+	if (is_remove_tip) {
+		cerr << "\nStart to remove tips caused by sequencing error!" << endl;
+		t0 = std::chrono::steady_clock::now();
+		remove_tips(tips);
+		ms_tip = ms_since(t0);
+		finished("Finished!");
+	}
+	if (is_remove_lowedge) {
+		cerr << "\nStart to remove small low coverage edges between two branching nodes!" << endl;
+		t0 = std::chrono::steady_clock::now();
+		remove_low_edges(branches);
+		ms_edge = ms_since(t0);
+		finished("Finshed!");        // :82
+	}
+	if (is_remove_bubble) {
+		cerr << "\nStart to remove bubbles caused by repeats and heterozygotes!" << endl;
+		t0 = std::chrono::steady_clock::now();
+		remove_bubbles(branches);
+		ms_bubble = ms_since(t0);
+		finished("Finished!");
+	}
+	cerr << "\nStart to read out contig sequence and the depth information!" << endl;
+	const int rc = read_out(ms_gpu, ms_files);
+	if (rc) return rc;
+	finished("Finished!");
+	if (getenv("DBGK_TIMINGS"))
+		cerr << "Contig stage host passes (ms): first pass " << ms_first << " tips " << ms_tip << " low edges " << ms_edge << " bubbles " << ms_bubble
+		     << " read-out " << ms_gpu << " headers, sort and files " << ms_files << endl;
+	return 0;
+}

@@ -1,0 +1,12 @@
+// contig_stage.h -- the contig stage of debruijn_contig: graph simplification on the host, contig read-out on the GPU.
+//
+// Follows build_contig_sequence() of the reference (DBG_contig/contig.cpp:54-102) pass by pass, with its stderr protocol and its
+// eight <prefix>.contig.* files.  Linked into bin/debruijn_contig only: a program that links the reference's own contig.cpp next to
+// libdbgasm_host.so keeps its own build_contig_sequence() and its own definitions of the -D/-T/... globals.
+#ifndef DBGK_HOST_CONTIG_STAGE_H_
+#define DBGK_HOST_CONTIG_STAGE_H_
+
+// runs on `kset` as build_debruijn_graph() left it (k <= 31); 0, or a DBGK_ERR_* code of the GPU read-out
+int run_contig_stage();
+
+#endif

@@ -1,12 +1,12 @@
-// debruijn_contig -- command line of the graph-construction stage on MI355X.
+// debruijn_contig -- command line of the contig builder on MI355X.
 //
 // Same options, defaults and positional argument as the reference's DBG_contig/main.cpp:97-124,
 // 166-193 (getopt string "k:r:f:o:t:i:l:e:b:D:T:I:P:W:C:G:B:U:L:E:M:h"); the help wording is this build's own.  The graph stage
-// (build_debruijn_graph) runs on the GPU.  The contig stage (tip/bubble removal, contig read-out:
-// DBG_contig/contig.cpp) is the reference's unchanged host code and is NOT part of this repository;
-// when this program is linked together with it build_contig_sequence() is
-// called exactly as in the reference, otherwise the program stops after the graph stage and
-// writes the artefacts that stage defines: <prefix>.contig.kmer.freq (first pass of
+// (build_debruijn_graph) runs on the GPU.  The contig stage (DBG_contig/contig.cpp) is this build's own for k <= 31
+// (contig_stage.cpp): tip, low-coverage-edge and bubble removal on the host in the reference's order, the contig read-out on the
+// GPU, the reference's eight <prefix>.contig.* files.  When this program is linked together with the reference's contig.cpp
+// instead its build_contig_sequence() is called exactly as in the reference.  For k = 32 and above the
+// program stops after the graph stage, as it does for a hash array of 2^32 - 1 entries or more, and writes the artefacts that stage defines: <prefix>.contig.kmer.freq (first pass of
 // calculate_kmer_links) and, if DBGK_DUMP is set, the canonical node dump.
 #include <unistd.h>
 #include <chrono>
@@ -15,10 +15,11 @@
 #include <cstring>
 
 #include "DBGgraph.h"
+#include "contig_stage.h"
 #include "dbgk_env.h"
 
-// parameters of the contig stage: parsed for command-line compatibility (main.cpp:177-189) and
-// handed to the contig stage when it is linked in (it defines the same globals; these are weak).
+// parameters of the contig stage (main.cpp:177-189): read by contig_stage.cpp; the reference's contig.cpp, when it is linked in
+// instead, defines the same globals (these are weak).
 int KmerFreqCutoff __attribute__((weak)) = 2;
 int is_remove_tip __attribute__((weak)) = 1;
 int Tip_len_cutoff __attribute__((weak)) = 100;
@@ -37,12 +38,12 @@ void build_contig_sequence() __attribute__((weak));  // DBG_contig/contig.h:67, 
 static void print_options(ostream &os, bool with_k_max)
 {
 	// option letters, argument kinds, defaults and order follow the reference (DBG_contig/main.cpp:97-124); the wording is ours
-	os << "   -k <int>    k-mer length" << (with_k_max ? " (the contig stage: at most 31; graph stage alone: up to 63, 128-bit keys)" : "") << " [" << KmerSize << "]" << endl
+	os << "   -k <int>    k-mer length" << (with_k_max ? " (contigs are built for k up to 31; the graph stage alone goes up to 63, 128-bit keys)" : "") << " [" << KmerSize << "]" << endl
 	   << "   -r <int>    longest read length used; longer reads are cut to this [" << maxReadLen << "]" << endl
 	   << "   -f <int>    input format: 1 = FASTQ, 2 = FASTA, one sequence per line, plain or .gz [" << Input_file_format << "]" << endl
 	   << "   -o <str>    prefix of the output files [" << Output_prefix << "]" << endl
-	   << "   -t <int>    host threads (table zeroing, contig stage; the k-mer work runs on the GPU) [" << threadNum << "]" << endl
-	   << "   -i <float>  initial size of the k-mer hash table in units of 1e9 entries, 16 bytes each [" << initHashSize << "]" << endl
+	   << "   -t <int>    host threads (table zeroing; the k-mer work and the contig read-out run on the GPU) [" << threadNum << "]" << endl
+	   << "   -i <float>  initial size of the k-mer hash table in units of 1e9 entries, 16 bytes each (contigs are built for tables below 2^32 - 1 entries) [" << initHashSize << "]" << endl
 	   << "   -l <float>  load factor at which the hash table is enlarged [" << hashLoadFactor << "]" << endl
 	   << "   -e <int>    how many times the hash table may double before further input is dropped [" << maxDoubleHashTimes << "]" << endl
 	   << "   -b <int>    reads per block; the table is checked for enlarging after every full block [" << BufferNum << "]" << endl
@@ -132,6 +133,12 @@ int main(int argc, char *argv[])
 	vector<string> reads_files;
 	reading_file_list(reads_lib_file, reads_files);
 
+	// this build's contig stage takes the first pass (link records, delete flags, tip / branch lists) from the device with the table;
+	// a table laid out like the reference's (DBGK_LAYOUT=ref) is made on the host, and the stage makes the pass there
+	const char *layout = getenv("DBGK_LAYOUT");
+	const bool own_contig_stage = KmerSize <= 31 && !build_contig_sequence;
+	if (own_contig_stage && !(layout && !strcmp(layout, "ref"))) setenv("DBGK_LINKS", "1", 0);
+
 	const double t_build0 = wall_now();
 	build_debruijn_graph(reads_files);
 	const double t_build1 = wall_now();
@@ -152,9 +159,14 @@ int main(int argc, char *argv[])
 		build_contig_sequence();
 		cerr << "\nRemove tips, merge bubbles, output contig sequence finished !" << endl;
 		cerr << "\nAssembly completely finished!" << endl;
-	} else {
+	} else if (own_contig_stage && kset->size < 0xffffffffull) { // the read-out numbers slots with 32 bits (include/dbgk.h, CONTIG section)
+		if (run_contig_stage() != 0) leave(1);
+		cerr << "\nRemove tips, merge bubbles, output contig sequence finished !" << endl;
+		cerr << "\nAssembly completely finished!" << endl;
+	} else { // k = 32: the reference's consumer stops at 31 (DBG_contig/main.cpp:100), and so does this build's; a table of 2^32 - 1 slots or more
 		cerr << "\nStart to calulate kmer links information!" << endl;
 		write_kmer_freq_file(Output_prefix + ".contig.kmer.freq", KmerFreqCutoff);
+		if (own_contig_stage) cerr << "\nThe hash array has " << kset->size << " entries; this build's contig stage takes fewer than 4294967295" << endl;
 		cerr << "\nGraph stage finished (contig stage not linked in, see INTEGRATION.md)" << endl;
 	}
 	if (getenv("DBGK_TIMINGS"))

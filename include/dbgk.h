@@ -1024,6 +1024,79 @@ int dbgk_super_emit(dbgk_super *s, const char *bases, const uint64_t *offsets, u
                     uint64_t n_items, char *out, uint64_t capacity, uint64_t *out_len);
 int dbgk_super_batch_stats(dbgk_super *s, dbgk_super_timing *out);
 
+/* ---- CONTIG: the contig read-out of debruijn_contig on the GPU (additions to ABI 7) ---------------------------------------------
+ * read_out_contig (DBG_contig/contig.cpp:900-1011) scans the simplified table in slot order; at the first live linear node it
+ * walks right, then left (get_linear_seq, :832-896), deletes what it passes and stops at the first neighbour that is not linear or
+ * not there.  Here every live linear node finds its two successors on the device (the probe of exist_kmerset, kmerSet.cpp:280-302,
+ * on the host-layout table), chains whose every step is answered by the neighbour's link back are ranked by pointer jumping from
+ * their smallest slot -- where the reference's scan starts them -- and written out on the device; every other chain (a step that
+ * is not answered, a step of a node onto itself, a cycle) is walked on the host in ascending slot order, as the reference does.
+ * The handle takes the table as the host holds it after simplification and no graph handle.  Contigs come in the order the
+ * reference's scan finds them; sorting, ids and the -M split are the caller's.  Every byte equals the reference's.             */
+typedef struct dbgk_contig dbgk_contig;
+
+typedef struct dbgk_contig_params {
+	int32_t k;                  /* 1 .. 31                                                                                */
+	int32_t kmer_freq_cutoff;   /* -D, as the klink records were computed with; kept for the record, the read-out reads klink */
+	int32_t contig_len_cutoff;  /* -M; kept for the record: the split into contigs and small ones is the caller's         */
+	int32_t reserved;           /* 0                                                                                      */
+} dbgk_contig_params;
+
+/* one contig: bytes left_len (reversed left walk) + k (the anchor's k-mer) + right_len (right walk) */
+typedef struct dbgk_contig_record {
+	uint64_t anchor;                    /* the slot the walks start from                                                  */
+	uint64_t left_end, right_end;       /* the slot a walk stopped at; the table size when there was no such node         */
+	uint32_t left_len, right_len;       /* steps of either walk (contig_leftward_len, contig_rightward_len)               */
+	uint32_t left_depth, right_depth;   /* sums of the steps' link depths                                                 */
+	uint8_t  left_mark, right_mark;     /* 0 break, 1 branch                                                              */
+	uint8_t  left_repeat, right_repeat; /* 0 Unknown, 1 Unique, 2 Repeat                                                  */
+	uint8_t  host_walked;               /* 1: read out by the host walker                                                 */
+	uint8_t  mid_depth;                 /* the depth byte of the k-mer's k bases: (char)avgDepth, 10 and 62 one less      */
+	uint8_t  pad[2];
+} dbgk_contig_record;
+
+typedef struct dbgk_contig_summary {
+	uint64_t contigs;           /* all, = kernel_contigs + host_contigs                                                   */
+	uint64_t kernel_contigs;    /* read out by the kernels                                                                */
+	uint64_t host_contigs;      /* read out by the host walker                                                            */
+	uint64_t bytes;             /* bases of all contigs (as many depth bytes)                                             */
+	uint64_t linear_nodes;      /* live linear nodes of the table                                                         */
+	uint64_t host_nodes;        /* ... on chains handed to the host walker                                                */
+	uint64_t rounds;            /* pointer-jumping rounds                                                                 */
+	uint64_t reserved;
+} dbgk_contig_summary;
+
+typedef struct dbgk_contig_timing {
+	uint64_t upload_bytes;      /* table, flags and link records copied to the device by dbgk_contig_set_table            */
+	uint64_t emit_bytes;        /* bytes the emit kernel wrote (bases + depths)                                           */
+	double ms_upload;           /* wall time of that copy                                                                 */
+	double ms_compact;          /* device time: numbering the live linear nodes (two kernels)                             */
+	double ms_successors;       /* device time of the successor kernel                                                    */
+	double ms_mutual;           /* device time of the order-independence check and the initial port states                */
+	double ms_rank;             /* device time of all pointer-jumping rounds                                              */
+	double ms_place;            /* device time: classify, contig numbering and offsets                                    */
+	double ms_scatter;          /* device time of the scatter of the steps                                                */
+	double ms_emit;             /* device time of the emit kernel                                                         */
+	double ms_host_walk;        /* wall time of the host walker                                                           */
+} dbgk_contig_timing;
+
+/* DBGK_ERR_ARG on a bad parameter, before any device work; DBGK_ERR_HIP without a usable gfx950 device: no host fall-back  */
+int dbgk_contig_create(const dbgk_contig_params *p, int device, dbgk_contig **out);
+int dbgk_contig_destroy(dbgk_contig *c);
+/* the table after simplification, as the host holds it: array[size], nul_flag and del_flag of size / 8 + 1 bytes (kmerSet.h:144-169),
+ * klink[size] in the layout of dbgk_export_host_table_links (byte 1 bit 0 = linear).  2 <= size < 2^32 - 1.  Copied to the device;
+ * the host arrays are read again by dbgk_contig_read_out (host walker) and must stay as they are until it returns.             */
+int dbgk_contig_set_table(dbgk_contig *c, uint64_t size, const dbgk_node *array, const uint8_t *nul_flag, const uint8_t *del_flag,
+                          const uint16_t *klink);
+/* the read-out; neither the host arrays nor their device copies are changed.  out may be NULL.  More than 2^30 - 1 live linear
+ * nodes are DBGK_ERR_ARG.                                                                                                     */
+int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out);
+int dbgk_contig_summary_get(dbgk_contig *c, dbgk_contig_summary *out);
+/* contigs in the order of the reference's scan: offsets (summary.contigs + 1; contig i is bytes [offsets[i], offsets[i + 1]) of
+ * bases and of depths), records (summary.contigs), bases and depths (summary.bytes each).  Any may be NULL.                   */
+int dbgk_contig_results(dbgk_contig *c, uint64_t *offsets, dbgk_contig_record *records, char *bases, char *depths);
+int dbgk_contig_timing_get(dbgk_contig *c, dbgk_contig_timing *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
