@@ -386,6 +386,8 @@ SYMBOLS = [
     ("dbgk_contig_summary_get", _i, [_vp, C.POINTER(ContigSummary)]),
     ("dbgk_contig_results", _i, [_vp, _vp, _vp, _vp, _vp]),
     ("dbgk_contig_timing_get", _i, [_vp, C.POINTER(ContigTiming)]),
+    ("dbgk_wide_contig_create", _i, [C.POINTER(ContigParams), _i, C.POINTER(_vp)]),
+    ("dbgk_wide_contig_set_table", _i, [_vp, _u64, _vp, _vp, _vp, _vp]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1577,13 +1579,15 @@ class ContigBuilder:
     """The contig read-out on the GPU (CONTIG section of include/dbgk.h).  set_table(array, nul_flag, del_flag, klink) takes the
     host-layout table after simplification: NODE_DTYPE array[size], the two flag arrays of size // 8 + 1 bytes (bit 128 >> (i % 8)
     of byte i // 8), the 2-byte link records (bit 8 = linear).  read_out() -> bases, depths, offsets, records, summary: contigs in
-    the order the reference's scan finds them."""
+    the order the reference's scan finds them.  wide=True: k up to 63 on a table of NODE32_DTYPE nodes (128-bit keys; parity
+    unpinned above k = 32), everything else the same."""
 
-    def __init__(self, k, kmer_freq_cutoff=2, contig_len_cutoff=125, device=0):
+    def __init__(self, k, kmer_freq_cutoff=2, contig_len_cutoff=125, device=0, wide=False):
+        self.wide = bool(wide)
         self._h = C.c_void_p()
         self._keep = None
-        _chk(lib().dbgk_contig_create(C.byref(ContigParams(k, kmer_freq_cutoff, contig_len_cutoff, 0)), device, C.byref(self._h)),
-             "dbgk_contig_create")
+        create = "dbgk_wide_contig_create" if self.wide else "dbgk_contig_create"
+        _chk(getattr(lib(), create)(C.byref(ContigParams(k, kmer_freq_cutoff, contig_len_cutoff, 0)), device, C.byref(self._h)), create)
 
     def close(self):
         if self._h:
@@ -1597,7 +1601,7 @@ class ContigBuilder:
         self.close()
 
     def set_table(self, array, nul_flag, del_flag, klink):
-        array = np.ascontiguousarray(array, dtype=NODE_DTYPE)
+        array = np.ascontiguousarray(array, dtype=NODE32_DTYPE if self.wide else NODE_DTYPE)
         size = len(array)
         nul_flag = np.ascontiguousarray(nul_flag, dtype=np.uint8)
         del_flag = np.ascontiguousarray(del_flag, dtype=np.uint8)
@@ -1605,8 +1609,8 @@ class ContigBuilder:
         if len(nul_flag) != size // 8 + 1 or len(del_flag) != size // 8 + 1 or len(klink) != size:
             raise ValueError("flag arrays of size // 8 + 1 bytes and one link record per slot")
         self._keep = (array, nul_flag, del_flag, klink)   # the host walker reads them during read_out
-        _chk(lib().dbgk_contig_set_table(self._h, size, array.ctypes.data, nul_flag.ctypes.data, del_flag.ctypes.data, klink.ctypes.data),
-             "dbgk_contig_set_table")
+        set_table = "dbgk_wide_contig_set_table" if self.wide else "dbgk_contig_set_table"
+        _chk(getattr(lib(), set_table)(self._h, size, array.ctypes.data, nul_flag.ctypes.data, del_flag.ctypes.data, klink.ctypes.data), set_table)
 
     def read_out(self):
         """-> bases (uint8), depths (uint8), offsets (uint64, contigs + 1), records (CONTIG_RECORD_DTYPE), summary (dict)"""

@@ -30,6 +30,7 @@
 #include "dbgk_fill.h"
 #include "dbgk_super.h"
 #include "dbgk_contig.h"
+#include "dbgk_wide_contig.h"
 
 // dbgk_sort.hip
 extern "C" int dbgk_internal_sort_pairs(uint64_t *d_keys, uint64_t *d_vals, uint64_t n, hipStream_t stream);

@@ -2,6 +2,11 @@
 // the live linear nodes, finds successors, checks order-independence, ranks the chains and writes the contigs; the two ordered
 // compactions scan their per-tile counts on the host (a few thousand numbers).  Chains the kernels hand over are walked here, the way
 // get_linear_seq does (DBG_contig/contig.cpp:832-896), in ascending slot order.
+//
+// A handle made by dbgk_wide_contig_create holds a table of 32-byte nodes (k up to 63, 128-bit keys; PARITY UNPINNED above k = 32, see
+// dbgk_wide_contig.h): the two kernels that read keys are the wide ones, everything else -- the other eight kernels, the scans, the
+// merge -- is the same code.  The host walker works on 128-bit keys for both kinds; a 16-byte node's key has the high word 0, where
+// every rule of include/dbgk_wide.h is the reference's.
 
 struct dbgk_contig {
 	int device = 0;
@@ -11,7 +16,10 @@ struct dbgk_contig {
 	dbgk_contig_params p{};
 	// the table: borrowed host arrays and their device copies
 	uint64_t size = 0;
+	bool wide = false;                       // 32-byte nodes: h_array32 / d_array32 instead of h_array / d_array
 	const dbgk_node *h_array = nullptr;
+	const dbgk_node32 *h_array32 = nullptr;
+	dbgk_node32 *d_array32 = nullptr;
 	const uint8_t *h_nul = nullptr, *h_del = nullptr;
 	const uint16_t *h_klink = nullptr;
 	Node *d_array = nullptr;
@@ -32,11 +40,11 @@ static_assert(sizeof(dbgk_contig_record) == 48 && sizeof(contigk::Record) == 48 
               offsetof(contigk::Record, left_mark) == 40 && offsetof(dbgk_contig_record, mid_depth) == 45, "dbgk_contig_record layout");
 static_assert(sizeof(dbgk_contig_summary) == 64 && sizeof(dbgk_contig_timing) == 88 && sizeof(contigk::PortState) == 16, "CONTIG layouts");
 
-extern "C" int dbgk_contig_create(const dbgk_contig_params *p, int device, dbgk_contig **out)
+static int contig_create(const dbgk_contig_params *p, int device, int k_max, dbgk_contig **out)
 {
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
-	if (!p || device < 0 || p->k < 1 || p->k > 31 || p->kmer_freq_cutoff < 0 || p->reserved) return DBGK_ERR_ARG;
+	if (!p || device < 0 || p->k < 1 || p->k > k_max || p->kmer_freq_cutoff < 0 || p->reserved) return DBGK_ERR_ARG;
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
 		g_last_error = "no usable HIP device";
@@ -46,6 +54,7 @@ extern "C" int dbgk_contig_create(const dbgk_contig_params *p, int device, dbgk_
 	if (!c) return DBGK_ERR_NOMEM;
 	c->device = device;
 	c->p = *p;
+	c->wide = k_max > 31;
 	int rc = DBGK_OK;
 	hipDeviceProp_t prop;
 	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
@@ -65,11 +74,16 @@ extern "C" int dbgk_contig_create(const dbgk_contig_params *p, int device, dbgk_
 	return DBGK_OK;
 }
 
+extern "C" int dbgk_contig_create(const dbgk_contig_params *p, int device, dbgk_contig **out) { return contig_create(p, device, 31, out); }
+
+extern "C" int dbgk_wide_contig_create(const dbgk_contig_params *p, int device, dbgk_contig **out) { return contig_create(p, device, 63, out); }
+
 static void contig_free_table(dbgk_contig *c)
 {
-	(void)hipFree(c->d_array); (void)hipFree(c->d_nul); (void)hipFree(c->d_del); (void)hipFree(c->d_klink);
+	(void)hipFree(c->d_array); (void)hipFree(c->d_array32); (void)hipFree(c->d_nul); (void)hipFree(c->d_del); (void)hipFree(c->d_klink);
 	(void)hipFree(c->d_bases); (void)hipFree(c->d_depths);
 	c->d_array = nullptr;
+	c->d_array32 = nullptr;
 	c->d_nul = c->d_del = c->d_bases = c->d_depths = nullptr;
 	c->d_klink = nullptr;
 	c->table_set = c->done = false;
@@ -88,30 +102,39 @@ extern "C" int dbgk_contig_destroy(dbgk_contig *c)
 	return DBGK_OK;
 }
 
-extern "C" int dbgk_contig_set_table(dbgk_contig *c, uint64_t size, const dbgk_node *array, const uint8_t *nul_flag, const uint8_t *del_flag,
-                                     const uint16_t *klink)
+// array: `size` nodes of node_bytes bytes each (16: dbgk_node, 32: dbgk_node32), as the handle's kind has them
+static int contig_set_table(dbgk_contig *c, uint64_t size, const void *array, size_t node_bytes, const uint8_t *nul_flag, const uint8_t *del_flag,
+                            const uint16_t *klink)
 {
 	// slots and ports are 32-bit on the device, 0xffffffff is "none"
 	if (!c || !array || !nul_flag || !del_flag || !klink || size < 2 || size >= 0xffffffffull) return DBGK_ERR_ARG;
+	if (c->wide != (node_bytes == sizeof(dbgk_node32))) {
+		g_last_error = c->wide ? "a wide contig handle takes its table through dbgk_wide_contig_set_table" : "dbgk_wide_contig_set_table needs a handle of dbgk_wide_contig_create";
+		return DBGK_ERR_STATE;
+	}
 	HIPCHK(hipSetDevice(c->device));
 	contig_free_table(c);
 	const uint64_t flag_bytes = size / 8 + 1;
-	if (hipMalloc(&c->d_array, size * sizeof(Node)) != hipSuccess || hipMalloc(&c->d_nul, flag_bytes) != hipSuccess ||
-	    hipMalloc(&c->d_del, flag_bytes) != hipSuccess || hipMalloc(&c->d_klink, size * 2) != hipSuccess) {
+	void *d_nodes = nullptr;
+	if (hipMalloc(&d_nodes, size * node_bytes) != hipSuccess) return DBGK_ERR_NOMEM;
+	if (c->wide) c->d_array32 = static_cast<dbgk_node32 *>(d_nodes);
+	else c->d_array = static_cast<Node *>(d_nodes);
+	if (hipMalloc(&c->d_nul, flag_bytes) != hipSuccess || hipMalloc(&c->d_del, flag_bytes) != hipSuccess || hipMalloc(&c->d_klink, size * 2) != hipSuccess) {
 		contig_free_table(c);
 		return DBGK_ERR_NOMEM;
 	}
 	const auto t0 = std::chrono::steady_clock::now();
-	HIPCHK(hipMemcpyAsync(c->d_array, array, size * sizeof(Node), hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(d_nodes, array, size * node_bytes, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(c->d_nul, nul_flag, flag_bytes, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(c->d_del, del_flag, flag_bytes, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(c->d_klink, klink, size * 2, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	c->timing = dbgk_contig_timing{};
 	c->timing.ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	c->timing.upload_bytes = size * (sizeof(Node) + 2) + 2 * flag_bytes;
+	c->timing.upload_bytes = size * (node_bytes + 2) + 2 * flag_bytes;
 	c->size = size;
-	c->h_array = array;
+	c->h_array = c->wide ? nullptr : static_cast<const dbgk_node *>(array);
+	c->h_array32 = c->wide ? static_cast<const dbgk_node32 *>(array) : nullptr;
 	c->h_nul = nul_flag;
 	c->h_del = del_flag;
 	c->h_klink = klink;
@@ -119,11 +142,26 @@ extern "C" int dbgk_contig_set_table(dbgk_contig *c, uint64_t size, const dbgk_n
 	return DBGK_OK;
 }
 
+extern "C" int dbgk_contig_set_table(dbgk_contig *c, uint64_t size, const dbgk_node *array, const uint8_t *nul_flag, const uint8_t *del_flag,
+                                     const uint16_t *klink)
+{
+	return contig_set_table(c, size, array, sizeof(dbgk_node), nul_flag, del_flag, klink);
+}
+
+extern "C" int dbgk_wide_contig_set_table(dbgk_contig *c, uint64_t size, const dbgk_node32 *array, const uint8_t *nul_flag, const uint8_t *del_flag,
+                                          const uint16_t *klink)
+{
+	return contig_set_table(c, size, array, sizeof(dbgk_node32), nul_flag, del_flag, klink);
+}
+
 namespace {
 
-// the reference's walk on the host table, with the delete flags of the chains walked so far
+// the reference's walk on the host table, with the delete flags of the chains walked so far.  Keys are 128-bit: a 16-byte node's has
+// the high word 0, where revcomp, the comparison and hash128 of include/dbgk_wide.h are the reference's 64-bit rules
 struct ContigHostWalker {
-	const dbgk_node *array;
+	using Key128 = dbgk_wide::Key128;
+	const dbgk_node *array;          // one of the two is set
+	const dbgk_node32 *array32;
 	const uint8_t *nul;
 	std::vector<uint8_t> del;
 	const uint16_t *klink;
@@ -131,24 +169,52 @@ struct ContigHostWalker {
 	int k;
 
 	static bool bit(const uint8_t *f, uint64_t i) { return (f[i >> 3] & (0x80u >> (i & 7u))) != 0; }
-	uint64_t revcomp(uint64_t kbit) const
+	Key128 key_at(uint64_t slot) const { return array32 ? Key128{array32[slot].kmer_hi, array32[slot].kmer_lo} : Key128{0, array[slot].kmer}; }
+	uint32_t link_at(uint64_t slot, bool right) const
 	{
-		uint64_t r = 0;
-		for (int i = 0; i < k; ++i) {
-			r = (r << 2) | (3u - (kbit & 3u));
-			kbit >>= 2;
+		return array32 ? (right ? array32[slot].r_link : array32[slot].l_link) : (right ? array[slot].r_link : array[slot].l_link);
+	}
+	// the two steps of contig.h:119-130; the mask has 2 k - 64 bits in hi, the leftward base lands in hi from k = 33 on
+	Key128 rightward(Key128 x, uint32_t base) const
+	{
+		Key128 r{(x.hi << 2) | (x.lo >> 62), (x.lo << 2) | base};
+		const int bits = 2 * k;
+		if (bits > 64) r.hi &= (1ull << (bits - 64)) - 1;
+		else {
+			r.hi = 0;
+			if (bits < 64) r.lo &= (1ull << bits) - 1;
 		}
 		return r;
 	}
-	uint64_t exist(uint64_t kmer) const   // exist_kmerset, kmerSet.cpp:280-302
+	Key128 leftward(Key128 x, uint32_t base) const
 	{
-		uint64_t slot = hash_code(kmer) % size;
+		Key128 r{x.hi >> 2, (x.lo >> 2) | (x.hi << 62)};
+		const int sh = 2 * (k - 1);
+		if (sh >= 64) r.hi += (uint64_t)base << (sh - 64);
+		else r.lo += (uint64_t)base << sh;
+		return r;
+	}
+	uint64_t exist(Key128 key) const   // exist_kmerset, kmerSet.cpp:280-302
+	{
+		uint64_t slot = dbgk_wide::hash128(key) % size;
 		for (uint64_t tries = 0; tries < size; ++tries) {
 			if (!bit(nul, slot)) return size;
-			if (array[slot].kmer == kmer) return bit(del.data(), slot) ? size : slot;
+			const Key128 at = key_at(slot);
+			if (at.hi == key.hi && at.lo == key.lo) return bit(del.data(), slot) ? size : slot;
 			slot = slot + 1 == size ? 0 : slot + 1;
 		}
 		return size;
+	}
+	std::string text(uint64_t slot) const   // the node's k bases
+	{
+		static const char fwd[] = "ACGT";
+		const Key128 x = key_at(slot);
+		std::string s(k, 'A');
+		for (int j = 0; j < k; ++j) {
+			const int sh = 2 * (k - 1 - j);
+			s[j] = fwd[(sh >= 64 ? x.hi >> (sh - 64) : x.lo >> sh) & 3u];
+		}
+		return s;
 	}
 	// get_linear_seq, contig.cpp:832-896; a walk that steps to a missing k-mer ends as break before klink is looked at
 	void walk(uint64_t idx, int dir, uint32_t &len, uint32_t &depth, std::string &seq, std::string &depths, uint64_t &last, uint8_t &mark,
@@ -156,23 +222,22 @@ struct ContigHostWalker {
 	{
 		static const char fwd[] = "ACGT", cmp[] = "TGCA";
 		const int original = dir;
-		const uint64_t mask = (1ull << (2 * k)) - 1;
 		len = depth = 0;
 		mark = repeat = 0;
 		for (;;) {
 			++len;
 			const uint32_t kl = klink[idx];
 			const uint32_t base = dir == 1 ? (kl >> 6) & 3u : (kl >> 2) & 3u;
-			const uint32_t link = dir == 1 ? array[idx].r_link : array[idx].l_link;
+			const uint32_t link = link_at(idx, dir == 1);
 			uint32_t d = (link >> ((3u - base) * 8u)) & 0xffu;
 			depth += d;
 			if (d == 10 || d == 62) --d;
 			depths.push_back((char)d);
 			seq.push_back((original == dir) ? fwd[base] : cmp[base]);
-			const uint64_t nk = dir == 1 ? ((array[idx].kmer << 2) | base) & mask : (array[idx].kmer >> 2) + ((uint64_t)base << (2 * (k - 1)));
-			const uint64_t rc = revcomp(nk);
-			uint64_t key = nk;
-			if (!(nk < rc)) {
+			const Key128 nk = dir == 1 ? rightward(key_at(idx), base) : leftward(key_at(idx), base);
+			const Key128 rc = dbgk_wide::revcomp(nk, k);
+			Key128 key = nk;
+			if (dbgk_wide::less_equal(rc, nk)) {   // !(nk < rc), contig.cpp:802
 				key = rc;
 				dir = -dir;
 			}
@@ -254,13 +319,21 @@ extern "C" int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out)
 	const dim3 block(kContigThreads);
 	ContigScratch mem;
 	Table t;
-	t.array = c->d_array;
+	t.array = c->d_array;                // not read on a wide handle: the kernels that take a Table there read flags and link records only
 	t.nul = c->d_nul;
 	t.del = c->d_del;
 	t.klink = c->d_klink;
 	t.size = c->size;
 	t.magic = make_mod_magic(c->size);
 	t.k = c->p.k;
+	wctgk::WideTable wt;
+	wt.array = c->d_array32;
+	wt.nul = c->d_nul;
+	wt.del = c->d_del;
+	wt.klink = c->d_klink;
+	wt.size = c->size;
+	wt.magic = t.magic;
+	wt.k = c->p.k;
 
 	// the live linear nodes in slot order
 	const uint64_t n_tiles = (c->size + kScanTile - 1) / kScanTile;
@@ -302,7 +375,8 @@ extern "C" int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out)
 		return DBGK_ERR_NOMEM;
 	const dim3 pgrid(contig_grid(c, n_ports)), ngrid(contig_grid(c, n_nodes));
 	begin();
-	hipLaunchKernelGGL(k_contig_successors, pgrid, block, 0, c->stream, t, d_slot_of, d_dense_of, n_ports, d_raw, d_step, d_end);
+	if (c->wide) hipLaunchKernelGGL(wctgk::k_wctg_successors, pgrid, block, 0, c->stream, wt, d_slot_of, d_dense_of, n_ports, d_raw, d_step, d_end);
+	else hipLaunchKernelGGL(k_contig_successors, pgrid, block, 0, c->stream, t, d_slot_of, d_dense_of, n_ports, d_raw, d_step, d_end);
 	end(tm.ms_successors);
 	if (rc) return rc;
 	begin();
@@ -372,8 +446,12 @@ extern "C" int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out)
 		end(tm.ms_scatter);
 		if (rc) return rc;
 		begin();
-		hipLaunchKernelGGL(k_contig_emit, dim3(contig_grid(c, (total + 7) / 8)), block, 0, c->stream, d_stage, d_off, d_rec, c->d_array,
-		                   (uint32_t)n_kernel, total, t.k, c->d_bases, c->d_depths);
+		if (c->wide)
+			hipLaunchKernelGGL(wctgk::k_wctg_emit, dim3(contig_grid(c, (total + 7) / 8)), block, 0, c->stream, d_stage, d_off, d_rec, c->d_array32,
+			                   (uint32_t)n_kernel, total, t.k, c->d_bases, c->d_depths);
+		else
+			hipLaunchKernelGGL(k_contig_emit, dim3(contig_grid(c, (total + 7) / 8)), block, 0, c->stream, d_stage, d_off, d_rec, c->d_array,
+			                   (uint32_t)n_kernel, total, t.k, c->d_bases, c->d_depths);
 		end(tm.ms_emit);
 		if (rc) return rc;
 		tm.emit_bytes = 2 * total;
@@ -396,8 +474,7 @@ extern "C" int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out)
 	uint64_t host_nodes = 0;
 	for (uint64_t i = 0; i < n_nodes; ++i) host_nodes += host_flag[i];
 	if (host_nodes) {
-		ContigHostWalker w{c->h_array, c->h_nul, std::vector<uint8_t>(c->h_del, c->h_del + c->size / 8 + 1), c->h_klink, c->size, c->p.k};
-		static const char fwd[] = "ACGT";
+		ContigHostWalker w{c->h_array, c->h_array32, c->h_nul, std::vector<uint8_t>(c->h_del, c->h_del + c->size / 8 + 1), c->h_klink, c->size, c->p.k};
 		for (uint64_t i = 0; i < n_nodes; ++i) {
 			const uint64_t slot = slot_of[i];
 			if (!host_flag[i] || ContigHostWalker::bit(w.del.data(), slot)) continue;
@@ -414,8 +491,7 @@ extern "C" int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out)
 			uint32_t md = (uint32_t)(int)avg & 0xffu;
 			if (md == 10 || md == 62) --md;
 			r.mid_depth = (uint8_t)md;
-			std::string kmer(c->p.k, 'A');
-			for (int j = 0; j < c->p.k; ++j) kmer[j] = fwd[(c->h_array[slot].kmer >> (2 * (c->p.k - 1 - j))) & 3u];
+			const std::string kmer = w.text(slot);
 			h_rec.push_back(r);
 			h_bases.push_back(left + kmer + right);
 			h_depths.push_back(left_d + std::string(c->p.k, (char)md) + right_d);

@@ -998,7 +998,19 @@ int write_links_dump(const string &path)
 
 int write_table_image(const string &path)
 {
-	// raw image of the host KmerSet: size, count, the node array, the nul_flag bytes (layout tests)
+	// raw image of the host KmerSet: size, count, the node array, the nul_flag bytes (layout tests); of the KmerSet128, with its
+	// 32-byte nodes, after a build with -k 33..63
+	if (KmerSize > 32) {
+		if (!kset_wide) return DBGK_ERR_STATE;
+		FILE *wf = fopen(path.c_str(), "wb");
+		if (!wf) return DBGK_ERR_ARG;
+		const uint64_t whdr[2] = {kset_wide->size, kset_wide->count};
+		fwrite(whdr, 8, 2, wf);
+		fwrite(kset_wide->array, sizeof(KmerNode32), kset_wide->size, wf);
+		fwrite(kset_wide->nul_flag, 1, kset_wide->size / 8 + 1, wf);
+		fclose(wf);
+		return DBGK_OK;
+	}
 	if (!kset) return DBGK_ERR_STATE;
 	FILE *fp = fopen(path.c_str(), "wb");
 	if (!fp) return DBGK_ERR_ARG;

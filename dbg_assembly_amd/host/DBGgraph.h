@@ -67,7 +67,7 @@ extern int DbgkLastStatus;
 int write_kmer_freq_file(const string &path, int kmer_freq_cutoff);
 // canonical dump (every node sorted by k-mer) of the current kset, the parity artefact
 int write_sorted_dump(const string &path);
-// raw image (size, count, node array, nul_flag) of the current kset
+// raw image (size, count, node array, nul_flag) of the current kset; after a build with -k 33..63 of kset_wide (32-byte nodes)
 int write_table_image(const string &path);
 // DBGK_LINKS=1 in the environment: build_debruijn_graph() also runs the consumer's whole first pass, calculate_kmer_links
 // (DBG_contig/contig.cpp:107-181), on the device for the table it hands over (dbgk_export_host_table_links): kset->del_flag

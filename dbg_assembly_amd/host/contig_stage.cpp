@@ -4,6 +4,11 @@
 // (recalculate_kmer_links, DBG_contig/contig.cpp:210-277) and so changes what later list entries see.  The read-out runs on the
 // GPU through the CONTIG section of include/dbgk.h; header strings, the sort by length, ids and the -M split are done here.
 // Line numbers name DBG_contig/contig.cpp unless another file is given.
+//
+// The stage is written once over the key type (Stage<G>): Keys64 is `kset` with the reference's uint64_t k-mers, Keys128 is
+// `kset_wide` with 128-bit k-mers (k = 33..63; PARITY UNPINNED above k = 32: the reference stops at 31, the rules are those of
+// include/dbgk_wide.h and kmerSet.h's hash_code128, each of which is the 64-bit rule when the high word is 0).  Needleman-Wunsch,
+// the sort, the ids and the -M split never see a key.
 #include "contig_stage.h"
 
 #include <algorithm>
@@ -15,6 +20,8 @@
 
 #include "DBGgraph.h"
 #include "dbgk.h"
+#include "dbgk_env.h"
+#include "dbgk_wide.h"
 
 // the command line's options (defined in main.cpp)
 extern int KmerFreqCutoff, is_remove_tip, Tip_len_cutoff, is_remove_lowedge, LowCovEdge_len_cutoff, is_remove_bubble, Bubble_len_cutoff,
@@ -33,221 +40,75 @@ inline int l_num(uint64_t i) { return klink[i] & 3; }
 inline int l_base(uint64_t i) { return (klink[i] >> 2) & 3; }
 inline int r_num(uint64_t i) { return (klink[i] >> 4) & 3; }
 inline int r_base(uint64_t i) { return (klink[i] >> 6) & 3; }
-// "no such node" is slot kset->size; the reference looks at klink[kset->size] there (:810, :648), this build calls it not linear
-inline bool is_linear(uint64_t i) { return i != kset->size && (klink[i] & 0x100); }
-inline void set_flag(uint64_t i, int flag) { if (i != kset->size) klink[i] |= flag; }
-// array[kset->size].kmer, which the reference prints for an end without a node (:344, :1006): the word behind its table, 0 there
-inline uint64_t kmer_at(uint64_t i) { return i == kset->size ? 0 : kset->array[i].kmer; }
-
-inline uint64_t next_leftward(uint64_t kmer, int base) { return (kmer >> 2) + ((uint64_t)base << ((KmerSize - 1) * 2)); }   // contig.h:119-123
-inline uint64_t next_rightward(uint64_t kmer, int base) { return ((kmer << 2) | (uint64_t)base) & KmerHeadMaskVal; }        // contig.h:127-130
 
 double ms_since(const std::chrono::steady_clock::time_point &t0)
 {
 	return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// canonical form of a neighbour k-mer; flipped says that it is the reverse complement
-uint64_t canonical(uint64_t kmer, bool &flipped)
-{
-	const uint64_t rc = get_rev_com_kbit(kmer, KmerSize);
-	flipped = !(kmer < rc);
-	return flipped ? rc : kmer;
-}
-
-// calculate_kmer_links (:107-181) on the host, for a table that did not get its link records from the device
-void first_pass_host(std::vector<uint64_t> &tips, std::vector<uint64_t> &branches)
-{
-	for (uint64_t i = 0; i < kset->size; i++) {
-		if (is_entity_null(kset->nul_flag, i)) continue;
-		int num[2] = {0, 0}, base[2] = {0, 0};
-		for (int side = 0; side < 2; side++) {
-			const uint32_t link = side ? kset->array[i].r_link : kset->array[i].l_link;
-			int max_depth = 0;
-			for (int j = 0; j < 4; j++) {
-				const int depth = get_next_kmer_depth(link, j);
-				if (depth > KmerFreqCutoff) {
-					if (num[side] < 3) num[side]++;
-					if (max_depth < depth) {
-						max_depth = depth;
-						base[side] = j;
-					}
-				}
-			}
-		}
-		klink[i] = (uint16_t)(num[0] | base[0] << 2 | num[1] << 4 | base[1] << 6 | ((num[0] == 1 && num[1] == 1) ? 0x100 : 0));
-		if (num[0] == 0 && num[1] == 0) set_entity_delete(kset->del_flag, i);
-		if (num[0] + num[1] == 1) tips.push_back(i);
-		if (num[0] > 1 || num[1] > 1) branches.push_back(i);
+// the table of 16-byte nodes, 64-bit k-mers: the reference's
+struct Keys64 {
+	typedef uint64_t Key;
+	static uint64_t size() { return kset->size; }
+	static uint8_t *nul_flag() { return kset->nul_flag; }
+	static uint8_t *del_flag() { return kset->del_flag; }
+	static Key kmer(uint64_t i) { return kset->array[i].kmer; }
+	static uint32_t &l_link(uint64_t i) { return kset->array[i].l_link; }
+	static uint32_t &r_link(uint64_t i) { return kset->array[i].r_link; }
+	static uint64_t exist(Key key) { return exist_kmerset(kset, key); }
+	static Key next_leftward(Key kmer, int base) { return (kmer >> 2) + ((uint64_t)base << ((KmerSize - 1) * 2)); }   // contig.h:119-123
+	static Key next_rightward(Key kmer, int base) { return ((kmer << 2) | (uint64_t)base) & KmerHeadMaskVal; }        // contig.h:127-130
+	static Key rev_com(Key kmer) { return get_rev_com_kbit(kmer, KmerSize); }
+	static std::string text(Key kmer) { return bit2seq(kmer, KmerSize); }
+	static std::string decimal(Key kmer) { return std::to_string(kmer); }
+	static int create(const dbgk_contig_params *p, int device, dbgk_contig **h) { return dbgk_contig_create(p, device, h); }
+	static int set_table(dbgk_contig *h)
+	{
+		return dbgk_contig_set_table(h, kset->size, reinterpret_cast<const dbgk_node *>(kset->array), kset->nul_flag, kset->del_flag, klink);
 	}
-}
-
-// recalculate_kmer_links, :210-277: a link whose neighbour is gone is cleared in the node itself
-void recalculate(uint64_t idx)
-{
-	if (idx == kset->size) return;
-	KmerNode &node = kset->array[idx];
-	int num[2] = {0, 0}, base[2] = {0, 0};
-	for (int side = 0; side < 2; side++) {
-		uint32_t &link = side ? node.r_link : node.l_link;
-		int max_depth = 0;
-		for (int j = 0; j < 4; j++) {
-			const int depth = get_next_kmer_depth(link, j);
-			if (depth <= KmerFreqCutoff) continue;
-			bool flipped;
-			const uint64_t key = canonical(side ? next_rightward(node.kmer, j) : next_leftward(node.kmer, j), flipped);
-			if (exist_kmerset(kset, key) != kset->size) {
-				if (num[side] < 3) num[side]++;
-				if (max_depth < depth) {
-					max_depth = depth;
-					base[side] = j;
-				}
-			} else {
-				link &= kClearBase[j];
-			}
-		}
-	}
-	klink[idx] = (uint16_t)((klink[idx] & 0xFE00) | num[0] | base[0] << 2 | num[1] << 4 | base[1] << 6 | ((num[0] == 1 && num[1] == 1) ? 0x100 : 0));
-}
-
-struct Path {                      // what get_linear_path returns
-	int len = 0, depth = 0;
-	std::vector<uint64_t> nodes;
-	std::string str;
-	uint64_t last = 0;
-	const char *mark = "linear";
 };
 
-// get_linear_path, :779-827: from idx along the strongest link until a node that is not linear, no node, or len_cutoff steps
-void linear_path(uint64_t idx, int direct, int len_cutoff, Path &p)
-{
-	const int original = direct;
-	for (;;) {
-		p.len++;
-		p.nodes.push_back(idx);
-		const KmerNode &node = kset->array[idx];
-		uint64_t next;
-		if (direct == 1) {
-			next = next_rightward(node.kmer, r_base(idx));
-			p.depth += get_next_kmer_depth(node.r_link, r_base(idx));
-			p.str.push_back(original == 1 ? bases[r_base(idx)] : c_bases[r_base(idx)]);
-		} else {
-			next = next_leftward(node.kmer, l_base(idx));
-			p.depth += get_next_kmer_depth(node.l_link, l_base(idx));
-			p.str.push_back(original == 1 ? c_bases[l_base(idx)] : bases[l_base(idx)]);
-		}
-		bool flipped;
-		const uint64_t key = canonical(next, flipped);
-		if (flipped) direct = -direct;
-		idx = exist_kmerset(kset, key);
-		if (!is_linear(idx) || p.len >= len_cutoff) {
-			p.last = idx;
-			if (idx == kset->size) p.mark = "break";
-			else p.mark = (l_num(idx) == 0 || r_num(idx) == 0) ? "break" : "branch";
-			return;
-		}
+// the table of 32-byte nodes, 128-bit k-mers {kmer_hi, kmer_lo}
+struct Keys128 {
+	typedef unsigned __int128 Key;
+	static Key make(uint64_t hi, uint64_t lo) { return ((Key)hi << 64) | lo; }
+	static uint64_t size() { return kset_wide->size; }
+	static uint8_t *nul_flag() { return kset_wide->nul_flag; }
+	static uint8_t *del_flag() { return kset_wide->del_flag; }
+	static Key kmer(uint64_t i) { return make(kset_wide->array[i].kmer_hi, kset_wide->array[i].kmer_lo); }
+	static uint32_t &l_link(uint64_t i) { return kset_wide->array[i].l_link; }
+	static uint32_t &r_link(uint64_t i) { return kset_wide->array[i].r_link; }
+	static uint64_t exist(Key key) { return exist_kmerset128(kset_wide, (uint64_t)(key >> 64), (uint64_t)key); }
+	// the base lands at bit 2 (k - 1): in the high word from k = 33 on; two bits move down from the high word
+	static Key next_leftward(Key kmer, int base) { return (kmer >> 2) + ((Key)base << ((KmerSize - 1) * 2)); }
+	// two bits move up into the high word; 2 k <= 126 bits stay
+	static Key next_rightward(Key kmer, int base) { return ((kmer << 2) | (Key)base) & ((((Key)1) << (2 * KmerSize)) - 1); }
+	static Key rev_com(Key kmer)
+	{
+		const dbgk_wide::Key128 r = dbgk_wide::revcomp(dbgk_wide::Key128{(uint64_t)(kmer >> 64), (uint64_t)kmer}, KmerSize);
+		return make(r.hi, r.lo);
 	}
-}
-
-void delete_nodes(const std::vector<uint64_t> &nodes)
-{
-	for (uint64_t v : nodes) set_entity_delete(kset->del_flag, v);
-}
-
-// the path as it reads from left to right: k-mer of its first node in front of, or behind, the steps' bases (:335-342)
-std::string path_sequence(uint64_t first_node, int direct, std::string steps)
-{
-	const std::string kmer = bit2seq(kset->array[first_node].kmer, KmerSize);
-	if (direct == 1) return kmer + steps;
-	std::reverse(steps.begin(), steps.end());
-	return steps + kmer;
-}
-
-// remove_error_tips, :281-355
-void remove_tips(const std::vector<uint64_t> &tips)
-{
-	uint64_t total_num = 0, total_len = 0;
-	const string path = Output_prefix + ".contig.tip.fa";
-	ofstream out(path.c_str());
-	if (!out) cerr << "fail to open file " << path << endl;
-	for (uint64_t idx : tips) {
-		const int direct = (l_num(idx) == 1) ? -1 : 1;
-		Path p;
-		linear_path(idx, direct, Tip_len_cutoff, p);
-		const double avg = (double)p.depth / p.len;
-		if (!(avg <= Tip_depth_cutoff && p.len <= Tip_len_cutoff)) continue;
-		total_num++;
-		total_len += p.len;
-		delete_nodes(p.nodes);
-		recalculate(p.last);
-		set_flag(p.last, IN_TIP);
-		const uint64_t left_kmer = direct == 1 ? kset->array[idx].kmer : kmer_at(p.last), right_kmer = direct == 1 ? kmer_at(p.last) : kset->array[idx].kmer;
-		const char *left_mark = direct == 1 ? "break" : p.mark, *right_mark = direct == 1 ? p.mark : "break";
-		out << ">tip_" << total_num << "\tlength: " << p.len + KmerSize << "\tavgDepth: " << avg << "\tLeftEndKmer: " << left_kmer << " " << left_mark
-		    << "\tRightEndKmer: " << right_kmer << " " << right_mark << "\n" << path_sequence(idx, direct, p.str) << "\n";
+	static std::string text(Key kmer)
+	{
+		std::string s(KmerSize, 'A');
+		for (int j = 0; j < KmerSize; j++) s[j] = bases[(int)(kmer >> (2 * (KmerSize - 1 - j))) & 3];
+		return s;
 	}
-	out.close();
-	cerr << "\nremove total tip number:  " << total_num << endl;
-	cerr << "remove total tip length:  " << total_len << endl;
-}
-
-// get_branch_bases, :361-370
-void branch_bases(uint32_t link, std::vector<uint8_t> &vb, std::vector<uint8_t> &vd)
-{
-	for (int j = 0; j < 4; j++) {
-		const int depth = get_next_kmer_depth(link, j);
-		if (depth > KmerFreqCutoff) {
-			vb.push_back(j);
-			vd.push_back(depth);
-		}
+	static std::string decimal(Key kmer)   // with a high word of 0 the reference's text
+	{
+		if (!kmer) return "0";
+		std::string s;
+		for (; kmer; kmer /= 10) s.push_back((char)('0' + (int)(kmer % 10)));
+		std::reverse(s.begin(), s.end());
+		return s;
 	}
-}
-
-// remove_lowCov_edges, :601-776: rightward edges of a branching node first, then its leftward ones (whose header line is spelt
-// differently, :763)
-void remove_low_edges(const std::vector<uint64_t> &branches)
-{
-	int total_num = 0, total_len = 0;
-	const string path = Output_prefix + ".contig.lowedge.fa";
-	ofstream out(path.c_str());
-	if (!out) cerr << "fail to open file " << path << endl;
-	for (uint64_t idx : branches) {
-		for (int direct = 1; direct >= -1; direct -= 2) {
-			if ((direct == 1 ? r_num(idx) : l_num(idx)) < 2) continue;
-			std::vector<uint8_t> vb, vd;
-			branch_bases(direct == 1 ? kset->array[idx].r_link : kset->array[idx].l_link, vb, vd);
-			for (size_t j = 0; j < vb.size(); j++) {
-				bool flipped;
-				const uint64_t key = canonical(direct == 1 ? next_rightward(kset->array[idx].kmer, vb[j]) : next_leftward(kset->array[idx].kmer, vb[j]), flipped);
-				const int direct1 = flipped ? -direct : direct;
-				const uint64_t idx1 = exist_kmerset(kset, key);
-				if (!is_linear(idx1)) continue;
-				Path p;
-				linear_path(idx1, direct1, LowCovEdge_len_cutoff, p);
-				const int len = p.len + 1, depth = p.depth + vd[j];
-				const double avg = (double)depth / len;
-				if (!(len <= LowCovEdge_len_cutoff && avg <= LowCovEdge_depth_cutoff && !is_linear(p.last))) continue;
-				total_num++;
-				total_len += len;
-				delete_nodes(p.nodes);
-				recalculate(p.last);
-				recalculate(idx);
-				set_flag(idx, IN_LOWEDGE);
-				set_flag(p.last, IN_LOWEDGE);
-				const std::string seq = path_sequence(idx1, direct1, p.str);
-				if (direct == 1)
-					out << ">lowedge_" << total_num << "\tlength: " << len + KmerSize << "\tavgDepth: " << avg << "\tLeftEndKmer: " << kset->array[idx].kmer
-					    << " branch" << "\tRightEndKmer: " << kmer_at(p.last) << " " << p.mark << "\n" << seq << "\n";
-				else
-					out << ">lowedge_" << total_num << "    length:" << len + KmerSize << "    avgDepth:" << avg << "\tLeftEndKmer: " << kmer_at(p.last) << " "
-					    << p.mark << "\tRightEndKmer: " << kset->array[idx].kmer << " branch" << "\n" << seq << "\n";
-			}
-		}
+	static int create(const dbgk_contig_params *p, int device, dbgk_contig **h) { return dbgk_wide_contig_create(p, device, h); }
+	static int set_table(dbgk_contig *h)
+	{
+		return dbgk_wide_contig_set_table(h, kset_wide->size, reinterpret_cast<const dbgk_node32 *>(kset_wide->array), kset_wide->nul_flag,
+		                                  kset_wide->del_flag, klink);
 	}
-	cerr << "\nremove total lowCovEdge number: " << total_num << endl;
-	cerr << "remove total lowCovEdge length: " << total_len << endl;
-	out.close();
-}
+};
 
 // compare_two_seq_simple, :587-595: gap columns do not count
 int count_differences(const std::string &a, const std::string &b)
@@ -289,8 +150,226 @@ void global_align(const std::string &si, const std::string &sj, std::string &ai,
 	std::reverse(aj.begin(), aj.end());
 }
 
+// get_branch_bases, :361-370
+void branch_bases(uint32_t link, std::vector<uint8_t> &vb, std::vector<uint8_t> &vd)
+{
+	for (int j = 0; j < 4; j++) {
+		const int depth = get_next_kmer_depth(link, j);
+		if (depth > KmerFreqCutoff) {
+			vb.push_back(j);
+			vd.push_back(depth);
+		}
+	}
+}
+
+void finished(const char *word)
+{
+	time_end = clock();
+	cerr << word << " Run time: " << double(time_end - time_start) / CLOCKS_PER_SEC << endl;
+}
+
+struct Path {                      // what get_linear_path returns
+	int len = 0, depth = 0;
+	std::vector<uint64_t> nodes;
+	std::string str;
+	uint64_t last = 0;
+	const char *mark = "linear";
+};
+
+template <class G>
+struct Stage {
+typedef typename G::Key Key;
+
+// "no such node" is slot size(); the reference looks at klink[G::size()] there (:810, :648), this build calls it not linear
+static bool is_linear(uint64_t i) { return i != G::size() && (klink[i] & 0x100); }
+static void set_flag(uint64_t i, int flag) { if (i != G::size()) klink[i] |= flag; }
+// array[G::size()].kmer, which the reference prints for an end without a node (:344, :1006): the word behind its table, 0 there
+static std::string kmer_at(uint64_t i) { return G::decimal(i == G::size() ? (Key)0 : G::kmer(i)); }
+
+// canonical form of a neighbour k-mer; flipped says that it is the reverse complement
+static Key canonical(Key kmer, bool &flipped)
+{
+	const Key rc = G::rev_com(kmer);
+	flipped = !(kmer < rc);
+	return flipped ? rc : kmer;
+}
+
+// calculate_kmer_links (:107-181) on the host, for a table that did not get its link records from the device
+static void first_pass_host(std::vector<uint64_t> &tips, std::vector<uint64_t> &branches)
+{
+	for (uint64_t i = 0; i < G::size(); i++) {
+		if (is_entity_null(G::nul_flag(), i)) continue;
+		int num[2] = {0, 0}, base[2] = {0, 0};
+		for (int side = 0; side < 2; side++) {
+			const uint32_t link = side ? G::r_link(i) : G::l_link(i);
+			int max_depth = 0;
+			for (int j = 0; j < 4; j++) {
+				const int depth = get_next_kmer_depth(link, j);
+				if (depth > KmerFreqCutoff) {
+					if (num[side] < 3) num[side]++;
+					if (max_depth < depth) {
+						max_depth = depth;
+						base[side] = j;
+					}
+				}
+			}
+		}
+		klink[i] = (uint16_t)(num[0] | base[0] << 2 | num[1] << 4 | base[1] << 6 | ((num[0] == 1 && num[1] == 1) ? 0x100 : 0));
+		if (num[0] == 0 && num[1] == 0) set_entity_delete(G::del_flag(), i);
+		if (num[0] + num[1] == 1) tips.push_back(i);
+		if (num[0] > 1 || num[1] > 1) branches.push_back(i);
+	}
+}
+
+// recalculate_kmer_links, :210-277: a link whose neighbour is gone is cleared in the node itself
+static void recalculate(uint64_t idx)
+{
+	if (idx == G::size()) return;
+	const Key kmer = G::kmer(idx);
+	int num[2] = {0, 0}, base[2] = {0, 0};
+	for (int side = 0; side < 2; side++) {
+		uint32_t &link = side ? G::r_link(idx) : G::l_link(idx);
+		int max_depth = 0;
+		for (int j = 0; j < 4; j++) {
+			const int depth = get_next_kmer_depth(link, j);
+			if (depth <= KmerFreqCutoff) continue;
+			bool flipped;
+			const Key key = canonical(side ? G::next_rightward(kmer, j) : G::next_leftward(kmer, j), flipped);
+			if (G::exist(key) != G::size()) {
+				if (num[side] < 3) num[side]++;
+				if (max_depth < depth) {
+					max_depth = depth;
+					base[side] = j;
+				}
+			} else {
+				link &= kClearBase[j];
+			}
+		}
+	}
+	klink[idx] = (uint16_t)((klink[idx] & 0xFE00) | num[0] | base[0] << 2 | num[1] << 4 | base[1] << 6 | ((num[0] == 1 && num[1] == 1) ? 0x100 : 0));
+}
+
+// get_linear_path, :779-827: from idx along the strongest link until a node that is not linear, no node, or len_cutoff steps
+static void linear_path(uint64_t idx, int direct, int len_cutoff, Path &p)
+{
+	const int original = direct;
+	for (;;) {
+		p.len++;
+		p.nodes.push_back(idx);
+		const Key kmer = G::kmer(idx);
+		Key next;
+		if (direct == 1) {
+			next = G::next_rightward(kmer, r_base(idx));
+			p.depth += get_next_kmer_depth(G::r_link(idx), r_base(idx));
+			p.str.push_back(original == 1 ? bases[r_base(idx)] : c_bases[r_base(idx)]);
+		} else {
+			next = G::next_leftward(kmer, l_base(idx));
+			p.depth += get_next_kmer_depth(G::l_link(idx), l_base(idx));
+			p.str.push_back(original == 1 ? c_bases[l_base(idx)] : bases[l_base(idx)]);
+		}
+		bool flipped;
+		const Key key = canonical(next, flipped);
+		if (flipped) direct = -direct;
+		idx = G::exist(key);
+		if (!is_linear(idx) || p.len >= len_cutoff) {
+			p.last = idx;
+			if (idx == G::size()) p.mark = "break";
+			else p.mark = (l_num(idx) == 0 || r_num(idx) == 0) ? "break" : "branch";
+			return;
+		}
+	}
+}
+
+static void delete_nodes(const std::vector<uint64_t> &nodes)
+{
+	for (uint64_t v : nodes) set_entity_delete(G::del_flag(), v);
+}
+
+// the path as it reads from left to right: k-mer of its first node in front of, or behind, the steps' bases (:335-342)
+static std::string path_sequence(uint64_t first_node, int direct, std::string steps)
+{
+	const std::string kmer = G::text(G::kmer(first_node));
+	if (direct == 1) return kmer + steps;
+	std::reverse(steps.begin(), steps.end());
+	return steps + kmer;
+}
+
+// remove_error_tips, :281-355
+static void remove_tips(const std::vector<uint64_t> &tips)
+{
+	uint64_t total_num = 0, total_len = 0;
+	const string path = Output_prefix + ".contig.tip.fa";
+	ofstream out(path.c_str());
+	if (!out) cerr << "fail to open file " << path << endl;
+	for (uint64_t idx : tips) {
+		const int direct = (l_num(idx) == 1) ? -1 : 1;
+		Path p;
+		linear_path(idx, direct, Tip_len_cutoff, p);
+		const double avg = (double)p.depth / p.len;
+		if (!(avg <= Tip_depth_cutoff && p.len <= Tip_len_cutoff)) continue;
+		total_num++;
+		total_len += p.len;
+		delete_nodes(p.nodes);
+		recalculate(p.last);
+		set_flag(p.last, IN_TIP);
+		const std::string left_kmer = direct == 1 ? G::decimal(G::kmer(idx)) : kmer_at(p.last), right_kmer = direct == 1 ? kmer_at(p.last) : G::decimal(G::kmer(idx));
+		const char *left_mark = direct == 1 ? "break" : p.mark, *right_mark = direct == 1 ? p.mark : "break";
+		out << ">tip_" << total_num << "\tlength: " << p.len + KmerSize << "\tavgDepth: " << avg << "\tLeftEndKmer: " << left_kmer << " " << left_mark
+		    << "\tRightEndKmer: " << right_kmer << " " << right_mark << "\n" << path_sequence(idx, direct, p.str) << "\n";
+	}
+	out.close();
+	cerr << "\nremove total tip number:  " << total_num << endl;
+	cerr << "remove total tip length:  " << total_len << endl;
+}
+
+// remove_lowCov_edges, :601-776: rightward edges of a branching node first, then its leftward ones (whose header line is spelt
+// differently, :763)
+static void remove_low_edges(const std::vector<uint64_t> &branches)
+{
+	int total_num = 0, total_len = 0;
+	const string path = Output_prefix + ".contig.lowedge.fa";
+	ofstream out(path.c_str());
+	if (!out) cerr << "fail to open file " << path << endl;
+	for (uint64_t idx : branches) {
+		for (int direct = 1; direct >= -1; direct -= 2) {
+			if ((direct == 1 ? r_num(idx) : l_num(idx)) < 2) continue;
+			std::vector<uint8_t> vb, vd;
+			branch_bases(direct == 1 ? G::r_link(idx) : G::l_link(idx), vb, vd);
+			for (size_t j = 0; j < vb.size(); j++) {
+				bool flipped;
+				const Key key = canonical(direct == 1 ? G::next_rightward(G::kmer(idx), vb[j]) : G::next_leftward(G::kmer(idx), vb[j]), flipped);
+				const int direct1 = flipped ? -direct : direct;
+				const uint64_t idx1 = G::exist(key);
+				if (!is_linear(idx1)) continue;
+				Path p;
+				linear_path(idx1, direct1, LowCovEdge_len_cutoff, p);
+				const int len = p.len + 1, depth = p.depth + vd[j];
+				const double avg = (double)depth / len;
+				if (!(len <= LowCovEdge_len_cutoff && avg <= LowCovEdge_depth_cutoff && !is_linear(p.last))) continue;
+				total_num++;
+				total_len += len;
+				delete_nodes(p.nodes);
+				recalculate(p.last);
+				recalculate(idx);
+				set_flag(idx, IN_LOWEDGE);
+				set_flag(p.last, IN_LOWEDGE);
+				const std::string seq = path_sequence(idx1, direct1, p.str);
+				if (direct == 1)
+					out << ">lowedge_" << total_num << "\tlength: " << len + KmerSize << "\tavgDepth: " << avg << "\tLeftEndKmer: " << G::decimal(G::kmer(idx))
+					    << " branch" << "\tRightEndKmer: " << kmer_at(p.last) << " " << p.mark << "\n" << seq << "\n";
+				else
+					out << ">lowedge_" << total_num << "    length:" << len + KmerSize << "    avgDepth:" << avg << "\tLeftEndKmer: " << kmer_at(p.last) << " "
+					    << p.mark << "\tRightEndKmer: " << G::decimal(G::kmer(idx)) << " branch" << "\n" << seq << "\n";
+			}
+		}
+	}
+	cerr << "\nremove total lowCovEdge number: " << total_num << endl;
+	cerr << "remove total lowCovEdge length: " << total_len << endl;
+	out.close();
+}
+
 // remove_hetero_bubbles, :375-582
-void remove_bubbles(const std::vector<uint64_t> &branches)
+static void remove_bubbles(const std::vector<uint64_t> &branches)
 {
 	const string path = Output_prefix + ".contig.bubble.fa";
 	ofstream out(path.c_str());
@@ -301,10 +380,10 @@ void remove_bubbles(const std::vector<uint64_t> &branches)
 		std::vector<uint8_t> vb, vd;
 		if (l_num(idx) == 2 && r_num(idx) == 1) {
 			direct = -1;
-			branch_bases(kset->array[idx].l_link, vb, vd);
+			branch_bases(G::l_link(idx), vb, vd);
 		} else if (l_num(idx) == 1 && r_num(idx) == 2) {
 			direct = 1;
-			branch_bases(kset->array[idx].r_link, vb, vd);
+			branch_bases(G::r_link(idx), vb, vd);
 		} else {
 			continue;
 		}
@@ -312,9 +391,9 @@ void remove_bubbles(const std::vector<uint64_t> &branches)
 		int dir[2];
 		for (int e = 0; e < 2; e++) {
 			bool flipped;
-			const uint64_t key = canonical(direct == 1 ? next_rightward(kset->array[idx].kmer, vb[e]) : next_leftward(kset->array[idx].kmer, vb[e]), flipped);
+			const Key key = canonical(direct == 1 ? G::next_rightward(G::kmer(idx), vb[e]) : G::next_leftward(G::kmer(idx), vb[e]), flipped);
 			dir[e] = flipped ? -direct : direct;
-			first[e] = exist_kmerset(kset, key);
+			first[e] = G::exist(key);
 		}
 		if (!is_linear(first[0]) || !is_linear(first[1])) continue;
 		Path p[2];
@@ -354,7 +433,7 @@ void remove_bubbles(const std::vector<uint64_t> &branches)
 		recalculate(idx);
 		total_num++;
 		total_len += removed == 1 ? len1 : len2;
-		const uint64_t left_kmer = direct == 1 ? kset->array[idx].kmer : kmer_at(p[0].last), right_kmer = direct == 1 ? kmer_at(p[0].last) : kset->array[idx].kmer;
+		const std::string left_kmer = direct == 1 ? G::decimal(G::kmer(idx)) : kmer_at(p[0].last), right_kmer = direct == 1 ? kmer_at(p[0].last) : G::decimal(G::kmer(idx));
 		const char *left_mark = direct == 1 ? "branch" : p[0].mark, *right_mark = direct == 1 ? p[0].mark : "branch";
 		out << ">bubble_" << total_num << "\ttype: " << type << "\tlength1: " << len1 + KmerSize << "\tavgDepth1: " << avg1 << "\tlength2: " << len2 + KmerSize
 		    << "\tavgDepth2: " << avg2 << "\tremoved: " << removed << "\tLeftEndKmer: " << left_kmer << " " << left_mark << "\tRightEndKmer: " << right_kmer
@@ -368,7 +447,7 @@ void remove_bubbles(const std::vector<uint64_t> &branches)
 }
 
 // read_out_contig, :900-1046: the contigs come from the GPU in the order of the reference's scan
-int read_out(double &ms_gpu, double &ms_files)
+static int read_out(double &ms_gpu, double &ms_files)
 {
 	const string seq_path = Output_prefix + ".contig.seq.fa", depth_path = Output_prefix + ".contig.seq.depth";
 	ofstream seq_out(seq_path.c_str()), depth_out(depth_path.c_str());
@@ -382,8 +461,8 @@ int read_out(double &ms_gpu, double &ms_files)
 	dbgk_contig_params prm = {KmerSize, KmerFreqCutoff < 0 ? 0 : KmerFreqCutoff, Contig_len_cutoff, 0};
 	const char *dev = getenv("DBGK_DEVICE");
 	dbgk_contig_summary sum;
-	int rc = dbgk_contig_create(&prm, dev ? atoi(dev) : 0, &h);
-	if (!rc) rc = dbgk_contig_set_table(h, kset->size, reinterpret_cast<const dbgk_node *>(kset->array), kset->nul_flag, kset->del_flag, klink);
+	int rc = G::create(&prm, dev ? atoi(dev) : 0, &h);
+	if (!rc) rc = G::set_table(h);
 	if (!rc) rc = dbgk_contig_read_out(h, &sum);
 	if (rc) {
 		cerr << "contig read-out on the GPU failed: " << dbgk_strerror(rc) << " " << dbgk_last_error() << endl;
@@ -418,8 +497,8 @@ int read_out(double &ms_gpu, double &ms_files)
 		(r.left_mark ? branch_points : break_points)++;
 		char num[64];
 		snprintf(num, sizeof num, "%.17g", avg);       // boost::lexical_cast<string>(double), :1006
-		header[i] = "\tlength: " + std::to_string(contig_len) + "\tavgDepth: " + num + "\tLeftEndKmer: " + std::to_string(kmer_at(r.left_end)) + " " +
-		            kMark[r.left_mark] + "-" + kRepeat[r.left_repeat] + "\tRightEndKmer: " + std::to_string(kmer_at(r.right_end)) + " " + kMark[r.right_mark] +
+		header[i] = "\tlength: " + std::to_string(contig_len) + "\tavgDepth: " + num + "\tLeftEndKmer: " + kmer_at(r.left_end) + " " +
+		            kMark[r.left_mark] + "-" + kRepeat[r.left_repeat] + "\tRightEndKmer: " + kmer_at(r.right_end) + " " + kMark[r.right_mark] +
 		            "-" + kRepeat[r.right_repeat] + "\t" + ((r.left_repeat == 2 && r.right_repeat == 2) ? "RepeatNode" : "") + "\n";
 		order[i] = std::make_pair(off[i + 1] - off[i], i);
 	}
@@ -451,19 +530,12 @@ int read_out(double &ms_gpu, double &ms_files)
 	return 0;
 }
 
-void finished(const char *word)
-{
-	time_end = clock();
-	cerr << word << " Run time: " << double(time_end - time_start) / CLOCKS_PER_SEC << endl;
-}
-
-} // namespace
-
 // build_contig_sequence, :54-102
-int run_contig_stage()
+static int run()
 {
 	double ms_first = 0, ms_tip = 0, ms_edge = 0, ms_bubble = 0, ms_gpu = 0, ms_files = 0;
 	cerr << "\nStart to calulate kmer links information!" << endl;
+	if (sizeof(Key) > 8) cerr << "Contig stage on 128-bit k-mers (32-byte nodes; parity unpinned above k = 32)" << endl;
 	auto t0 = std::chrono::steady_clock::now();
 	std::vector<uint64_t> tips, branches;
 	if (DbgkKmerLinks) {             // the first pass came with the table, computed on the device (dbgk_export_host_table_links)
@@ -472,7 +544,7 @@ int run_contig_stage()
 		branches.swap(DbgkBranchNodes);
 	} else {                         // a table laid out on the host (DBGK_LAYOUT=ref): its slots are not the device table's, so the same pass here.
 		                                 // The records live until the program leaves (main.cpp leaves through _exit): never freed
-		klink = static_cast<uint16_t *>(calloc(kset->size, sizeof(uint16_t)));
+		klink = static_cast<uint16_t *>(calloc(G::size(), sizeof(uint16_t)));
 		if (!klink) return DBGK_ERR_NOMEM;
 		first_pass_host(tips, branches);
 	}
@@ -509,4 +581,35 @@ int run_contig_stage()
 		cerr << "Contig stage host passes (ms): first pass " << ms_first << " tips " << ms_tip << " low edges " << ms_edge << " bubbles " << ms_bubble
 		     << " read-out " << ms_gpu << " headers, sort and files " << ms_files << endl;
 	return 0;
+}
+};   // Stage
+
+} // namespace
+
+int run_contig_stage() { return Stage<Keys64>::run(); }
+
+int run_contig_stage_wide() { return Stage<Keys128>::run(); }
+
+// test hook contig_wide: `kset` carried over to 32-byte nodes with a high word of 0 -- the same slots, flags and link words
+// (hash_code128(0, lo) == hash_code(lo), so every key sits where a 128-bit probe looks for it) -- and the wide stage on that
+int run_contig_stage_wide_on_kset()
+{
+	const uint64_t size = kset->size, flag_bytes = size / 8 + 1;
+	KmerNode32 *array = static_cast<KmerNode32 *>(kmerset_alloc(size * sizeof(KmerNode32), true));
+	uint8_t *nul = static_cast<uint8_t *>(kmerset_alloc(flag_bytes, false)), *del = static_cast<uint8_t *>(kmerset_alloc(flag_bytes, false));
+	if (!array || !nul || !del) {
+		free(array), free(nul), free(del);
+		return DBGK_ERR_NOMEM;
+	}
+	for (uint64_t i = 0; i < size; i++) {
+		array[i].kmer_lo = kset->array[i].kmer;
+		array[i].l_link = kset->array[i].l_link;
+		array[i].r_link = kset->array[i].r_link;
+	}
+	memcpy(nul, kset->nul_flag, flag_bytes);
+	memcpy(del, kset->del_flag, flag_bytes);
+	if (kset_wide) free_hash128(kset_wide);
+	kset_wide = adopt_kmerset128(size, kset->load_factor, kset->count, kset->count_conflict, array, nul, del);
+	if (!kset_wide) return DBGK_ERR_NOMEM;
+	return run_contig_stage_wide();
 }

@@ -2,12 +2,13 @@
 //
 // Same options, defaults and positional argument as the reference's DBG_contig/main.cpp:97-124,
 // 166-193 (getopt string "k:r:f:o:t:i:l:e:b:D:T:I:P:W:C:G:B:U:L:E:M:h"); the help wording is this build's own.  The graph stage
-// (build_debruijn_graph) runs on the GPU.  The contig stage (DBG_contig/contig.cpp) is this build's own for k <= 31
-// (contig_stage.cpp): tip, low-coverage-edge and bubble removal on the host in the reference's order, the contig read-out on the
-// GPU, the reference's eight <prefix>.contig.* files.  When this program is linked together with the reference's contig.cpp
-// instead its build_contig_sequence() is called exactly as in the reference.  For k = 32 and above the
-// program stops after the graph stage, as it does for a hash array of 2^32 - 1 entries or more, and writes the artefacts that stage defines: <prefix>.contig.kmer.freq (first pass of
-// calculate_kmer_links) and, if DBGK_DUMP is set, the canonical node dump.
+// (build_debruijn_graph) runs on the GPU.  The contig stage (DBG_contig/contig.cpp) is this build's own for k <= 31 and for
+// k = 33..63 (contig_stage.cpp): tip, low-coverage-edge and bubble removal on the host in the reference's order, the contig
+// read-out on the GPU, the reference's eight <prefix>.contig.* files.  Above k = 32 the stage works on 128-bit k-mers (kset_wide);
+// the reference stops at 31, so parity is unpinned there.  When this program is linked together with the reference's contig.cpp
+// instead its build_contig_sequence() is called exactly as in the reference for k <= 31.  For k = 32 the
+// program stops after the graph stage, as it does for a hash array of 2^32 - 1 entries or more, and writes the artefacts that stage
+// defines: <prefix>.contig.kmer.freq (first pass of calculate_kmer_links) and, if DBGK_DUMP is set, the canonical node dump.
 #include <unistd.h>
 #include <chrono>
 #include <cstdio>
@@ -38,7 +39,7 @@ void build_contig_sequence() __attribute__((weak));  // DBG_contig/contig.h:67, 
 static void print_options(ostream &os, bool with_k_max)
 {
 	// option letters, argument kinds, defaults and order follow the reference (DBG_contig/main.cpp:97-124); the wording is ours
-	os << "   -k <int>    k-mer length" << (with_k_max ? " (contigs are built for k up to 31; the graph stage alone goes up to 63, 128-bit keys)" : "") << " [" << KmerSize << "]" << endl
+	os << "   -k <int>    k-mer length" << (with_k_max ? " (contigs are built for k <= 31 and for k = 33..63, the latter on 128-bit keys; k = 32: graph stage only)" : "") << " [" << KmerSize << "]" << endl
 	   << "   -r <int>    longest read length used; longer reads are cut to this [" << maxReadLen << "]" << endl
 	   << "   -f <int>    input format: 1 = FASTQ, 2 = FASTA, one sequence per line, plain or .gz [" << Input_file_format << "]" << endl
 	   << "   -o <str>    prefix of the output files [" << Output_prefix << "]" << endl
@@ -151,16 +152,22 @@ int main(int argc, char *argv[])
 	if (const char *img = getenv("DBGK_DUMP_TABLE")) write_table_image(img);
 	if (const char *lk = getenv("DBGK_DUMP_LINKS")) write_links_dump(lk);
 
-	if (KmerSize > 32) { // the reference's consumer is written for 64-bit k-mers (uint64_t kmer, DBG_contig/kmerSet.h:71)
+	if (KmerSize > 32 && kset_wide && kset_wide->size < 0xffffffffull) { // this build's own stage on 128-bit k-mers (parity unpinned above k = 32)
+		if (run_contig_stage_wide() != 0) leave(1);
+		cerr << "\nRemove tips, merge bubbles, output contig sequence finished !" << endl;
+		cerr << "\nAssembly completely finished!" << endl;
+	} else if (KmerSize > 32) { // the reference's consumer is written for 64-bit k-mers (uint64_t kmer, DBG_contig/kmerSet.h:71)
 		cerr << "\nStart to calulate kmer links information!" << endl;
 		write_kmer_freq_file(Output_prefix + ".contig.kmer.freq", KmerFreqCutoff);
-		cerr << "\nGraph stage finished: k = " << KmerSize << " graph in kset_wide (32-byte nodes); the contig stage handles k <= 31 only" << endl;
+		if (kset_wide) cerr << "\nThe hash array has " << kset_wide->size << " entries; this build's contig stage takes fewer than 4294967295" << endl;
+		cerr << "\nGraph stage finished: k = " << KmerSize << " graph in kset_wide (32-byte nodes)" << endl;
 	} else if (build_contig_sequence) {
 		build_contig_sequence();
 		cerr << "\nRemove tips, merge bubbles, output contig sequence finished !" << endl;
 		cerr << "\nAssembly completely finished!" << endl;
 	} else if (own_contig_stage && kset->size < 0xffffffffull) { // the read-out numbers slots with 32 bits (include/dbgk.h, CONTIG section)
-		if (run_contig_stage() != 0) leave(1);
+		// test hook contig_wide: the stage on 128-bit k-mers, on this table with a high word of 0
+		if ((dbgk_hook("contig_wide") ? run_contig_stage_wide_on_kset() : run_contig_stage()) != 0) leave(1);
 		cerr << "\nRemove tips, merge bubbles, output contig sequence finished !" << endl;
 		cerr << "\nAssembly completely finished!" << endl;
 	} else { // k = 32: the reference's consumer stops at 31 (DBG_contig/main.cpp:100), and so does this build's; a table of 2^32 - 1 slots or more

@@ -1036,7 +1036,7 @@ int dbgk_super_batch_stats(dbgk_super *s, dbgk_super_timing *out);
 typedef struct dbgk_contig dbgk_contig;
 
 typedef struct dbgk_contig_params {
-	int32_t k;                  /* 1 .. 31                                                                                */
+	int32_t k;                  /* 1 .. 31; 1 .. 63 for dbgk_wide_contig_create                                           */
 	int32_t kmer_freq_cutoff;   /* -D, as the klink records were computed with; kept for the record, the read-out reads klink */
 	int32_t contig_len_cutoff;  /* -M; kept for the record: the split into contigs and small ones is the caller's         */
 	int32_t reserved;           /* 0                                                                                      */
@@ -1096,6 +1096,20 @@ int dbgk_contig_summary_get(dbgk_contig *c, dbgk_contig_summary *out);
  * bases and of depths), records (summary.contigs), bases and depths (summary.bytes each).  Any may be NULL.                   */
 int dbgk_contig_results(dbgk_contig *c, uint64_t *offsets, dbgk_contig_record *records, char *bases, char *depths);
 int dbgk_contig_timing_get(dbgk_contig *c, dbgk_contig_timing *out);
+
+/* ---- CONTIG on 128-bit keys (additions to ABI 7; this build only: PARITY UNPINNED above k = 32) -------------------------------------
+ * The same read-out for a table of dbgk_node32 (include/dbgk_wide.h), k = 1 .. 63.  The reference stops at k = 31, so nothing pins
+ * the bytes above k = 32; the rules are those of dbgk_wide.h (revcomp, 128-bit comparison, hash_code(lo ^ hash_code(hi)) for a high
+ * word that is not 0, linear probing with wrap), every one of which is the reference's 64-bit rule when the high word is 0: a wide
+ * handle at k <= 31 on a table of {0, kmer} nodes returns what a handle of dbgk_contig_create returns for the 16-byte table.
+ * dbgk_contig_read_out, _results, _summary_get, _timing_get and _destroy serve both kinds of handle; slots stay 32-bit, so records,
+ * summary and timing are the same structs.  k outside 1 .. 63 is DBGK_ERR_ARG before any device work; DBGK_ERR_HIP without a usable
+ * gfx950 device: no host fall-back.                                                                                              */
+int dbgk_wide_contig_create(const dbgk_contig_params *p, int device, dbgk_contig **out);
+/* as dbgk_contig_set_table, 32-byte nodes; the same flag and link-record layouts, 2 <= size < 2^32 - 1.  On a handle of
+ * dbgk_contig_create this is DBGK_ERR_STATE, as dbgk_contig_set_table is on a handle of dbgk_wide_contig_create.                  */
+int dbgk_wide_contig_set_table(dbgk_contig *c, uint64_t size, const dbgk_node32 *array, const uint8_t *nul_flag, const uint8_t *del_flag,
+                               const uint16_t *klink);
 
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
