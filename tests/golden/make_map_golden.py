@@ -11,9 +11,15 @@ fall off the end of non-void functions, as in oracle/Makefile):
     g++ -O2 -w -o map_reads kmerSet.o map_func.cpp seqKmer.cpp gzstream.cpp map_reads.cpp -lz -lpthread
     g++ -O2 -w -o map_pair  kmerSet.o map_func.cpp seqKmer.cpp gzstream.cpp map_pair.cpp  -lz -lpthread
 
-    python tests/golden/make_map_golden.py /path/to/map_reads /path/to/map_pair
+    python tests/golden/make_map_golden.py /path/to/map_reads /path/to/map_pair [cases | edges]
 
-Every category the tests rely on is asserted here to be present in the reference's output (map_restatement.coverage)."""
+Every category the tests rely on is asserted here to be present in the reference's output (map_restatement.coverage).
+
+tests/golden/map_edge_cases/ is a second set (written with `edges`, or with both when no third argument is given): the crafted
+scenarios of tests/map_edge_cases.py at (k, s) = (31, 5), (21, 5), (15, 40) and (31, 1), without bytes from 128 on.  Per (k, s)
+one contig file; per scenario the reads as gzipped FASTA and two library files (the one of map_pair names the reads file twice:
+every read is its own mate), and two cases, <scenario>__reads and <scenario>__pair.  What the reference wrote for a case is
+kept as one file, <case>.out.json.gz: {output file name: text}, in the form map_restatement.expected_outputs gives."""
 import gzip
 import json
 import os
@@ -148,8 +154,37 @@ def run_reference(exe, D, case):
     shutil.rmtree(tmp)
 
 
+def main_edges(exe):
+    import map_edge_cases as E
+    D = os.path.join(HERE, "map_edge_cases")
+    shutil.rmtree(D, ignore_errors=True)
+    os.makedirs(D)
+    cases = []
+    for scn in E.golden_scenarios():
+        ctg = "contigs_k%ds%d.fa" % (scn.k, scn.s)
+        text = "".join(">c%d\n%s\n" % (n, q.decode()) for n, q in enumerate(scn.contigs))
+        assert not os.path.exists(os.path.join(D, ctg)) or open(os.path.join(D, ctg)).read() == text
+        open(os.path.join(D, ctg), "w").write(text)
+        write_reads(os.path.join(D, scn.name + ".fa.gz"), [("r%d" % n, q.decode()) for n, q in enumerate(scn.reads)], 2)
+        open(os.path.join(D, scn.name + ".lib"), "w").write(scn.name + ".fa.gz\n")
+        open(os.path.join(D, scn.name + ".pe.lib"), "w").write("%s.fa.gz\n%s.fa.gz\n" % (scn.name, scn.name))
+        args = ["-k", str(scn.k), "-s", str(scn.s), "-r", str(scn.r), "-i", repr(scn.identity), "-f", "2", "-l", "100"]
+        cases.append(dict(name=scn.name + "__reads", scenario=scn.name, program="map_reads", args=args, contigs=ctg, lib=scn.name + ".lib"))
+        cases.append(dict(name=scn.name + "__pair", scenario=scn.name, program="map_pair", args=args, contigs=ctg, lib=scn.name + ".pe.lib"))
+    open(os.path.join(D, "cases.json"), "w").write("[\n" + ",\n".join(" " + json.dumps(c) for c in cases) + "\n]\n")
+    for case in cases:
+        run_reference(exe[case["program"]], D, case)
+        write_gz(os.path.join(D, case["name"] + ".out.json.gz"), json.dumps(MR.expected_outputs(D, case), sort_keys=True).encode())
+        shutil.rmtree(os.path.join(D, case["name"]))
+
+
 def main():
     exe = {"map_reads": os.path.abspath(sys.argv[1]), "map_pair": os.path.abspath(sys.argv[2])}
+    which = sys.argv[3] if len(sys.argv) > 3 else "both"
+    if which in ("edges", "both"):
+        main_edges(exe)
+    if which == "edges":
+        return
     for prog, name in (("map_reads", "map_usage_reads.txt"), ("map_pair", "map_usage_pair.txt")):
         open(os.path.join(HERE, name), "wb").write(subprocess.run([exe[prog]], capture_output=True, timeout=60).stdout)
     rng = np.random.default_rng(11)

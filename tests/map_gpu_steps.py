@@ -1,5 +1,5 @@
 """GPU steps of tests/test_map_gpu.py, each run in a child process of its own under a time limit:
-    python tests/map_gpu_steps.py capi_goldens | large
+    python tests/map_gpu_steps.py capi_goldens | large | edges
 Prints one JSON line of findings; exits non-zero on a mismatch."""
 import json
 import os
@@ -85,5 +85,60 @@ def large():
             "windows_per_read": st["windows_probed"] / n_reads, "ms_map": st["ms_map"]}
 
 
+def edges():
+    """the crafted scenarios of tests/map_edge_cases.py at the first chunks 1, 4 and 64 of the seed scan: all eight fields of
+    both hits equal the restatement's, the counters equal the census of lengths; one batch wide enough for the grid-stride
+    loop; the reference-written goldens of the scenarios through capi.Mapper"""
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count   # torch's HIP runtime first, as tests/conftest.py has it
+    from dbg_assembly_amd import capi
+    import map_edge_cases as E
+    from test_map_edges_cpu import EDGE_CASES, edge_expected, edge_golden_cases
+    cats, stats = {}, {"by_lds": 0, "by_long": 0, "skipped": 0}
+
+    def run(m, scn, idx, want):
+        reads = [scn.reads[n] for n in idx]
+        got = to_hits(m.map_sequences(reads))
+        st = m.batch_stats()
+        assert {key: st[key] for key in stats} == E.census(scn, reads), (scn.name, st)
+        for n, g, w in zip(idx, got, want):
+            assert g == w, (scn.name, n, scn.expect[n], g, w)
+        for key in stats:
+            stats[key] += st[key]
+        return got
+
+    for scn in E.scenarios():
+        X, hits = E.restated(scn.name)
+        with capi.Mapper(k=scn.k, s=scn.s, r=scn.r, identity=scn.identity, second_alignment=scn.second) as m:
+            m.set_contigs(scn.contigs)
+            per_ramp = []
+            for ramp in E.RAMPS:
+                m.set_ramp(ramp)
+                per_ramp.append([run(m, scn, idx, [hits[n] for n in idx]) for idx in E.batches(scn)])
+            assert per_ramp[0] == per_ramp[1] == per_ramp[2], (scn.name, "hits depend on the ramp of the seed scan")
+        for e in scn.expect:
+            cats[e["cat"]] = cats.get(e["cat"], 0) + len(E.RAMPS)
+    # a partly filled last workgroup behind a full grid of 32 workgroups per CU, four reads each
+    scn, idx = E.grid_reads(4 * 32 * n_cu + 5)
+    X, hits = E.restated(scn.name)
+    with capi.Mapper(k=scn.k, s=scn.s, r=scn.r, identity=scn.identity, second_alignment=scn.second) as m:
+        m.set_contigs(scn.contigs)
+        run(m, scn, idx, [hits[n] for n in idx])
+    cats["grid"] = len(idx)
+    golden = 0
+    for case in edge_golden_cases():
+        def mapper(X, reads, P, second):
+            with capi.Mapper(k=P.k, s=P.s, r=P.r, identity=P.i, second_alignment=second) as m:
+                m.set_contigs(X.contigs)
+                return to_hits(m.map_sequences(reads))
+
+        got, want = MR.run_case(EDGE_CASES, case, mapper), edge_expected(case)
+        assert sorted(got) == sorted(want)
+        for f in want:
+            assert got[f] == want[f], (case["name"], f)
+        golden += 1
+    return dict(categories=cats, ramps=list(E.RAMPS), golden_cases=golden, n_cu=n_cu, **stats)
+
+
 if __name__ == "__main__":
-    print(json.dumps({"capi_goldens": capi_goldens, "large": large}[sys.argv[1]]()))
+    print(json.dumps({"capi_goldens": capi_goldens, "large": large, "edges": edges}[sys.argv[1]]()))
