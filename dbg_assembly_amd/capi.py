@@ -215,6 +215,22 @@ class ContigTiming(C.Structure):
                                           "ms_emit", "ms_host_walk")]
 
 
+TRACE_REQUEST_DTYPE = np.dtype([("slot", "<u8"), ("direct", "<i4"), ("reserved", "<i4")])  # dbgk_trace_request
+TRACE_ROW_DTYPE = np.dtype([("start", "<u4"), ("last", "<u4"), ("len", "<u4"), ("depth", "<u4"), ("direct", "i1"), ("mark", "u1"),
+                            ("status", "u1"), ("pad", "u1"), ("reserved", "<u4")])  # dbgk_trace_row
+TRACE_TRACED, TRACE_BELOW_CUTOFF, TRACE_ABSENT, TRACE_NOT_LINEAR = 0, 1, 2, 3
+TRACE_MAX_CUTOFF = 65536
+
+
+class TraceSummary(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("rows", "traced", "nodes", "batches")]
+
+
+class SimplifyTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("bytes_returned", "batches", "updated_slots", "reserved")] + \
+               [(f, C.c_double) for f in ("ms_trace", "ms_branches", "ms_fill", "ms_update")]
+
+
 class DbgkError(RuntimeError):
     def __init__(self, status, what):
         self.status = status
@@ -388,6 +404,11 @@ SYMBOLS = [
     ("dbgk_contig_timing_get", _i, [_vp, C.POINTER(ContigTiming)]),
     ("dbgk_wide_contig_create", _i, [C.POINTER(ContigParams), _i, C.POINTER(_vp)]),
     ("dbgk_wide_contig_set_table", _i, [_vp, _u64, _vp, _vp, _vp, _vp]),
+    ("dbgk_simplify_trace", _i, [_vp, _vp, _u64, C.c_int32, C.POINTER(TraceSummary)]),
+    ("dbgk_simplify_trace_branches", _i, [_vp, _vp, _u64, C.c_int32, C.POINTER(TraceSummary)]),
+    ("dbgk_simplify_trace_results", _i, [_vp, _vp, _vp, _vp, _vp]),
+    ("dbgk_simplify_update", _i, [_vp, _vp, _u64]),
+    ("dbgk_simplify_timing_get", _i, [_vp, C.POINTER(SimplifyTiming)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1633,3 +1654,39 @@ class ContigBuilder:
         s = ContigTiming()
         _chk(lib().dbgk_contig_timing_get(self._h, C.byref(s)), "dbgk_contig_timing_get")
         return {f: getattr(s, f) for f, _ in ContigTiming._fields_}
+
+    def _trace_results(self, s):
+        rows = np.zeros(max(s.rows, 1), dtype=TRACE_ROW_DTYPE)
+        first = np.zeros(s.rows + 1, dtype=np.uint64)
+        nodes = np.zeros(max(s.nodes, 1), dtype=np.uint32)
+        bases = np.zeros(max(s.nodes, 1), dtype=np.uint8)
+        _chk(lib().dbgk_simplify_trace_results(self._h, rows.ctypes.data, first.ctypes.data, nodes.ctypes.data, bases.ctypes.data),
+             "dbgk_simplify_trace_results")
+        return rows[:s.rows], first, nodes[:s.nodes], bases[:s.nodes], {f: getattr(s, f) for f, _ in TraceSummary._fields_}
+
+    def trace(self, slots, directs, len_cutoff):
+        """get_linear_path(slots[i], directs[i], len_cutoff) for every i (SIMPLIFY section of include/dbgk.h) -> rows (TRACE_ROW_DTYPE),
+        node offsets (uint64, rows + 1), nodes (uint32 slots), bases (uint8 codes 0..3 = ACGT), summary (dict)"""
+        req = np.zeros(len(slots), dtype=TRACE_REQUEST_DTYPE)
+        req["slot"], req["direct"] = slots, directs
+        s = TraceSummary()
+        _chk(lib().dbgk_simplify_trace(self._h, req.ctypes.data if len(req) else None, len(req), len_cutoff, C.byref(s)), "dbgk_simplify_trace")
+        return self._trace_results(s)
+
+    def trace_branches(self, slots, len_cutoff):
+        """8 rows per branching slot, row 8 i + 4 side + j (side 0 right, 1 left; base j) -> as trace()"""
+        slots = np.ascontiguousarray(slots, dtype=np.uint64)
+        s = TraceSummary()
+        _chk(lib().dbgk_simplify_trace_branches(self._h, slots.ctypes.data if len(slots) else None, len(slots), len_cutoff, C.byref(s)),
+             "dbgk_simplify_trace_branches")
+        return self._trace_results(s)
+
+    def update(self, slots):
+        """the arrays given to set_table were changed in place at these slots: carry link words, link records and delete bits over"""
+        slots = np.ascontiguousarray(slots, dtype=np.uint64)
+        _chk(lib().dbgk_simplify_update(self._h, slots.ctypes.data if len(slots) else None, len(slots)), "dbgk_simplify_update")
+
+    def simplify_timing(self):
+        s = SimplifyTiming()
+        _chk(lib().dbgk_simplify_timing_get(self._h, C.byref(s)), "dbgk_simplify_timing_get")
+        return {f: getattr(s, f) for f, _ in SimplifyTiming._fields_ if f != "reserved"}

@@ -117,6 +117,31 @@ __global__ __launch_bounds__(kContigThreads) void k_contig_compact_linear(Table 
 	}
 }
 
+// The neighbour of `kmer` through the link with code `base` on its left or right side (contig.h:119-130) in canonical form; a
+// palindrome counts as flipped (contig.cpp:802, :858).  k <= 31
+__device__ __forceinline__ uint64_t neighbour_key(const Table &t, uint64_t kmer, uint32_t base, uint32_t left, bool &flip)
+{
+	const uint64_t nk = left ? (kmer >> 2) + ((uint64_t)base << (2 * (t.k - 1))) : ((kmer << 2) | base) & ((1ull << (2 * t.k)) - 1);
+	const uint64_t rc = dbgk::revcomp_kbit(nk, t.k);
+	flip = !(nk < rc);
+	return flip ? rc : nk;
+}
+
+// exist_kmerset (kmerSet.cpp:280-302) on a table of either node width: the slot on the chain from hash % size for which same(slot)
+// holds, t.size when the chain ends at an empty slot first or the match is deleted.  Bounded by the table size: a table without an
+// empty slot ends here, not in a loop.  The one statement of the rule for the read-out's successors and the simplification walks
+template <class Tab, class Same>
+__device__ __forceinline__ uint64_t probe_slot(const Tab &t, uint64_t hash, Same same)
+{
+	uint64_t v = dbgk::fast_mod(hash, t.magic);
+	for (uint64_t tries = 0; tries < t.size; ++tries) {
+		if (!bit_of(t.nul, v)) break;
+		if (same(v)) return bit_of(t.del, v) ? t.size : v;
+		v = v + 1 == t.size ? 0 : v + 1;
+	}
+	return t.size;
+}
+
 // One step of get_linear_seq (contig.cpp:844-890) per port: the neighbour's k-mer, its canonical form and the direction the walk has
 // behind it, the probe of exist_kmerset (kmerSet.cpp:280-302: deleted and empty slots are absent), and how the step ends.
 //   raw_next[p]  port the walk continues through when the neighbour is a live linear node, kEnd otherwise
@@ -127,7 +152,6 @@ __global__ __launch_bounds__(kContigThreads) void k_contig_successors(Table t, c
                                                                       uint32_t *__restrict__ raw_next, uint32_t *__restrict__ step,
                                                                       uint32_t *__restrict__ end_slot)
 {
-	const uint64_t mask = (1ull << (2 * t.k)) - 1;   // k <= 31
 	for (uint32_t p = blockIdx.x * kContigThreads + threadIdx.x; p < n_ports; p += gridDim.x * kContigThreads) {
 		const uint32_t left = p & 1u;
 		const uint64_t u = slot_of[p >> 1];
@@ -136,20 +160,10 @@ __global__ __launch_bounds__(kContigThreads) void k_contig_successors(Table t, c
 		const uint32_t base = left ? (kl >> 2) & 3u : (kl >> 6) & 3u;
 		const uint32_t link = left ? (uint32_t)nd.links : (uint32_t)(nd.links >> 32);
 		const uint32_t depth = (link >> ((3u - base) * 8u)) & 0xffu;
-		const uint64_t nk = left ? (nd.kmer >> 2) + ((uint64_t)base << (2 * (t.k - 1))) : ((nd.kmer << 2) | base) & mask;
-		const uint64_t rc = dbgk::revcomp_kbit(nk, t.k);
-		const bool flip = !(nk < rc);
-		const uint64_t key = flip ? rc : nk;
-		uint64_t v = dbgk::fast_mod(dbgk::hash_code(key), t.magic);
-		bool found = false;
-		for (uint64_t tries = 0; tries < t.size; ++tries) {            // a table without an empty slot ends here, not in a loop
-			if (!bit_of(t.nul, v)) break;
-			if (t.array[v].kmer == key) {
-				found = !bit_of(t.del, v);
-				break;
-			}
-			v = v + 1 == t.size ? 0 : v + 1;
-		}
+		bool flip;
+		const uint64_t key = neighbour_key(t, nd.kmer, base, left, flip);
+		const uint64_t v = probe_slot(t, dbgk::hash_code(key), [&](uint64_t s) { return t.array[s].kmer == key; });
+		const bool found = v != t.size;
 		uint32_t cls = END_ABSENT, nxt = kEnd, es = kEnd;
 		if (found) {
 			const uint32_t kv = t.klink[v];

@@ -34,6 +34,14 @@ struct dbgk_contig {
 	std::vector<char> bases, depths;
 	dbgk_contig_summary summary{};
 	dbgk_contig_timing timing{};
+	// SIMPLIFY (dbgk_host_simplify.h): what the last trace call found
+	bool traced = false;
+	std::vector<dbgk_trace_row> trace_rows;
+	std::vector<uint64_t> trace_first;
+	std::vector<uint32_t> trace_nodes;
+	std::vector<uint8_t> trace_bases;
+	dbgk_trace_summary trace_summary{};
+	dbgk_simplify_timing simplify_timing{};
 };
 
 static_assert(sizeof(dbgk_contig_record) == 48 && sizeof(contigk::Record) == 48 && offsetof(dbgk_contig_record, left_mark) == 40 &&
@@ -130,6 +138,8 @@ static int contig_set_table(dbgk_contig *c, uint64_t size, const void *array, si
 	HIPCHK(hipMemcpyAsync(c->d_klink, klink, size * 2, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	c->timing = dbgk_contig_timing{};
+	c->simplify_timing = dbgk_simplify_timing{};
+	c->traced = false;
 	c->timing.ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 	c->timing.upload_bytes = size * (node_bytes + 2) + 2 * flag_bytes;
 	c->size = size;

@@ -1,8 +1,14 @@
 // contig_stage.cpp -- the contig stage of debruijn_contig (see contig_stage.h).
 //
-// The three simplification passes run on the host in list order: each removal re-derives the links of the nodes at its ends
-// (recalculate_kmer_links, DBG_contig/contig.cpp:210-277) and so changes what later list entries see.  The read-out runs on the
-// GPU through the CONTIG section of include/dbgk.h; header strings, the sort by length, ids and the -M split are done here.
+// The three simplification passes decide on the host in list order: each removal re-derives the links of the nodes at its ends
+// (recalculate_kmer_links, DBG_contig/contig.cpp:210-277) and so changes what later list entries see.  That holds for the decisions,
+// not for the walks: a removal sets the delete flag of its path's nodes and recalculates one or two end nodes, and a later walk
+// differs only if it touches one of those slots.  So before a pass all of its walks (get_linear_path, :779-827) are traced at once on
+// the GPU against the table as it stands then (SIMPLIFY section of include/dbgk.h), the loops consume the traces in list order, and
+// a bitmap of the slots changed since says where a trace no longer holds: there the host walks the path itself, as it did for every
+// path before (traced_or_walked).  After a pass the changed slots go to the device copy, which the read-out then uses as it is.
+// The read-out runs on the GPU through the CONTIG section of include/dbgk.h; header strings, the sort by length, ids and the -M split
+// are done here.  Test hook simplify_host=1: no tracing, every path walked on the host.
 // Line numbers name DBG_contig/contig.cpp unless another file is given.
 //
 // The stage is written once over the key type (Stage<G>): Keys64 is `kset` with the reference's uint64_t k-mers, Keys128 is
@@ -182,7 +188,106 @@ typedef typename G::Key Key;
 
 // "no such node" is slot size(); the reference looks at klink[G::size()] there (:810, :648), this build calls it not linear
 static bool is_linear(uint64_t i) { return i != G::size() && (klink[i] & 0x100); }
-static void set_flag(uint64_t i, int flag) { if (i != G::size()) klink[i] |= flag; }
+// bits 9..12 are read by no walk: the slot goes to the device copy, but no trace is lost over it
+static void set_flag(uint64_t i, int flag)
+{
+	if (i == G::size()) return;
+	klink[i] |= flag;
+	if (handle) dirty.push_back(i);
+}
+
+// ---- the traced walks of the pass that is running ----
+static dbgk_contig *handle;                    // made before the first enabled pass, kept through the read-out
+static bool have_traces;                       // this pass has traces (its cutoff fits DBGK_TRACE_MAX_CUTOFF)
+static std::vector<dbgk_trace_row> rows;
+static std::vector<uint64_t> node_first;
+static std::vector<uint32_t> trace_nodes;
+static std::vector<uint8_t> trace_bases;
+static std::vector<uint8_t> changed;           // one bit per slot: changed since the traces were taken
+static std::vector<uint64_t> dirty;            // slots to carry to the device copy after the pass
+static uint64_t n_used, n_fell_back;
+
+static bool is_changed(uint64_t i) { return (changed[i >> 3] >> (i & 7)) & 1; }
+static void mark_changed(uint64_t i)
+{
+	if (!handle) return;
+	changed[i >> 3] |= (uint8_t)(1u << (i & 7));
+	dirty.push_back(i);
+}
+
+static int gpu_failed(int rc)
+{
+	cerr << "tracing the simplification paths on the GPU failed: " << dbgk_strerror(rc) << " " << dbgk_last_error() << endl;
+	return rc;
+}
+
+// the handle with the table as it stands; 0, or a DBGK_ERR_* code
+static int open_handle()
+{
+	dbgk_contig_params prm = {KmerSize, KmerFreqCutoff < 0 ? 0 : KmerFreqCutoff, Contig_len_cutoff, 0};
+	const char *dev = getenv("DBGK_DEVICE");
+	int rc = G::create(&prm, dev ? atoi(dev) : 0, &handle);
+	if (!rc) rc = G::set_table(handle);
+	if (rc && handle) {
+		dbgk_contig_destroy(handle);
+		handle = NULL;
+	}
+	return rc;
+}
+
+// Before a pass: trace its walks -- `list` holds tips (requests (idx, l_num(idx) == 1 ? -1 : +1)) or branching nodes (8 rows each).
+// get_branch_bases compares with KmerFreqCutoff as it is; the handle holds max(KmerFreqCutoff, 0).  For a negative cutoff the two differ
+// on edges of depth 0: the host admits them (0 > -1), the kernel's row says BELOW_CUTOFF.  Such a row has no trace, so the host walks
+// that path itself and the result is the same
+static int begin_pass(const std::vector<uint64_t> &list, bool tips, int len_cutoff)
+{
+	have_traces = false;
+	n_used = n_fell_back = 0;
+	if (dbgk_hook("simplify_host")) return 0;
+	if (!handle) {
+		const int rc = open_handle();
+		if (rc) return gpu_failed(rc);
+	}
+	changed.assign(G::size() / 8 + 1, 0);
+	dirty.clear();
+	if (len_cutoff > DBGK_TRACE_MAX_CUTOFF) return 0;
+	dbgk_trace_summary sum;
+	int rc;
+	if (tips) {
+		std::vector<dbgk_trace_request> req(list.size());
+		for (size_t i = 0; i < list.size(); i++) req[i] = dbgk_trace_request{list[i], l_num(list[i]) == 1 ? -1 : 1, 0};
+		rc = dbgk_simplify_trace(handle, req.data(), req.size(), len_cutoff, &sum);
+	} else {
+		rc = dbgk_simplify_trace_branches(handle, list.data(), list.size(), len_cutoff, &sum);
+	}
+	if (rc) return gpu_failed(rc);
+	rows.resize(sum.rows);
+	node_first.resize(sum.rows + 1);
+	trace_nodes.resize(sum.nodes);
+	trace_bases.resize(sum.nodes);
+	rc = dbgk_simplify_trace_results(handle, rows.data(), node_first.data(), trace_nodes.data(), trace_bases.data());
+	if (rc) return gpu_failed(rc);
+	have_traces = true;
+	return 0;
+}
+
+// After a pass: the device copy gets what the pass changed; the pass's line under DBGK_TIMINGS
+static int end_pass(const char *name, dbgk_simplify_timing &before)
+{
+	if (!handle) return 0;
+	const int rc = dbgk_simplify_update(handle, dirty.data(), dirty.size());
+	if (rc) return gpu_failed(rc);
+	dbgk_simplify_timing now;
+	dbgk_simplify_timing_get(handle, &now);
+	if (getenv("DBGK_TIMINGS"))
+		cerr << "Contig stage traced paths (" << name << "): requests " << (have_traces ? rows.size() : 0) << " traces used " << n_used
+		     << " fell back to the host walk " << n_fell_back << " device ms "
+		     << (now.ms_trace + now.ms_branches + now.ms_fill + now.ms_update) - (before.ms_trace + before.ms_branches + before.ms_fill + before.ms_update)
+		     << " bytes copied back " << now.bytes_returned - before.bytes_returned << endl;
+	before = now;
+	have_traces = false;
+	return 0;
+}
 // array[G::size()].kmer, which the reference prints for an end without a node (:344, :1006): the word behind its table, 0 there
 static std::string kmer_at(uint64_t i) { return G::decimal(i == G::size() ? (Key)0 : G::kmer(i)); }
 
@@ -225,6 +330,7 @@ static void first_pass_host(std::vector<uint64_t> &tips, std::vector<uint64_t> &
 static void recalculate(uint64_t idx)
 {
 	if (idx == G::size()) return;
+	mark_changed(idx);
 	const Key kmer = G::kmer(idx);
 	int num[2] = {0, 0}, base[2] = {0, 0};
 	for (int side = 0; side < 2; side++) {
@@ -280,9 +386,40 @@ static void linear_path(uint64_t idx, int direct, int len_cutoff, Path &p)
 	}
 }
 
+// linear_path(idx, direct, len_cutoff, p), from the pass's trace where that still holds.  row: the request's (a tip), or
+// 8 i + 4 side + j for base j on the right (side 0) or left of branching node i; branch: that node, or size() for a tip.  The trace
+// is the walk if and only if the branching node is unchanged (its row was derived from its link words), the row starts where the
+// host just found the walk to start, in that direction, and no node of the path and not its last slot has changed; every slot a
+// walk reads beyond those -- the probe chains it passes -- holds keys and filled bits, which no pass changes.
+static void traced_or_walked(uint64_t row, uint64_t branch, uint64_t idx, int direct, int len_cutoff, Path &p)
+{
+	if (have_traces) {
+		const dbgk_trace_row &r = rows[row];
+		bool ok = r.status == DBGK_TRACE_TRACED && r.len > 0 && r.start == idx && r.direct == direct && (branch == G::size() || !is_changed(branch)) &&
+		          (r.last == G::size() || !is_changed(r.last));
+		for (uint64_t j = node_first[row]; ok && j < node_first[row + 1]; j++) ok = !is_changed(trace_nodes[j]);
+		if (ok) {
+			n_used++;
+			p.len = (int)r.len;
+			p.depth = (int)r.depth;
+			p.last = r.last;
+			p.mark = r.mark ? "branch" : "break";
+			p.nodes.assign(trace_nodes.begin() + node_first[row], trace_nodes.begin() + node_first[row + 1]);
+			p.str.resize(r.len);
+			for (uint32_t j = 0; j < r.len; j++) p.str[j] = bases[trace_bases[node_first[row] + j]];
+			return;
+		}
+		n_fell_back++;
+	}
+	linear_path(idx, direct, len_cutoff, p);
+}
+
 static void delete_nodes(const std::vector<uint64_t> &nodes)
 {
-	for (uint64_t v : nodes) set_entity_delete(G::del_flag(), v);
+	for (uint64_t v : nodes) {
+		set_entity_delete(G::del_flag(), v);
+		mark_changed(v);
+	}
 }
 
 // the path as it reads from left to right: k-mer of its first node in front of, or behind, the steps' bases (:335-342)
@@ -301,10 +438,11 @@ static void remove_tips(const std::vector<uint64_t> &tips)
 	const string path = Output_prefix + ".contig.tip.fa";
 	ofstream out(path.c_str());
 	if (!out) cerr << "fail to open file " << path << endl;
-	for (uint64_t idx : tips) {
+	for (size_t i = 0; i < tips.size(); i++) {
+		const uint64_t idx = tips[i];
 		const int direct = (l_num(idx) == 1) ? -1 : 1;
 		Path p;
-		linear_path(idx, direct, Tip_len_cutoff, p);
+		traced_or_walked(i, G::size(), idx, direct, Tip_len_cutoff, p);
 		const double avg = (double)p.depth / p.len;
 		if (!(avg <= Tip_depth_cutoff && p.len <= Tip_len_cutoff)) continue;
 		total_num++;
@@ -330,7 +468,8 @@ static void remove_low_edges(const std::vector<uint64_t> &branches)
 	const string path = Output_prefix + ".contig.lowedge.fa";
 	ofstream out(path.c_str());
 	if (!out) cerr << "fail to open file " << path << endl;
-	for (uint64_t idx : branches) {
+	for (size_t i = 0; i < branches.size(); i++) {
+		const uint64_t idx = branches[i];
 		for (int direct = 1; direct >= -1; direct -= 2) {
 			if ((direct == 1 ? r_num(idx) : l_num(idx)) < 2) continue;
 			std::vector<uint8_t> vb, vd;
@@ -342,7 +481,7 @@ static void remove_low_edges(const std::vector<uint64_t> &branches)
 				const uint64_t idx1 = G::exist(key);
 				if (!is_linear(idx1)) continue;
 				Path p;
-				linear_path(idx1, direct1, LowCovEdge_len_cutoff, p);
+				traced_or_walked(8 * i + (direct == 1 ? 0 : 4) + vb[j], idx, idx1, direct1, LowCovEdge_len_cutoff, p);
 				const int len = p.len + 1, depth = p.depth + vd[j];
 				const double avg = (double)depth / len;
 				if (!(len <= LowCovEdge_len_cutoff && avg <= LowCovEdge_depth_cutoff && !is_linear(p.last))) continue;
@@ -375,7 +514,8 @@ static void remove_bubbles(const std::vector<uint64_t> &branches)
 	ofstream out(path.c_str());
 	if (!out) cerr << "fail to open file " << path << endl;
 	uint64_t total_num = 0, total_len = 0;
-	for (uint64_t idx : branches) {
+	for (size_t i = 0; i < branches.size(); i++) {
+		const uint64_t idx = branches[i];
 		int direct = 0;
 		std::vector<uint8_t> vb, vd;
 		if (l_num(idx) == 2 && r_num(idx) == 1) {
@@ -397,8 +537,7 @@ static void remove_bubbles(const std::vector<uint64_t> &branches)
 		}
 		if (!is_linear(first[0]) || !is_linear(first[1])) continue;
 		Path p[2];
-		linear_path(first[0], dir[0], Bubble_len_cutoff, p[0]);
-		linear_path(first[1], dir[1], Bubble_len_cutoff, p[1]);
+		for (int e = 0; e < 2; e++) traced_or_walked(8 * i + (direct == 1 ? 0 : 4) + vb[e], idx, first[e], dir[e], Bubble_len_cutoff, p[e]);
 		const double avg1 = (double)p[0].depth / p[0].len, avg2 = (double)p[1].depth / p[1].len;
 		if (p[0].last != p[1].last) {
 			if (avg1 > LowCovEdge_depth_cutoff && avg2 > LowCovEdge_depth_cutoff) set_flag(idx, IN_REPEAT);   // a tiny repeat, no bubble (:471-473)
@@ -457,12 +596,11 @@ static int read_out(double &ms_gpu, double &ms_files)
 	if (!small_out || !small_depth_out) cerr << "fail to open small file " << small_path << "\t" << small_depth_path << endl;
 
 	auto t0 = std::chrono::steady_clock::now();
-	dbgk_contig *h = NULL;
-	dbgk_contig_params prm = {KmerSize, KmerFreqCutoff < 0 ? 0 : KmerFreqCutoff, Contig_len_cutoff, 0};
-	const char *dev = getenv("DBGK_DEVICE");
+	// the passes' handle, whose device copy they kept equal to the host arrays; without one (no pass, or simplify_host) the table goes up here
 	dbgk_contig_summary sum;
-	int rc = G::create(&prm, dev ? atoi(dev) : 0, &h);
-	if (!rc) rc = G::set_table(h);
+	int rc = handle ? 0 : open_handle();
+	dbgk_contig *h = handle;
+	handle = NULL;
 	if (!rc) rc = dbgk_contig_read_out(h, &sum);
 	if (rc) {
 		cerr << "contig read-out on the GPU failed: " << dbgk_strerror(rc) << " " << dbgk_last_error() << endl;
@@ -534,6 +672,7 @@ static int read_out(double &ms_gpu, double &ms_files)
 static int run()
 {
 	double ms_first = 0, ms_tip = 0, ms_edge = 0, ms_bubble = 0, ms_gpu = 0, ms_files = 0;
+	dbgk_simplify_timing traced_so_far = {};
 	cerr << "\nStart to calulate kmer links information!" << endl;
 	if (sizeof(Key) > 8) cerr << "Contig stage on 128-bit k-mers (32-byte nodes; parity unpinned above k = 32)" << endl;
 	auto t0 = std::chrono::steady_clock::now();
@@ -555,21 +694,27 @@ static int run()
 	if (is_remove_tip) {
 		cerr << "\nStart to remove tips caused by sequencing error!" << endl;
 		t0 = std::chrono::steady_clock::now();
+		if (int rc = begin_pass(tips, true, Tip_len_cutoff)) return rc;
 		remove_tips(tips);
+		if (int rc = end_pass("tips", traced_so_far)) return rc;
 		ms_tip = ms_since(t0);
 		finished("Finished!");
 	}
 	if (is_remove_lowedge) {
 		cerr << "\nStart to remove small low coverage edges between two branching nodes!" << endl;
 		t0 = std::chrono::steady_clock::now();
+		if (int rc = begin_pass(branches, false, LowCovEdge_len_cutoff)) return rc;
 		remove_low_edges(branches);
+		if (int rc = end_pass("low edges", traced_so_far)) return rc;
 		ms_edge = ms_since(t0);
 		finished("Finshed!");        // :82
 	}
 	if (is_remove_bubble) {
 		cerr << "\nStart to remove bubbles caused by repeats and heterozygotes!" << endl;
 		t0 = std::chrono::steady_clock::now();
+		if (int rc = begin_pass(branches, false, Bubble_len_cutoff)) return rc;
 		remove_bubbles(branches);
+		if (int rc = end_pass("bubbles", traced_so_far)) return rc;
 		ms_bubble = ms_since(t0);
 		finished("Finished!");
 	}
@@ -583,6 +728,17 @@ static int run()
 	return 0;
 }
 };   // Stage
+
+template <class G> dbgk_contig *Stage<G>::handle = NULL;
+template <class G> bool Stage<G>::have_traces = false;
+template <class G> std::vector<dbgk_trace_row> Stage<G>::rows;
+template <class G> std::vector<uint64_t> Stage<G>::node_first;
+template <class G> std::vector<uint32_t> Stage<G>::trace_nodes;
+template <class G> std::vector<uint8_t> Stage<G>::trace_bases;
+template <class G> std::vector<uint8_t> Stage<G>::changed;
+template <class G> std::vector<uint64_t> Stage<G>::dirty;
+template <class G> uint64_t Stage<G>::n_used = 0;
+template <class G> uint64_t Stage<G>::n_fell_back = 0;
 
 } // namespace
 

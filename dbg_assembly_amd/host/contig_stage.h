@@ -1,4 +1,6 @@
-// contig_stage.h -- the contig stage of debruijn_contig: graph simplification on the host, contig read-out on the GPU.
+// contig_stage.h -- the contig stage of debruijn_contig: graph simplification decided on the host in list order over paths traced on
+// the GPU (all walks of a pass at once, against the table as the pass finds it; the host walks a path itself where its trace touches a
+// slot changed since), contig read-out on the GPU on the same handle.  Test hook simplify_host=1: no tracing.
 //
 // Follows build_contig_sequence() of the reference (DBG_contig/contig.cpp:54-102) pass by pass, with its stderr protocol and its
 // eight <prefix>.contig.* files.  Linked into bin/debruijn_contig only: a program that links the reference's own contig.cpp next to

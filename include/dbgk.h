@@ -1111,6 +1111,73 @@ int dbgk_wide_contig_create(const dbgk_contig_params *p, int device, dbgk_contig
 int dbgk_wide_contig_set_table(dbgk_contig *c, uint64_t size, const dbgk_node32 *array, const uint8_t *nul_flag, const uint8_t *del_flag,
                                const uint16_t *klink);
 
+/* ---- SIMPLIFY: the linear paths of the contig stage's simplification passes, traced on the GPU (additions to ABI 7) ------------------
+ * remove_error_tips, remove_lowCov_edges and remove_hetero_bubbles (DBG_contig/contig.cpp:281-776) call get_linear_path (:779-827) once
+ * per list entry, in list order.  These calls trace all walks of a pass at once on the device copy of the table a CONTIG handle holds
+ * (dbgk_contig_set_table / dbgk_wide_contig_set_table), as the table stands at that moment; the caller consumes them in list order and
+ * walks a path itself where a trace touches a slot it has changed since.  dbgk_simplify_update carries the caller's changes into the
+ * device copy.  All calls serve both kinds of handle (PARITY UNPINNED above k = 32, as for the read-out).  Arguments are checked before
+ * any device work: a slot at or above the table size, a direct other than +1 / -1 and a len_cutoff above DBGK_TRACE_MAX_CUTOFF are
+ * DBGK_ERR_ARG, a call before set_table is DBGK_ERR_STATE.  There is no host fall-back.                                              */
+#define DBGK_TRACE_MAX_CUTOFF 65536   /* a walk on a cycle ends at the cutoff only */
+
+typedef struct dbgk_trace_request {
+	uint64_t slot;              /* the node the walk starts from: walked whatever its state                                */
+	int32_t  direct;            /* +1 leaving rightward, -1 leaving leftward                                              */
+	int32_t  reserved;          /* 0                                                                                      */
+} dbgk_trace_request;
+
+/* status of a row */
+#define DBGK_TRACE_TRACED        0   /* a walk: len >= 1                                                                   */
+#define DBGK_TRACE_BELOW_CUTOFF  1   /* branch rows: the edge's depth is not above kmer_freq_cutoff; no neighbour looked up */
+#define DBGK_TRACE_ABSENT        2   /* branch rows: the neighbour is not in the table (or deleted); start = table size    */
+#define DBGK_TRACE_NOT_LINEAR    3   /* branch rows: the neighbour (start) is no linear node                               */
+
+typedef struct dbgk_trace_row {
+	uint32_t start;             /* slot the walk starts from; table size when there is none                               */
+	uint32_t last;              /* the slot get_linear_path returns; table size when there is no such node                */
+	uint32_t len;               /* steps (0 without a walk)                                                               */
+	uint32_t depth;             /* sum of the steps' link depths                                                          */
+	int8_t   direct;            /* direction at start, +1 / -1 (for a branch row: after the flip); 0 when not looked up   */
+	uint8_t  mark;              /* 0 break, 1 branch                                                                      */
+	uint8_t  status;            /* DBGK_TRACE_*                                                                           */
+	uint8_t  pad;
+	uint32_t reserved;
+} dbgk_trace_row;
+
+typedef struct dbgk_trace_summary {
+	uint64_t rows;              /* requests, or 8 per branching slot                                                      */
+	uint64_t traced;            /* rows with a walk                                                                       */
+	uint64_t nodes;             /* steps of all walks                                                                     */
+	uint64_t batches;           /* batches the rows were traced in                                                        */
+} dbgk_trace_summary;
+
+typedef struct dbgk_simplify_timing {   /* sums since set_table */
+	uint64_t bytes_returned;    /* rows, nodes and base codes copied back from the device                                 */
+	uint64_t batches;
+	uint64_t updated_slots;
+	uint64_t reserved;
+	double ms_trace;            /* device time of the length pass of dbgk_simplify_trace                                  */
+	double ms_branches;         /* ... of dbgk_simplify_trace_branches                                                    */
+	double ms_fill;             /* device time of the pass that writes nodes and base codes                               */
+	double ms_update;           /* device time of the update kernel                                                       */
+} dbgk_simplify_timing;
+
+/* get_linear_path(req[i].slot, req[i].direct, len_cutoff) for every i < n, one row each.  out may be NULL; n may be 0.           */
+int dbgk_simplify_trace(dbgk_contig *c, const dbgk_trace_request *req, uint64_t n, int32_t len_cutoff, dbgk_trace_summary *out);
+/* for every listed slot 8 rows: row 8 i + 4 side + j is the edge of base j on the right (side 0) or left (side 1) of slots[i].  An edge
+ * whose link depth is above the handle's kmer_freq_cutoff (get_branch_bases, :361-370) has its neighbour looked up; a neighbour that is
+ * a live linear node is traced with len_cutoff, in the direction the walk has there.                                               */
+int dbgk_simplify_trace_branches(dbgk_contig *c, const uint64_t *slots, uint64_t n, int32_t len_cutoff, dbgk_trace_summary *out);
+/* what the last trace call found: rows (summary.rows), node_offsets (rows + 1: row i's steps are [node_offsets[i], node_offsets[i + 1])
+ * of nodes and of bases), nodes (summary.nodes slots), bases (summary.nodes base codes 0..3 = ACGT, in the orientation the path's
+ * string has, :793-800).  Any pointer may be NULL.  DBGK_ERR_STATE before a trace call.                                             */
+int dbgk_simplify_trace_results(dbgk_contig *c, dbgk_trace_row *rows, uint64_t *node_offsets, uint32_t *nodes, uint8_t *bases);
+/* reads the host arrays given to set_table again at these slots -- the node's two link words, its link record, its delete bit -- and
+ * writes them into the device copy.  A slot may be listed more than once.                                                          */
+int dbgk_simplify_update(dbgk_contig *c, const uint64_t *slots, uint64_t n);
+int dbgk_simplify_timing_get(dbgk_contig *c, dbgk_simplify_timing *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
