@@ -226,6 +226,20 @@ class TraceSummary(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("rows", "traced", "nodes", "batches")]
 
 
+ALIGN_ROW_DTYPE = np.dtype([("len_i", "<u4"), ("len_j", "<u4"), ("score", "<i4"), ("aligned_len", "<u4"), ("diffs", "<u4"), ("status", "u1"),
+                            ("pad", "u1", (3,))])  # dbgk_align_row
+ALIGN_MAX_LEN = 256
+ALIGN_DONE, ALIGN_TOO_LONG = 0, 1
+
+
+class AlignSummary(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("pairs", "aligned", "too_long", "batches", "aligned_bytes", "reserved")]
+
+
+class AlignTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("bytes_up", "bytes_back", "batches", "pairs", "cells", "reserved")] + [("ms_align", C.c_double)]
+
+
 class SimplifyTiming(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("bytes_returned", "batches", "updated_slots", "reserved")] + \
                [(f, C.c_double) for f in ("ms_trace", "ms_branches", "ms_fill", "ms_update")]
@@ -409,6 +423,9 @@ SYMBOLS = [
     ("dbgk_simplify_trace_results", _i, [_vp, _vp, _vp, _vp, _vp]),
     ("dbgk_simplify_update", _i, [_vp, _vp, _u64]),
     ("dbgk_simplify_timing_get", _i, [_vp, C.POINTER(SimplifyTiming)]),
+    ("dbgk_align_pairs", _i, [_vp, _vp, _vp, _u64, C.POINTER(AlignSummary)]),
+    ("dbgk_align_results", _i, [_vp, _vp, _vp, _vp, _vp]),
+    ("dbgk_align_timing_get", _i, [_vp, C.POINTER(AlignTiming)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1690,3 +1707,28 @@ class ContigBuilder:
         s = SimplifyTiming()
         _chk(lib().dbgk_simplify_timing_get(self._h, C.byref(s)), "dbgk_simplify_timing_get")
         return {f: getattr(s, f) for f, _ in SimplifyTiming._fields_ if f != "reserved"}
+
+    def align(self, pairs):
+        """global_aligning(a, b) for every (a, b) of pairs (str or bytes over ACGT; SIMPLIFY section of include/dbgk.h) -> rows
+        (ALIGN_ROW_DTYPE), the aligned first strings and the aligned second strings (lists of bytes; b"" for a pair that is
+        ALIGN_TOO_LONG), summary (dict).  Needs no table."""
+        seqs = [x.encode() if isinstance(x, str) else bytes(x) for pair in pairs for x in pair]
+        offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(x) for x in seqs], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+        n = len(seqs) // 2
+        s = AlignSummary()
+        _chk(lib().dbgk_align_pairs(self._h, blob.ctypes.data if n else None, offsets.ctypes.data if n else None, n, C.byref(s)), "dbgk_align_pairs")
+        rows = np.zeros(max(n, 1), dtype=ALIGN_ROW_DTYPE)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        a_i = np.zeros(max(s.aligned_bytes, 1), dtype=np.uint8)
+        a_j = np.zeros(max(s.aligned_bytes, 1), dtype=np.uint8)
+        _chk(lib().dbgk_align_results(self._h, rows.ctypes.data, first.ctypes.data, a_i.ctypes.data, a_j.ctypes.data), "dbgk_align_results")
+        cut = [int(v) for v in first]
+        return (rows[:n], [a_i[cut[p]:cut[p + 1]].tobytes() for p in range(n)], [a_j[cut[p]:cut[p + 1]].tobytes() for p in range(n)],
+                {f: getattr(s, f) for f, _ in AlignSummary._fields_ if f != "reserved"})
+
+    def align_timing(self):
+        s = AlignTiming()
+        _chk(lib().dbgk_align_timing_get(self._h, C.byref(s)), "dbgk_align_timing_get")
+        return {f: getattr(s, f) for f, _ in AlignTiming._fields_ if f != "reserved"}

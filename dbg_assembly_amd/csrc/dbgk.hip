@@ -33,6 +33,7 @@
 #include "dbgk_wide_contig.h"
 #include "dbgk_simplify.h"
 #include "dbgk_wide_simplify.h"
+#include "dbgk_align.h"
 
 // dbgk_sort.hip
 extern "C" int dbgk_internal_sort_pairs(uint64_t *d_keys, uint64_t *d_vals, uint64_t n, hipStream_t stream);
@@ -464,3 +465,4 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_super.h"
 #include "dbgk_host_contig.h"
 #include "dbgk_host_simplify.h"
+#include "dbgk_host_align.h"

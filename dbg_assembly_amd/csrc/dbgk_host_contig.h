@@ -42,6 +42,13 @@ struct dbgk_contig {
 	std::vector<uint8_t> trace_bases;
 	dbgk_trace_summary trace_summary{};
 	dbgk_simplify_timing simplify_timing{};
+	// ALIGN (dbgk_host_align.h): what the last dbgk_align_pairs found
+	bool aligned = false;
+	std::vector<dbgk_align_row> align_rows;
+	std::vector<uint64_t> align_first;
+	std::vector<char> align_i, align_j;
+	dbgk_align_summary align_summary{};
+	dbgk_align_timing align_timing{};
 };
 
 static_assert(sizeof(dbgk_contig_record) == 48 && sizeof(contigk::Record) == 48 && offsetof(dbgk_contig_record, left_mark) == 40 &&

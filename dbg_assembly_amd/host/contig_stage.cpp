@@ -9,6 +9,10 @@
 // path before (traced_or_walked).  After a pass the changed slots go to the device copy, which the read-out then uses as it is.
 // The read-out runs on the GPU through the CONTIG section of include/dbgk.h; header strings, the sort by length, ids and the -M split
 // are done here.  Test hook simplify_host=1: no tracing, every path walked on the host.
+// The bubbles pass aligns two arms where their lengths differ or too many of their bases do (global_aligning).  An alignment is a function
+// of its two strings, so those of all bubbles the pass's traces show are computed at once on the GPU when the pass begins
+// (collect_alignments, dbgk_align_pairs); the ordered loop takes a result if and only if the strings it holds at that moment are byte
+// for byte the submitted ones, and aligns on the host otherwise.  Test hooks: align_host=1, nothing is submitted; align_stale=1, see collect_alignments.
 // Line numbers name DBG_contig/contig.cpp unless another file is given.
 //
 // The stage is written once over the key type (Stage<G>): Keys64 is `kset` with the reference's uint64_t k-mers, Keys128 is
@@ -207,6 +211,14 @@ static std::vector<uint8_t> changed;           // one bit per slot: changed sinc
 static std::vector<uint64_t> dirty;            // slots to carry to the device copy after the pass
 static uint64_t n_used, n_fell_back;
 
+// ---- the alignments of the bubbles pass, computed when it begins ----
+static std::vector<int64_t> pair_of;           // per entry of the pass's list: the pair it submitted, or -1
+static std::vector<std::string> submitted;     // pair p: strings 2 p and 2 p + 1, as composed from the traces
+static std::vector<dbgk_align_row> align_rows;
+static std::vector<uint64_t> align_first;
+static std::string align_i, align_j;
+static uint64_t n_candidates, n_too_long, n_align_used, n_align_host;
+
 static bool is_changed(uint64_t i) { return (changed[i >> 3] >> (i & 7)) & 1; }
 static void mark_changed(uint64_t i)
 {
@@ -269,6 +281,113 @@ static int begin_pass(const std::vector<uint64_t> &list, bool tips, int len_cuto
 	if (rc) return gpu_failed(rc);
 	have_traces = true;
 	return 0;
+}
+
+// the string of a traced row, as path_sequence gives it for the walk
+static std::string traced_sequence(uint64_t row)
+{
+	const dbgk_trace_row &r = rows[row];
+	std::string steps(r.len, 'A');
+	for (uint32_t j = 0; j < r.len; j++) steps[j] = bases[trace_bases[node_first[row] + j]];
+	return path_sequence(r.start, r.direct, steps);
+}
+
+// Before the bubbles pass, behind begin_pass: every list entry that is a bubble in the pass's traces -- two edges on one side, one on the
+// other, both arms traced, both ending on the same node -- has its two strings composed as remove_bubbles composes them, and those that
+// remove_bubbles would align (the same expressions, in double) go to the GPU in one call.  Reads rows, never traced_or_walked: the pass's
+// counts of used traces are not touched.  Without traces, or under the test hook align_host, nothing is submitted.
+static int collect_alignments(const std::vector<uint64_t> &branches)
+{
+	pair_of.clear();
+	submitted.clear();
+	align_rows.clear();
+	n_candidates = n_too_long = n_align_used = n_align_host = 0;
+	if (!have_traces) return 0;
+	const bool submit = !dbgk_hook("align_host");
+	// test hook align_stale: every pair goes up with its two strings exchanged, so no result is the one the loop asks for -- the only way
+	// to the other side of the comparison in aligned_arms, which no removal of this pass can bring about
+	const bool exchange = dbgk_hook("align_stale") != NULL;
+	pair_of.assign(branches.size(), -1);
+	for (size_t i = 0; i < branches.size(); i++) {
+		const uint64_t idx = branches[i];
+		int direct = 0;
+		std::vector<uint8_t> vb, vd;
+		if (l_num(idx) == 2 && r_num(idx) == 1) {
+			direct = -1;
+			branch_bases(G::l_link(idx), vb, vd);
+		} else if (l_num(idx) == 1 && r_num(idx) == 2) {
+			direct = 1;
+			branch_bases(G::r_link(idx), vb, vd);
+		} else {
+			continue;
+		}
+		if (vb.size() < 2) continue;
+		const uint64_t row1 = 8 * i + (direct == 1 ? 0 : 4) + vb[0], row2 = 8 * i + (direct == 1 ? 0 : 4) + vb[1];
+		const dbgk_trace_row &r1 = rows[row1], &r2 = rows[row2];
+		if (r1.status != DBGK_TRACE_TRACED || r2.status != DBGK_TRACE_TRACED || r1.last != r2.last) continue;
+		n_candidates++;
+		std::string s1 = traced_sequence(row1), s2 = traced_sequence(row2);
+		if (r1.direct != r2.direct) {
+			std::reverse(s1.begin(), s1.end());
+			complement_sequence(s1);
+		}
+		const int len1 = (int)r1.len + 1, len2 = (int)r2.len + 1;
+		double diff_rate = 0;
+		if (len1 == len2) diff_rate = (double)count_differences(s1, s2) / len1;
+		if (!(len1 != len2 || diff_rate > Bubble_base_diff_rate_cutoff) || !submit) continue;
+		if (exchange) s1.swap(s2);
+		pair_of[i] = (int64_t)(submitted.size() / 2);
+		submitted.push_back(s1);
+		submitted.push_back(s2);
+	}
+	if (submitted.empty()) return 0;
+	std::string seqs;
+	std::vector<uint64_t> offsets(1, 0);
+	for (const std::string &t : submitted) {
+		seqs += t;
+		offsets.push_back(seqs.size());
+	}
+	dbgk_align_summary sum;
+	int rc = dbgk_align_pairs(handle, seqs.data(), offsets.data(), submitted.size() / 2, &sum);
+	if (rc) return gpu_failed(rc);
+	align_rows.resize(sum.pairs);
+	align_first.resize(sum.pairs + 1);
+	align_i.assign(sum.aligned_bytes, '\0');
+	align_j.assign(sum.aligned_bytes, '\0');
+	rc = dbgk_align_results(handle, align_rows.data(), align_first.data(), &align_i[0], &align_j[0]);
+	if (rc) return gpu_failed(rc);
+	n_too_long = sum.too_long;
+	return 0;
+}
+
+// global_aligning(s1, s2) for entry i of the pass's list: the GPU's strings if and only if this entry submitted a pair, the strings the
+// loop holds now are byte for byte the submitted ones, and the pair was aligned; on the host otherwise
+static void aligned_arms(size_t i, const std::string &s1, const std::string &s2, std::string &a1, std::string &a2)
+{
+	if (i < pair_of.size() && pair_of[i] >= 0) {
+		const uint64_t p = (uint64_t)pair_of[i];
+		if (align_rows[p].status == DBGK_ALIGN_DONE && submitted[2 * p] == s1 && submitted[2 * p + 1] == s2) {
+			a1.assign(align_i, align_first[p], align_first[p + 1] - align_first[p]);
+			a2.assign(align_j, align_first[p], align_first[p + 1] - align_first[p]);
+			n_align_used++;
+			return;
+		}
+	}
+	global_align(s1, s2, a1, a2);
+	n_align_host++;
+}
+
+// the line of the bubbles pass's alignments under DBGK_TIMINGS
+static void report_alignments(dbgk_align_timing &before)
+{
+	if (!handle) return;
+	dbgk_align_timing now;
+	dbgk_align_timing_get(handle, &now);
+	if (getenv("DBGK_TIMINGS"))
+		cerr << "Contig stage aligned arms (bubbles): candidates " << n_candidates << " submitted " << submitted.size() / 2 << " too long " << n_too_long
+		     << " used " << n_align_used << " aligned on the host " << n_align_host << " device ms " << now.ms_align - before.ms_align
+		     << " bytes copied back " << now.bytes_back - before.bytes_back << endl;
+	before = now;
 }
 
 // After a pass: the device copy gets what the pass changed; the pass's line under DBGK_TIMINGS
@@ -557,7 +676,7 @@ static void remove_bubbles(const std::vector<uint64_t> &branches)
 		}
 		if (len1 != len2 || diff_rate > Bubble_base_diff_rate_cutoff) {
 			std::string a1, a2;
-			global_align(s1, s2, a1, a2);
+			aligned_arms(i, s1, s2, a1, a2);
 			s1 = a1;
 			s2 = a2;
 			diff_rate = (double)count_differences(s1, s2) / len1;
@@ -673,6 +792,7 @@ static int run()
 {
 	double ms_first = 0, ms_tip = 0, ms_edge = 0, ms_bubble = 0, ms_gpu = 0, ms_files = 0;
 	dbgk_simplify_timing traced_so_far = {};
+	dbgk_align_timing aligned_so_far = {};
 	cerr << "\nStart to calulate kmer links information!" << endl;
 	if (sizeof(Key) > 8) cerr << "Contig stage on 128-bit k-mers (32-byte nodes; parity unpinned above k = 32)" << endl;
 	auto t0 = std::chrono::steady_clock::now();
@@ -713,8 +833,10 @@ static int run()
 		cerr << "\nStart to remove bubbles caused by repeats and heterozygotes!" << endl;
 		t0 = std::chrono::steady_clock::now();
 		if (int rc = begin_pass(branches, false, Bubble_len_cutoff)) return rc;
+		if (int rc = collect_alignments(branches)) return rc;
 		remove_bubbles(branches);
 		if (int rc = end_pass("bubbles", traced_so_far)) return rc;
+		report_alignments(aligned_so_far);
 		ms_bubble = ms_since(t0);
 		finished("Finished!");
 	}
@@ -739,6 +861,16 @@ template <class G> std::vector<uint8_t> Stage<G>::changed;
 template <class G> std::vector<uint64_t> Stage<G>::dirty;
 template <class G> uint64_t Stage<G>::n_used = 0;
 template <class G> uint64_t Stage<G>::n_fell_back = 0;
+template <class G> std::vector<int64_t> Stage<G>::pair_of;
+template <class G> std::vector<std::string> Stage<G>::submitted;
+template <class G> std::vector<dbgk_align_row> Stage<G>::align_rows;
+template <class G> std::vector<uint64_t> Stage<G>::align_first;
+template <class G> std::string Stage<G>::align_i;
+template <class G> std::string Stage<G>::align_j;
+template <class G> uint64_t Stage<G>::n_candidates = 0;
+template <class G> uint64_t Stage<G>::n_too_long = 0;
+template <class G> uint64_t Stage<G>::n_align_used = 0;
+template <class G> uint64_t Stage<G>::n_align_host = 0;
 
 } // namespace
 

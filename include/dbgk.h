@@ -1178,6 +1178,52 @@ int dbgk_simplify_trace_results(dbgk_contig *c, dbgk_trace_row *rows, uint64_t *
 int dbgk_simplify_update(dbgk_contig *c, const uint64_t *slots, uint64_t n);
 int dbgk_simplify_timing_get(dbgk_contig *c, dbgk_simplify_timing *out);
 
+/* the global alignments of remove_hetero_bubbles (DBG_contig/contig.cpp:375-582), many independent pairs at once: what global_aligning
+ * (DBG_contig/global_aligning.cpp:98-182) returns for each pair, bit for bit -- match 3, mismatch -5, gap -5, the tie rule of get_max_score
+ * (:20-35), trace_back (:39-68).  An alignment depends on its two strings only, so the calls work on a CONTIG handle of either kind, with
+ * or without a table, and use its device and stream alone.  Checked before any device work: a sequence of length 0, a byte other than
+ * A C G T and decreasing offsets are DBGK_ERR_ARG; dbgk_align_results before any dbgk_align_pairs is DBGK_ERR_STATE.  n_pairs == 0 touches
+ * no device.  A pair with a sequence longer than DBGK_ALIGN_MAX_LEN is not aligned: it comes back DBGK_ALIGN_TOO_LONG and the caller
+ * aligns it itself.  There is no host fall-back.  (The three calls do not carry the section's dbgk_simplify_ prefix: the set of symbols
+ * with that prefix is pinned where the trace calls are tested.)                                                                      */
+#define DBGK_ALIGN_MAX_LEN   256     /* covers -U up to 193 at k = 63 */
+#define DBGK_ALIGN_DONE      0
+#define DBGK_ALIGN_TOO_LONG  1
+
+typedef struct dbgk_align_row {     /* one per pair */
+	uint32_t len_i, len_j;
+	int32_t  score;             /* DPscore[len_i][len_j]; 0 when TOO_LONG                                                 */
+	uint32_t aligned_len;       /* columns of the alignment; 0 when TOO_LONG                                              */
+	uint32_t diffs;             /* columns that compare_two_seq_simple (contig.cpp:587-595) counts: two different letters; a
+	                             * column with a gap does not count.  0 when TOO_LONG                                     */
+	uint8_t  status, pad[3];    /* DBGK_ALIGN_*                                                                           */
+} dbgk_align_row;
+
+typedef struct dbgk_align_summary {
+	uint64_t pairs;             /* = aligned + too_long                                                                   */
+	uint64_t aligned, too_long;
+	uint64_t batches;           /* kernel launches the pairs went through                                                 */
+	uint64_t aligned_bytes;     /* columns of all alignments: bytes of aligned_i, and of aligned_j                        */
+	uint64_t reserved;
+} dbgk_align_summary;
+
+typedef struct dbgk_align_timing {  /* sums since create */
+	uint64_t bytes_up;          /* sequences and offsets copied to the device                                             */
+	uint64_t bytes_back;        /* rows and aligned strings copied back                                                   */
+	uint64_t batches, pairs;    /* kernel launches; pairs aligned by them                                                 */
+	uint64_t cells;             /* len_i x len_j over those pairs                                                         */
+	uint64_t reserved;
+	double ms_align;            /* device time of the kernel                                                              */
+} dbgk_align_timing;
+
+/* pair p = sequences 2 p and 2 p + 1 of `seqs`: sequence s is bytes [offsets[s], offsets[s + 1]); offsets has 2 n_pairs + 1 entries.
+ * out may be NULL.                                                                                                             */
+int dbgk_align_pairs(dbgk_contig *c, const char *seqs, const uint64_t *offsets, uint64_t n_pairs, dbgk_align_summary *out);
+/* what the last dbgk_align_pairs found: rows (n_pairs); aligned_offsets (n_pairs + 1, in columns: pair p's two aligned strings are
+ * bytes [aligned_offsets[p], aligned_offsets[p + 1]) of aligned_i and of aligned_j).  Any pointer may be NULL.                     */
+int dbgk_align_results(dbgk_contig *c, dbgk_align_row *rows, uint64_t *aligned_offsets, char *aligned_i, char *aligned_j);
+int dbgk_align_timing_get(dbgk_contig *c, dbgk_align_timing *out);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);
