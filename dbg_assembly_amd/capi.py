@@ -288,6 +288,7 @@ SYMBOLS = [
     ("dbgk_link_stats_device", _i, [_vp, C.c_int32, C.POINTER(LinkStats)]),
     ("dbgk_wide_export_sorted", _i, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("dbgk_wide_export_host_table", _i, [_vp, _u64, _vp, _vp]),
+    ("dbgk_wide_export_host_table_links", _i, [_vp, _u64, _vp, _vp, C.c_int32, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _u64, C.POINTER(_u64), _vp]),
     ("dbgk_wide_partition_export", _i, [_vp, C.c_uint32, _vp, _u64, _vp]),
     ("dbgk_wide_merge_nodes", _i, [_vp, _vp, _u64]),
     ("dbgk_wide_pass_info", _i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
@@ -333,6 +334,7 @@ SYMBOLS = [
     ("dbgk_comm_export_host_table_links", _i, [_vp, _u64, _vp, _vp, C.c_int32, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _u64, C.POINTER(_u64), _vp]),
     ("dbgk_comm_wide_export_sorted", _i, [_vp, _vp, _u64, C.POINTER(_u64)]),
     ("dbgk_comm_wide_export_host_table", _i, [_vp, _u64, _vp, _vp]),
+    ("dbgk_comm_wide_export_host_table_links", _i, [_vp, _u64, _vp, _vp, C.c_int32, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _u64, C.POINTER(_u64), _vp]),
     ("dbgk_comm_kfreq_export_counts", _i, [_vp, _u64, _u64, _vp]),
     ("dbgk_comm_kfreq_export_bits", _i, [_vp, C.c_uint32, _u64, _u64, _vp]),
     ("dbgk_synth_reads_device", _i, [_vp, C.POINTER(SynthParams), _u64, _u64, _vp, _vp]),
@@ -751,6 +753,23 @@ class Graph:
         _chk(lib().dbgk_wide_export_host_table(self._h, size, array.ctypes.data, flags.ctypes.data), "dbgk_wide_export_host_table")
         return array, flags
 
+    def wide_export_host_table_links(self, cutoff=2, size=None):
+        """dbgk_wide_export_host_table + the consumer's whole first pass for that table (k_wide_kmer_links on the device table, the
+        nodes placed on the host patched in): -> (array, nul_flag, klink u16[size], del_flag, tip slots, branch slots, LinkStats)"""
+        size = self.table_slots if size is None else int(size)
+        array = np.zeros(size, dtype=NODE32_DTYPE)
+        flags = np.zeros(size // 8 + 1, dtype=np.uint8)
+        klink = np.zeros(size, dtype=np.uint16)
+        dele = np.zeros(size // 8 + 1, dtype=np.uint8)
+        cap = int(self.stats.count)
+        tips, branches = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint64)
+        nt, nb = C.c_uint64(), C.c_uint64()
+        st = LinkStats()
+        _chk(lib().dbgk_wide_export_host_table_links(self._h, size, array.ctypes.data, flags.ctypes.data, cutoff, klink.ctypes.data, dele.ctypes.data,
+                                                     tips.ctypes.data, cap, C.byref(nt), branches.ctypes.data, cap, C.byref(nb), C.byref(st)),
+             "dbgk_wide_export_host_table_links")
+        return array, flags, klink, dele, tips[:nt.value], branches[:nb.value], st
+
     def wide_partition_export(self, n_parts, d_nodes=None, capacity=0):
         counts = np.zeros(n_parts, np.uint64)
         _chk(lib().dbgk_wide_partition_export(self._h, n_parts, d_nodes, capacity, counts.ctypes.data), "dbgk_wide_partition_export")
@@ -995,6 +1014,22 @@ class Comm:
         flags = np.zeros(size // 8 + 1, dtype=np.uint8)
         _chk(lib().dbgk_comm_wide_export_host_table(self._c, size, array.ctypes.data, flags.ctypes.data), "dbgk_comm_wide_export_host_table")
         return array, flags
+
+    def wide_export_host_table_links(self, cutoff=2):
+        """dbgk_comm_wide_export_host_table_links -> (array, nul_flag, klink u16[size], del_flag, tip slots, branch slots, LinkStats)"""
+        size = self.table_slots
+        array = np.zeros(size, dtype=NODE32_DTYPE)
+        flags = np.zeros(size // 8 + 1, dtype=np.uint8)
+        klink = np.zeros(size, dtype=np.uint16)
+        dele = np.zeros(size // 8 + 1, dtype=np.uint8)
+        cap = int(self.stats.count)
+        tips, branches = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint64)
+        nt, nb = C.c_uint64(), C.c_uint64()
+        st = LinkStats()
+        _chk(lib().dbgk_comm_wide_export_host_table_links(self._c, size, array.ctypes.data, flags.ctypes.data, cutoff, klink.ctypes.data, dele.ctypes.data,
+                                                          tips.ctypes.data, cap, C.byref(nt), branches.ctypes.data, cap, C.byref(nb), C.byref(st)),
+             "dbgk_comm_wide_export_host_table_links")
+        return array, flags, klink, dele, tips[:nt.value], branches[:nb.value], st
 
     # ---- a communicator of frequency tables (engine=ENGINE_KFREQ)
     def kfreq_counts(self, first=0, n=None):

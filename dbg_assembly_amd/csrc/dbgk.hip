@@ -13,6 +13,7 @@
 #include <chrono>
 #include <cmath>
 #include <emmintrin.h>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -22,6 +23,7 @@
 #include "dbgk_kernels.h"
 #include "dbgk_partition.h"
 #include "dbgk_wide_kernels.h"
+#include "dbgk_wide_links_patch.h"
 #include "dbgk_wide_partition.h"
 #include "dbgk_correct.h"
 #include "dbgk_map.h"
@@ -457,6 +459,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_engines.h"
 #include "dbgk_host_misc.h"
 #include "dbgk_comm.h"
+#include "dbgk_host_wide_links.h"
 #include "dbgk_host_correct.h"
 #include "dbgk_host_map.h"
 #include "dbgk_host_clean.h"

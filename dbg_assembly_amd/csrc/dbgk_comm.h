@@ -1134,7 +1134,7 @@ extern "C" int dbgk_comm_wide_export_sorted(dbgk_comm *c, dbgk_node32 *out, uint
 // the host table of the whole job (host_size == the global table size): the shards' slices side by side, then the nodes that
 // live outside the table on the devices (zero low word, key 0) put on their probe chains by add_node_to_kmerset's rule
 // (kmerSet.cpp:253-273) -- the contract of dbgk_wide_export_host_table for ONE table over several GPUs
-extern "C" int dbgk_comm_wide_export_host_table(dbgk_comm *c, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag)
+static int comm_wide_export_host_table_impl(dbgk_comm *c, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag, std::vector<PlacedNode> *placed)
 {
 	if (!c || !array || !nul_flag) return DBGK_ERR_ARG;
 	if (!c->finalized || !c->wide) return DBGK_ERR_STATE;
@@ -1156,14 +1156,11 @@ extern "C" int dbgk_comm_wide_export_host_table(dbgk_comm *c, uint64_t host_size
 	std::vector<WNode> side(kWideSideSlots);
 	HIPCHK(hipMemcpyAsync(side.data(), h0->wside, kWideSideSlots * sizeof(WNode), hipMemcpyDeviceToHost, h0->stream));
 	HIPCHK(hipStreamSynchronize(h0->stream));
-	auto place = [&](dbgk_node32 nd) {
-		uint64_t hc = dbgk_wide::hash128(dbgk_wide::Key128{nd.kmer_hi, nd.kmer_lo}) % host_size;
-		while (nul_flag[hc >> 3] & (uint8_t)(128u >> (hc & 7u))) hc = (hc + 1 == host_size) ? 0 : hc + 1;
-		array[hc] = nd;
-		nul_flag[hc >> 3] |= (uint8_t)(128u >> (hc & 7u));
-	};
-	for (const WNode &sd : side)
-		if (sd.hi1) place(dbgk_node32{sd.hi1 - 1ull, 0ull, (uint32_t)sd.links, (uint32_t)(sd.links >> 32), 0});
-	place(dbgk_node32{0, 0, tot.polyA_l_link, tot.polyA_r_link, 0}); // DBGgraph.cpp:418
+	wide_place_outside_nodes(side, tot.polyA_l_link, tot.polyA_r_link, host_size, array, nul_flag, placed);
 	return DBGK_OK;
+}
+
+extern "C" int dbgk_comm_wide_export_host_table(dbgk_comm *c, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag)
+{
+	return comm_wide_export_host_table_impl(c, host_size, array, nul_flag, nullptr);
 }

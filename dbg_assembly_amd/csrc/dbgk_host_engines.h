@@ -136,10 +136,27 @@ extern "C" int dbgk_wide_export_sorted(dbgk_handle *h, dbgk_node32 *out, uint64_
 	return DBGK_OK;
 }
 
+// the nodes of a WIDE table that live outside it on the device, put on their probe chains in the host image.
+// `placed` (optional): slot and link words of every node put on its chain here, for the link pass (dbgk_wide_links_patch.h)
+static void wide_place_outside_nodes(const std::vector<WNode> &side, uint32_t polyA_l_link, uint32_t polyA_r_link, uint64_t host_size, dbgk_node32 *array,
+                                     uint8_t *nul_flag, std::vector<PlacedNode> *placed)
+{
+	auto place = [&](dbgk_node32 nd) { // add_node_to_kmerset's rule (kmerSet.cpp:253-273): first slot without a flag on the key's chain
+		uint64_t hc = dbgk_wide::hash128(dbgk_wide::Key128{nd.kmer_hi, nd.kmer_lo}) % host_size;
+		while (nul_flag[hc >> 3] & (uint8_t)(128u >> (hc & 7u))) hc = (hc + 1 == host_size) ? 0 : hc + 1;
+		array[hc] = nd;
+		nul_flag[hc >> 3] |= (uint8_t)(128u >> (hc & 7u));
+		if (placed) placed->push_back(PlacedNode{hc, (uint64_t)nd.l_link | ((uint64_t)nd.r_link << 32)});
+	};
+	for (const WNode &s : side)
+		if (s.hi1) place(dbgk_node32{s.hi1 - 1ull, 0ull, (uint32_t)s.links, (uint32_t)(s.links >> 32), 0});
+	place(dbgk_node32{0, 0, polyA_l_link, polyA_r_link, 0}); // DBGgraph.cpp:418
+}
+
 // host-layout table of host_size == table_slots 32-byte nodes + nul_flag: every key reachable by linear probing from
 // hash128(key) % size without crossing a clear flag.  The few nodes that live outside the main table on the
 // device (keys whose low word is 0, the key-0 node) are put on their probe chains here, on the host.
-extern "C" int dbgk_wide_export_host_table(dbgk_handle *h, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag)
+static int wide_export_host_table_impl(dbgk_handle *h, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag, std::vector<PlacedNode> *placed)
 {
 	if (!h || !array || !nul_flag) return DBGK_ERR_ARG;
 	if (!h->wide || !h->finalized) return DBGK_ERR_STATE;
@@ -168,16 +185,13 @@ extern "C" int dbgk_wide_export_host_table(dbgk_handle *h, uint64_t host_size, d
 	(void)hipFree(d_flags);
 	if (e != hipSuccess) return hip_fail(e, "wide_export_host_table", __LINE__);
 	if (h->sharded) return DBGK_OK; // a shard's slice as it is: side-table nodes and the key-0 node are placed over the WHOLE table by the caller
-	auto place = [&](dbgk_node32 nd) { // add_node_to_kmerset's rule (kmerSet.cpp:253-273): first slot without a flag on the key's chain
-		uint64_t hc = dbgk_wide::hash128(dbgk_wide::Key128{nd.kmer_hi, nd.kmer_lo}) % host_size;
-		while (nul_flag[hc >> 3] & (uint8_t)(128u >> (hc & 7u))) hc = (hc + 1 == host_size) ? 0 : hc + 1;
-		array[hc] = nd;
-		nul_flag[hc >> 3] |= (uint8_t)(128u >> (hc & 7u));
-	};
-	for (const WNode &s : side)
-		if (s.hi1) place(dbgk_node32{s.hi1 - 1ull, 0ull, (uint32_t)s.links, (uint32_t)(s.links >> 32), 0});
-	place(dbgk_node32{0, 0, (uint32_t)(h->h_ctr->polyA_links & 0xFFFFFFFFu), (uint32_t)(h->h_ctr->polyA_links >> 32), 0}); // DBGgraph.cpp:418
+	wide_place_outside_nodes(side, (uint32_t)(h->h_ctr->polyA_links & 0xFFFFFFFFu), (uint32_t)(h->h_ctr->polyA_links >> 32), host_size, array, nul_flag, placed);
 	return DBGK_OK;
+}
+
+extern "C" int dbgk_wide_export_host_table(dbgk_handle *h, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag)
+{
+	return wide_export_host_table_impl(h, host_size, array, nul_flag, nullptr);
 }
 
 // several GPUs with 128-bit keys: nodes grouped by owner, merged by the owner (dbgk_partition_* / dbgk_merge_nodes for

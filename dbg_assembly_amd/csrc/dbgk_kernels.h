@@ -19,6 +19,7 @@
 #pragma once
 
 #include "dbgk_device.h"
+#include "dbgk_link_record.h"
 
 namespace dbgk {
 
@@ -1001,28 +1002,7 @@ __global__ __launch_bounds__(kBlock) void k_link_stats(const Node *__restrict__ 
 // ---------------------------------------------------------------------------------------------
 constexpr int kLinkChunk = 4096; // slots per block: 16 sweeps of 256 threads
 
-__device__ __forceinline__ uint32_t kmer_link_record(uint64_t links, int cutoff)
-{
-	// contig.cpp:129-163: a side's link number = counters above the cutoff (at most 3: a 2-bit field), its base = the FIRST
-	// base with the largest such counter (strict <), 0 when there is none
-	uint32_t rec = 0;
-#pragma unroll
-	for (int side = 0; side < 2; side++) {
-		const uint32_t w = side ? (uint32_t)(links >> 32) : (uint32_t)links;
-		int num = 0, best = 0, base = 0;
-#pragma unroll
-		for (int j = 0; j < 4; j++) {
-			const int d = (int)((w >> (24 - 8 * j)) & 0xFFu); // get_next_kmer_depth (kmerSet.cpp:341-344): A in bits 31..24
-			if (d > cutoff) {
-				if (num < 3) num++;
-				if (best < d) { best = d; base = j; }
-			}
-		}
-		rec |= ((uint32_t)num | ((uint32_t)base << 2)) << (4 * side);
-	}
-	if ((rec & 3u) == 1u && ((rec >> 4) & 3u) == 1u) rec |= 1u << 8; // linear: exactly one link on each side (:170-173)
-	return rec;
-}
+// kmer_link_record(links, cutoff): dbgk_link_record.h (shared with host code that has no HIP)
 
 template <int PASS>
 __global__ __launch_bounds__(kBlock) void k_kmer_links(const Node *__restrict__ nodes, uint64_t size, const Counters *__restrict__ ctr, int cutoff,

@@ -302,6 +302,92 @@ __global__ __launch_bounds__(kBlock) void k_wide_link_stats(const WNode *__restr
 	}
 }
 
+// The WHOLE first pass of the consumer (calculate_kmer_links, contig.cpp:107-181) on the wide table in place: k_kmer_links for
+// 32-byte nodes, same geometry and contract (one block owns kLinkChunk consecutive slots; PASS 0 writes klink[i] for every
+// i < size, the del_flag bytes, DepthStat / class counts and the block's tip and branch counts; the host prefix-sums those; PASS 1
+// writes the two lists in ascending slot order).  A slot is occupied iff lo != 0; of a node only `lo` and `links` are loaded, 16
+// adjacent bytes.  Nodes outside the table (side table, key 0) are the host's (dbgk_wide_links_patch.h).  Listed slot numbers
+// are slot_base + i: a shard's slots counted in the whole table.
+typedef unsigned long long WLoLinks __attribute__((ext_vector_type(2), aligned(8))); // {lo, links}: one 16-byte load at the node's second word
+
+template <int PASS>
+__global__ __launch_bounds__(kBlock) void k_wide_kmer_links(const WNode *__restrict__ nodes, uint64_t size, int cutoff, uint64_t slot_base,
+                                                            uint16_t *__restrict__ klink, uint8_t *__restrict__ del_flag,
+                                                            unsigned long long *__restrict__ stats, uint32_t *__restrict__ block_counts,
+                                                            const unsigned long long *__restrict__ block_base, unsigned long long *__restrict__ tips,
+                                                            unsigned long long *__restrict__ branches)
+{
+	__shared__ unsigned int hist[256];
+	__shared__ unsigned long long red[kBlock / 64];
+	__shared__ unsigned int wave_cnt[2][kBlock / 64];
+	__shared__ unsigned long long run[2];
+	const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+	if (PASS == 0) hist[t] = 0; // kBlock == 256
+	if (t == 0) {
+		run[0] = PASS ? block_base[2 * blockIdx.x] : 0ull;
+		run[1] = PASS ? block_base[2 * blockIdx.x + 1] : 0ull;
+	}
+	__syncthreads();
+	unsigned long long cls[5] = {0, 0, 0, 0, 0};
+	const uint64_t first = (uint64_t)blockIdx.x * kLinkChunk;
+	for (int sweep = 0; sweep < kLinkChunk / kBlock; sweep++) {
+		const uint64_t i = first + (uint64_t)sweep * kBlock + t;
+		bool occ = false;
+		uint32_t rec = 0;
+		if (i < size) {
+			const WLoLinks v = *reinterpret_cast<const WLoLinks *>(&nodes[i].lo);
+			const uint64_t links = v.y;
+			occ = v.x != 0ull;
+			if (occ) {
+				rec = kmer_link_record(links, cutoff);
+				if (PASS == 0) link_classes(links, cutoff, hist, cls);
+			}
+		}
+		const uint32_t ln = rec & 3u, rn = (rec >> 4) & 3u;
+		const bool del = occ && ln == 0u && rn == 0u, tip = occ && ln + rn == 1u, branch = occ && (ln > 1u || rn > 1u);
+		if (PASS == 0) {
+			if (i < size) klink[i] = (uint16_t)rec;
+			// del_flag byte of 8 consecutive slots, bit of slot i = 128 >> (i % 8): lanes 8b .. 8b+7 of the wave's ballot
+			const unsigned long long m = __ballot(del);
+			if ((lane & 7u) == 0u && i < size) {
+				const uint32_t bits = (uint32_t)(m >> lane) & 0xFFu;
+				del_flag[i >> 3] = (uint8_t)(__brev(bits) >> 24);
+			}
+		}
+		// ordered positions: threads in slot order inside a sweep, sweeps in order
+		const unsigned long long mt = __ballot(tip), mb = __ballot(branch);
+		const unsigned long long below = (1ull << lane) - 1ull;
+		if (lane == 0u) {
+			wave_cnt[0][wave] = (unsigned int)__popcll(mt);
+			wave_cnt[1][wave] = (unsigned int)__popcll(mb);
+		}
+		__syncthreads();
+		if (PASS == 1) {
+			unsigned long long bt = run[0], bb = run[1];
+			for (uint32_t w = 0; w < wave; w++) { bt += wave_cnt[0][w]; bb += wave_cnt[1][w]; }
+			if (tip) tips[bt + (unsigned long long)__popcll(mt & below)] = slot_base + i;
+			if (branch) branches[bb + (unsigned long long)__popcll(mb & below)] = slot_base + i;
+		}
+		__syncthreads();
+		if (t == 0) {
+			for (uint32_t w = 0; w < kBlock / 64; w++) { run[0] += wave_cnt[0][w]; run[1] += wave_cnt[1][w]; }
+		}
+		__syncthreads();
+	}
+	if (PASS == 0) {
+		if (t == 0) {
+			block_counts[2 * blockIdx.x] = (uint32_t)run[0];
+			block_counts[2 * blockIdx.x + 1] = (uint32_t)run[1];
+		}
+		if (hist[t]) atomicAdd(&stats[t], (unsigned long long)hist[t]);
+#pragma unroll
+		for (int c = 0; c < 5; c++) {
+			const unsigned long long s = block_sum(cls[c], red);
+			if (t == 0 && s) atomicAdd(&stats[256 + c], s);
+		}
+	}
+}
+
 // ---- several GPUs: nodes grouped by owner = (hash128(key) >> 32) % n_parts, merged by the owner ----------------
 // (the flow of dbgk_partition_export / dbgk_merge_nodes for 32-byte nodes: every GPU builds the graph of its share
 // of the reads, ships each node to its owner, the owner adds the counters up -- exact for any split of the input

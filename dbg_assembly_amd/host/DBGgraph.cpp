@@ -705,8 +705,34 @@ static void build_debruijn_graph_wide(vector<string> &reads_files, Session *S, u
 			free(array), free(nul), free(del);
 			fail(*S, DBGK_ERR_NOMEM, "host table allocation");
 		} else {
-			rc = S->comm ? dbgk_comm_wide_export_host_table(S->comm, initial_size, reinterpret_cast<dbgk_node32 *>(array), nul)
-			             : dbgk_wide_export_host_table(S->h, initial_size, reinterpret_cast<dbgk_node32 *>(array), nul);
+			const bool links = getenv("DBGK_LINKS") && atoi(getenv("DBGK_LINKS")) != 0;
+			free(DbgkKmerLinks); // (of an earlier build in this process: another table)
+			DbgkKmerLinks = NULL;
+			if (links) { // the consumer's first pass on the device, for exactly this table (as for 16-byte nodes below)
+				dbgk_node32 *nodes = reinterpret_cast<dbgk_node32 *>(array);
+				DbgkKmerLinks = static_cast<uint16_t *>(malloc(initial_size * sizeof(uint16_t)));
+				DbgkTipNodes.assign(st.count ? st.count : 1, 0);
+				DbgkBranchNodes.assign(st.count ? st.count : 1, 0);
+				uint64_t nt = 0, nb = 0;
+				const int cutoff = &KmerFreqCutoff ? KmerFreqCutoff : 2;
+				if (!DbgkKmerLinks) rc = DBGK_ERR_NOMEM;
+				else if (S->comm) // several GPU shards: the pass per shard on its slot range
+					rc = dbgk_comm_wide_export_host_table_links(S->comm, initial_size, nodes, nul, cutoff, DbgkKmerLinks, del, DbgkTipNodes.data(),
+					                                            DbgkTipNodes.size(), &nt, DbgkBranchNodes.data(), DbgkBranchNodes.size(), &nb, NULL);
+				else
+					rc = dbgk_wide_export_host_table_links(S->h, initial_size, nodes, nul, cutoff, DbgkKmerLinks, del, DbgkTipNodes.data(), DbgkTipNodes.size(), &nt,
+					                                       DbgkBranchNodes.data(), DbgkBranchNodes.size(), &nb, NULL);
+				DbgkTipNodes.resize(rc == DBGK_OK ? nt : 0);
+				DbgkBranchNodes.resize(rc == DBGK_OK ? nb : 0);
+				if (rc == DBGK_OK) cerr << "First pass of the contig stage done on the GPU: " << nt << " tip nodes, " << nb << " branching nodes" << endl;
+				else {
+					free(DbgkKmerLinks);
+					DbgkKmerLinks = NULL;
+				}
+			} else {
+				rc = S->comm ? dbgk_comm_wide_export_host_table(S->comm, initial_size, reinterpret_cast<dbgk_node32 *>(array), nul)
+				             : dbgk_wide_export_host_table(S->h, initial_size, reinterpret_cast<dbgk_node32 *>(array), nul);
+			}
 			if (rc != DBGK_OK) {
 				free(array), free(nul), free(del);
 				fail(*S, rc, "dbgk_wide_export_host_table");
@@ -903,8 +929,9 @@ void build_debruijn_graph(vector<string> &reads_files)
 				fail(*S, DBGK_ERR_NOMEM, "host table allocation");
 			} else {
 				const bool links = getenv("DBGK_LINKS") && atoi(getenv("DBGK_LINKS")) != 0;
+				free(DbgkKmerLinks); // (of an earlier build in this process: another table)
+				DbgkKmerLinks = NULL;
 				if (links) { // the consumer's first pass on the device, for exactly this table
-					free(DbgkKmerLinks);
 					DbgkKmerLinks = static_cast<uint16_t *>(malloc(use_size * sizeof(uint16_t)));
 					DbgkTipNodes.assign(st.count ? st.count : 1, 0);
 					DbgkBranchNodes.assign(st.count ? st.count : 1, 0);
@@ -983,13 +1010,17 @@ int write_kmer_freq_file(const string &path, int kmer_freq_cutoff)
 int write_links_dump(const string &path)
 {
 	// what DBGK_LINKS=1 left behind: `K slot record(hex) deleted` for every occupied slot, then `T slot` / `B slot` lines
-	if (!kset || !DbgkKmerLinks) return DBGK_ERR_STATE;
+	// (after a build with -k 33..63: of kset_wide)
+	const bool wide = KmerSize > 32;
+	if ((wide ? !kset_wide : !kset) || !DbgkKmerLinks) return DBGK_ERR_STATE;
+	const uint64_t size = wide ? kset_wide->size : kset->size;
+	uint8_t *nul = wide ? kset_wide->nul_flag : kset->nul_flag, *del = wide ? kset_wide->del_flag : kset->del_flag;
 	FILE *fp = fopen(path.c_str(), "w");
 	if (!fp) return DBGK_ERR_ARG;
-	fprintf(fp, "#size %llu tips %llu branches %llu\n", (unsigned long long)kset->size, (unsigned long long)DbgkTipNodes.size(),
+	fprintf(fp, "#size %llu tips %llu branches %llu\n", (unsigned long long)size, (unsigned long long)DbgkTipNodes.size(),
 	        (unsigned long long)DbgkBranchNodes.size());
-	for (uint64_t i = 0; i < kset->size; i++)
-		if (!is_entity_null(kset->nul_flag, i)) fprintf(fp, "K\t%llu\t%04x\t%d\n", (unsigned long long)i, DbgkKmerLinks[i], is_entity_delete(kset->del_flag, i));
+	for (uint64_t i = 0; i < size; i++)
+		if (!is_entity_null(nul, i)) fprintf(fp, "K\t%llu\t%04x\t%d\n", (unsigned long long)i, DbgkKmerLinks[i], is_entity_delete(del, i));
 	for (uint64_t v : DbgkTipNodes) fprintf(fp, "T\t%llu\n", (unsigned long long)v);
 	for (uint64_t v : DbgkBranchNodes) fprintf(fp, "B\t%llu\n", (unsigned long long)v);
 	fclose(fp);

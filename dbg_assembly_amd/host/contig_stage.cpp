@@ -797,11 +797,11 @@ static int run()
 	if (sizeof(Key) > 8) cerr << "Contig stage on 128-bit k-mers (32-byte nodes; parity unpinned above k = 32)" << endl;
 	auto t0 = std::chrono::steady_clock::now();
 	std::vector<uint64_t> tips, branches;
-	if (DbgkKmerLinks) {             // the first pass came with the table, computed on the device (dbgk_export_host_table_links)
+	if (DbgkKmerLinks) {             // the first pass came with the table, computed on the device (dbgk_export_host_table_links, dbgk_wide_export_host_table_links)
 		klink = DbgkKmerLinks;
 		tips.swap(DbgkTipNodes);
 		branches.swap(DbgkBranchNodes);
-	} else {                         // a table laid out on the host (DBGK_LAYOUT=ref): its slots are not the device table's, so the same pass here.
+	} else {                         // a table laid out on the host (DBGK_LAYOUT=ref: its slots are not the device table's) or DBGK_LINKS=0: the same pass here.
 		                                 // The records live until the program leaves (main.cpp leaves through _exit): never freed
 		klink = static_cast<uint16_t *>(calloc(G::size(), sizeof(uint16_t)));
 		if (!klink) return DBGK_ERR_NOMEM;

@@ -11,7 +11,8 @@
 // runs on `kset` as build_debruijn_graph() left it (k <= 31); 0, or a DBGK_ERR_* code of the GPU read-out
 int run_contig_stage();
 // the same stage on `kset_wide` (k = 33..63, 128-bit k-mers; PARITY UNPINNED above k = 32: the reference stops at 31).  The first
-// pass runs on the host; the stage says on stderr that it is the one on 128-bit k-mers
+// pass comes with the table from the device (dbgk_wide_export_host_table_links) unless DBGK_LINKS=0 keeps it on the host; the stage
+// says on stderr that it is the one on 128-bit k-mers
 int run_contig_stage_wide();
 // test hook contig_wide (k <= 31): copies `kset` into `kset_wide` with a high word of 0, slot for slot, and runs the wide stage on it.
 // Every 128-bit rule is then the reference's 64-bit one, so the files must be the reference's: what anchors the wide stage

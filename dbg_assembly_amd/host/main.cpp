@@ -74,7 +74,7 @@ static void usage()
 	     << "                DBGK_ENGINE=1|2   1 = global-atomic insert, 2 = partitioned records + LDS-built table regions (default)" << endl
 	     << "                DBGK_STORE_KMERS=<n>  k-mer occurrences the partitioned engine holds before merging them into the table" << endl
 	     << "                DBGK_LAYOUT=ref   lay the hash table out slot for slot like `debruijn_contig -t 1` of the reference" << endl
-	     << "                DBGK_LINKS=1      also run the contig stage's first pass (link records, delete flags, tip / branch lists) on the GPU" << endl
+	     << "                DBGK_LINKS=1      also run the contig stage's first pass (link records, delete flags, tip / branch lists) on the GPU; 0 = on the host" << endl
 	     << "                DBGK_GPUS=<n> | DBGK_GPU_LIST=a,b,..   one table over several GPUs;  DBGK_WIDE_PASSES=<n>  (-k > 32) passes over the input" << endl
 	     << "\nExample: \ndebruijn_contig  -k 31 -r 250  -t 10  -i 0.1  -M 125 -o Ecoli reads_files.lib   2> reads_files.debruijn_contig.log \n" << endl;
 	exit(0);
@@ -134,11 +134,15 @@ int main(int argc, char *argv[])
 	vector<string> reads_files;
 	reading_file_list(reads_lib_file, reads_files);
 
-	// this build's contig stage takes the first pass (link records, delete flags, tip / branch lists) from the device with the table;
-	// a table laid out like the reference's (DBGK_LAYOUT=ref) is made on the host, and the stage makes the pass there
+	// this build's contig stage takes the first pass (link records, delete flags, tip / branch lists) from the device with the table,
+	// for 16-byte nodes and, above k = 32, for 32-byte ones (DBGK_LINKS=0 keeps the pass on the host); a table laid out like the
+	// reference's (DBGK_LAYOUT=ref) is made on the host, and the stage makes the pass there
 	const char *layout = getenv("DBGK_LAYOUT");
 	const bool own_contig_stage = KmerSize <= 31 && !build_contig_sequence;
-	if (own_contig_stage && !(layout && !strcmp(layout, "ref"))) setenv("DBGK_LINKS", "1", 0);
+	// (the wide stage takes tables below 2^32 - 1 entries; a larger one stops after the graph stage and has no use for the pass)
+	const uint64_t wanted = (uint64_t)(initHashSize * 1000000000);
+	const bool own_wide_stage = KmerSize > 32 && KmerSize <= 63 && (wanted < 3 ? 3 : find_next_prime(wanted)) < 0xffffffffull;
+	if ((own_contig_stage && !(layout && !strcmp(layout, "ref"))) || own_wide_stage) setenv("DBGK_LINKS", "1", 0);
 
 	const double t_build0 = wall_now();
 	build_debruijn_graph(reads_files);

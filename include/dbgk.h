@@ -313,6 +313,13 @@ int dbgk_wide_export_sorted(dbgk_handle *h, dbgk_node32 *out, uint64_t capacity,
  * reachable by linear probing from hash128(key) % host_size without crossing a clear flag, unused slots all-zero,
  * the key-0 node on key 0's chain -- the invariants of SURVEY 8(b) with the 128-bit hash                      */
 int dbgk_wide_export_host_table(dbgk_handle *h, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag);
+/* dbgk_wide_export_host_table + the consumer's whole first pass for that table: dbgk_export_host_table_links for 32-byte nodes.
+ * Same arguments, optional outputs, DBGK_ERR_CAPACITY and result layout; host_size == table_slots.  The pass reads the device
+ * table in place; the nodes the host puts on their chains afterwards (zero low word, key 0) are added on the host.  Unsharded
+ * WIDE handles (others: DBGK_ERR_STATE).  PARITY UNPINNED above k = 32.  (ABI 7, appended)                                     */
+int dbgk_wide_export_host_table_links(dbgk_handle *h, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag, int32_t kmer_freq_cutoff,
+                                      uint16_t *klink, uint8_t *del_flag, uint64_t *tip_nodes, uint64_t tip_capacity, uint64_t *n_tips,
+                                      uint64_t *branch_nodes, uint64_t branch_capacity, uint64_t *n_branches, dbgk_link_stats *stats);
 /* several GPUs: every GPU builds the graph of its share of the reads (reads shard by record), then ships each node to
  * its owner, (hash128(key) >> 32) % n_parts -- the device analogue of the reference's `kmer % threadNum` ownership
  * (DBGgraph.cpp:148) -- which adds the counters up (per-byte saturating, exact for any split of the input).
@@ -518,6 +525,11 @@ int dbgk_comm_export_host_table_links(dbgk_comm *c, uint64_t host_size, dbgk_nod
  * dbgk_wide_begin_pass), the record stores are built at dbgk_comm_finalize.  Results of the whole job:                          */
 int dbgk_comm_wide_export_sorted(dbgk_comm *c, dbgk_node32 *out, uint64_t capacity, uint64_t *n_out);
 int dbgk_comm_wide_export_host_table(dbgk_comm *c, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag);
+/* dbgk_wide_export_host_table_links for the shards of one table: the pass runs per shard on its slot range, slot numbers are those
+ * of the whole table, lists ascending over all shards.  (ABI 7, appended)                                                       */
+int dbgk_comm_wide_export_host_table_links(dbgk_comm *c, uint64_t host_size, dbgk_node32 *array, uint8_t *nul_flag, int32_t kmer_freq_cutoff,
+                                           uint16_t *klink, uint8_t *del_flag, uint64_t *tip_nodes, uint64_t tip_capacity, uint64_t *n_tips,
+                                           uint64_t *branch_nodes, uint64_t branch_capacity, uint64_t *n_branches, dbgk_link_stats *stats);
 /* cfg->engine == DBGK_ENGINE_KFREQ: a communicator of n whole frequency tables.  Every member counts the reads
  * dealt to it; dbgk_comm_finalize makes member d the owner of an n-th of the k-mer values and adds the other
  * members' slices of that range to its own (peer copies in chunks, overlapped with the saturating add).  The
