@@ -32,9 +32,11 @@ class Table:
         return v < self.total and (self.bits[v >> 3] >> (7 - (v & 7))) & 1 == 1
 
 
-def _tree(read, T, P, start, end, rightward, modify, max_change, last_pos):
+def _tree(read, T, P, start, end, rightward, modify, max_change, last_pos, observe=None):
     """correct_multi_bases_rightward / _leftward on a frontier of (ctx, change, edits).
-    Returns (num_corrected, len_need_trim, last_pos, node_limit_hit)."""
+    Returns (num_corrected, len_need_trim, last_pos, node_limit_hit).  observe: a list that gets one dict per tree --
+    its direction and span, the sizes of the frontiers it accepted and the cumulative node count after every cycle it
+    expanded (the last one is the cycle that was discarded, if any)."""
     k = P.k
     km1 = (1 << (2 * (k - 1))) - 1
     full = (1 << (2 * k)) - 1
@@ -47,6 +49,9 @@ def _tree(read, T, P, start, end, rightward, modify, max_change, last_pos):
     front = [(root, 0, ())]
     nodes, cyc, depth, hit = 0, start, 0, 0
     step = 1 if rightward else -1
+    seen = {"right": bool(rightward), "start": start, "end": end, "modify": modify, "frontiers": [], "cum": []}
+    if observe is not None:
+        observe.append(seen)
     while (cyc <= end) if rightward else (cyc >= end):
         here = read[cyc - 1]
         new = []
@@ -63,8 +68,10 @@ def _tree(read, T, P, start, end, rightward, modify, max_change, last_pos):
                 if T.hi(km) and nch <= max_change:
                     new.append((nctx, nch, ed if same else ed + ((cyc, BASES[j]),)))
         nodes += len(new)
+        seen["cum"].append(nodes)
         if new and nodes < P.n:
             front = new
+            seen["frontiers"].append(len(new))
         else:
             hit = int(nodes >= P.n)
             break
@@ -103,8 +110,9 @@ def _runs(mask, want):
     return out
 
 
-def correct_one_read(seq, T, P):
-    """-> (corrected full-length read bytes, one_base, multi, deleted, left_trim, right_trim, node_limit_hits)"""
+def correct_one_read(seq, T, P, observe=None):
+    """-> (corrected full-length read bytes, one_base, multi, deleted, left_trim, right_trim, node_limit_hits);
+    observe: see _tree"""
     k = P.k
     read = bytearray(seq)
     L = len(read)
@@ -146,13 +154,13 @@ def correct_one_read(seq, T, P):
         if accum >= P.c:
             fails.extend(range(i, len(regs) - 1))
             break
-        nc, tr, _, h = _tree(read, T, P, regs[i][1] + k, regs[i + 1][0] + k - 2, True, 0, P.c - accum, -1)
+        nc, tr, _, h = _tree(read, T, P, regs[i][1] + k, regs[i + 1][0] + k - 2, True, 0, P.c - accum, -1, observe)
         hits += h
         if tr == 0 and nc > 0:
             multi += nc
             accum += nc
         else:
-            nc, tr, _, h = _tree(read, T, P, regs[i + 1][0] - 1, regs[i][1] + 1, False, 0, P.c - accum, -1)
+            nc, tr, _, h = _tree(read, T, P, regs[i + 1][0] - 1, regs[i][1] + 1, False, 0, P.c - accum, -1, observe)
             hits += h
             if tr == 0 and nc > 0:
                 multi += nc
@@ -173,7 +181,7 @@ def correct_one_read(seq, T, P):
     hs = best[0]
     if hs > 1:
         if accum < P.c:
-            nc, lt, llast, h = _tree(read, T, P, hs - 1, 1, False, 1, P.c - accum, llast)
+            nc, lt, llast, h = _tree(read, T, P, hs - 1, 1, False, 1, P.c - accum, llast, observe)
             hits += h
             if nc > 0:
                 multi += nc
@@ -185,7 +193,7 @@ def correct_one_read(seq, T, P):
     he = best[1] + k - 1
     if he < L:
         if accum < P.c:
-            nc, rt, rlast, h = _tree(read, T, P, he + 1, L, True, 1, P.c - accum, rlast)
+            nc, rt, rlast, h = _tree(read, T, P, he + 1, L, True, 1, P.c - accum, rlast, observe)
             hits += h
             if nc > 0:
                 multi += nc
