@@ -302,6 +302,8 @@ SYMBOLS = [
     ("dbgk_kfreq_export_bits", _i, [_vp, C.c_uint32, _u64, _u64, _vp]),
     ("dbgk_kfreq_merge_counts", _i, [_vp, _vp, _u64, _u64]),
     ("dbgk_kfreq_device_counts", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("dbgk_kfreq_spectrum", _i, [_vp, _u64, _u64, _vp]),
+    ("dbgk_kfreq_spectrum_ms", _i, [_vp, C.POINTER(C.c_double)]),
     ("dbgk_extract_kmers", _i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     ("dbgk_partition_counts", _i, [_vp, C.c_uint32, _vp]),
     ("dbgk_partition_export", _i, [_vp, C.c_uint32, _vp, _u64]),
@@ -337,6 +339,7 @@ SYMBOLS = [
     ("dbgk_comm_wide_export_host_table_links", _i, [_vp, _u64, _vp, _vp, C.c_int32, _vp, _vp, _vp, _u64, C.POINTER(_u64), _vp, _u64, C.POINTER(_u64), _vp]),
     ("dbgk_comm_kfreq_export_counts", _i, [_vp, _u64, _u64, _vp]),
     ("dbgk_comm_kfreq_export_bits", _i, [_vp, C.c_uint32, _u64, _u64, _vp]),
+    ("dbgk_comm_kfreq_spectrum", _i, [_vp, _vp]),
     ("dbgk_synth_reads_device", _i, [_vp, C.POINTER(SynthParams), _u64, _u64, _vp, _vp]),
     ("dbgk_device_malloc", _i, [_vp, C.c_size_t, C.POINTER(_vp)]),
     ("dbgk_device_free", _i, [_vp, _vp]),
@@ -357,6 +360,8 @@ SYMBOLS = [
     ("dbgk_corr_export_bits", _i, [_vp, _u64, _u64, _vp]),
     ("dbgk_corr_reads", _i, [_vp, _vp, _vp, _u64, _vp, _vp]),
     ("dbgk_corr_batch_stats", _i, [_vp, C.POINTER(CorrStats)]),
+    ("dbgk_corr_mutation_scan", _i, [_vp, _vp, _vp, _u64, C.c_uint32, _vp]),
+    ("dbgk_corr_mutation_scan_ms", _i, [_vp, C.POINTER(C.c_double)]),
     ("dbgk_map_create", _i, [C.POINTER(MapParams), _i, C.POINTER(_vp)]),
     ("dbgk_map_destroy", _i, [_vp]),
     ("dbgk_map_set_contigs", _i, [_vp, _vp, _vp, _u64]),
@@ -807,6 +812,19 @@ class Graph:
         _chk(lib().dbgk_kfreq_export_bits(self._h, cutoff, first_byte, n_bytes, out.ctypes.data), "dbgk_kfreq_export_bits")
         return out
 
+    def kfreq_spectrum(self, first=0, n=None):
+        """np.uint64[256]: bin c = counters of [first, first + n) equal to c (255: 255 or more), binned on the device"""
+        n = (4 ** self.k - first) if n is None else n
+        out = np.zeros(256, np.uint64)
+        _chk(lib().dbgk_kfreq_spectrum(self._h, first, n, out.ctypes.data), "dbgk_kfreq_spectrum")
+        return out
+
+    def kfreq_spectrum_ms(self):
+        """device ms of the histogram kernel of the last kfreq_spectrum"""
+        ms = C.c_double()
+        _chk(lib().dbgk_kfreq_spectrum_ms(self._h, C.byref(ms)), "dbgk_kfreq_spectrum_ms")
+        return ms.value
+
     def kfreq_device_counts(self):
         """(device address, number of counters) of a finalized KFREQ handle"""
         ptr, n = C.c_void_p(), _u64()
@@ -1044,6 +1062,12 @@ class Comm:
         _chk(lib().dbgk_comm_kfreq_export_bits(self._c, cutoff, first_byte, n_bytes, out.ctypes.data), "dbgk_comm_kfreq_export_bits")
         return out
 
+    def kfreq_spectrum(self):
+        """np.uint64[256] over the whole table: every member bins the range it owns"""
+        out = np.zeros(256, np.uint64)
+        _chk(lib().dbgk_comm_kfreq_spectrum(self._c, out.ctypes.data), "dbgk_comm_kfreq_spectrum")
+        return out
+
 
 # ---- host helpers mirrored from the reference (kmerSet.cpp:72-95), needed to size tables ---------
 
@@ -1151,6 +1175,27 @@ class Corrector:
         s = CorrStats()
         _chk(lib().dbgk_corr_batch_stats(self._h, C.byref(s)), "dbgk_corr_batch_stats")
         return {f: getattr(s, f) for f, _ in CorrStats._fields_}
+
+    def mutation_scan(self, bases, offsets, skip):
+        """simulate_lowfreq_kmer's scan -> np.uint64[k + 1]: bin j = mutated sites with j of their k windows absent"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.ndim != 1 or len(offsets) < 1:
+            raise ValueError("offsets needs at least one entry (n + 1 entries for n sequences)")
+        if int(offsets[-1]) > bases.size:
+            raise ValueError("the last offset lies beyond the bases")
+        if not 0 <= int(skip) < 1 << 32:
+            raise ValueError("skip must fit in 32 bits (1 .. 2^32 - 1)")
+        hist = np.zeros(self.k + 1, dtype=np.uint64)
+        _chk(lib().dbgk_corr_mutation_scan(self._h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, int(skip), hist.ctypes.data),
+             "dbgk_corr_mutation_scan")
+        return hist
+
+    def mutation_scan_ms(self):
+        """device ms of the scan kernel of the last mutation_scan"""
+        ms = C.c_double()
+        _chk(lib().dbgk_corr_mutation_scan_ms(self._h, C.byref(ms)), "dbgk_corr_mutation_scan_ms")
+        return ms.value
 
 
 def concat_sequences(seqs):

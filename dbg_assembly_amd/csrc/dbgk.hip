@@ -26,6 +26,7 @@
 #include "dbgk_wide_links_patch.h"
 #include "dbgk_wide_partition.h"
 #include "dbgk_correct.h"
+#include "dbgk_spectrum.h"
 #include "dbgk_map.h"
 #include "dbgk_clean.h"
 #include "dbgk_link.h"
@@ -173,6 +174,9 @@ struct dbgk_handle {
 	uint8_t *counts = nullptr;
 	uint64_t n_counts = 0;
 	uint64_t kf_distinct = 0, kf_sum = 0;
+	unsigned long long *kf_bins = nullptr; // the 256 device bins of dbgk_kfreq_spectrum, made at its first call
+	hipEvent_t kf_ev[2] = {nullptr, nullptr};
+	double kf_spectrum_ms = 0;             // device time of the last k_kf_spectrum
 
 	// PARTITION engine
 	bool part = false;            // records are partitioned at push time, table built at finalize
@@ -398,6 +402,9 @@ static void free_handle(dbgk_handle *h)
 	if (h->wside) (void)hipFree(h->wside);
 	if (h->table) (void)hipFree(h->table);
 	if (h->counts) (void)hipFree(h->counts);
+	if (h->kf_bins) (void)hipFree(h->kf_bins);
+	for (hipEvent_t e : h->kf_ev)
+		if (e) (void)hipEventDestroy(e);
 	if (h->first_pos) (void)hipFree(h->first_pos);
 	if (h->d_ctr) (void)hipFree(h->d_ctr);
 	if (h->h_ctr) (void)hipHostFree(h->h_ctr);
@@ -461,6 +468,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_comm.h"
 #include "dbgk_host_wide_links.h"
 #include "dbgk_host_correct.h"
+#include "dbgk_host_spectrum.h"
 #include "dbgk_host_map.h"
 #include "dbgk_host_clean.h"
 #include "dbgk_host_link.h"

@@ -18,6 +18,7 @@ struct dbgk_corr {
 	uint64_t cap_bytes = 0, cap_reads = 0, cap_scratch = 0;
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	dbgk_corr_stats last{};
+	double ms_mut_scan = 0;       // device time of the last k_mut_scan
 };
 
 static int corr_use(dbgk_corr *c)
@@ -135,7 +136,8 @@ extern "C" int dbgk_corr_from_kfreq(dbgk_corr *c, dbgk_handle *h, uint32_t cutof
 {
 	if (!c || !h) return DBGK_ERR_ARG;
 	if (!h->kfreq || !h->finalized || c->sealed) return DBGK_ERR_STATE;
-	if (h->cfg.kmer_size != c->p.k || h->device != c->device || h->n_counts != c->cp.total) return DBGK_ERR_ARG;
+	// (a KFREQ table of k < 3 is padded to 64 counters: only the first 4^k are read)
+	if (h->cfg.kmer_size != c->p.k || h->device != c->device || h->n_counts != std::max<uint64_t>(c->cp.total, 64)) return DBGK_ERR_ARG;
 	int rc = corr_use(c);
 	if (rc) return rc;
 	HIPCHK(hipStreamSynchronize(h->stream)); // the counts are final on the handle's stream

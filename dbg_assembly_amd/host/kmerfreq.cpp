@@ -16,8 +16,12 @@
 // Counting runs on the GPU (KFREQ engine of include/dbgk.h): every k-mer window of every read, N
 // counted as A (correct_error/ReadMe.txt), canonical = min(forward, reverse complement).
 //
+// The original tool also prints the k-mer frequency spectrum, <prefix>.kmer.freq.stat (the reference ships three,
+// test/01.clean_correct/*.kmer.freq.stat); here the 4^k counters are binned on the GPU (dbgk_kfreq_spectrum) and
+// kmer_spectrum.h writes the text.  The counters are bytes, so the file has 255 rows and row 255 means "255 or more".
+//
 // usage: kmerfreq [-k 17] [-f 1|2] [-b 1|8] [-m cutoff] [-t threads] [-o prefix] [-e store size | -a] <reads.lib>
-//        output: <prefix>.kmer.freq.cz, <prefix>.kmer.freq.cz.len   (prefix defaults to <reads.lib>)
+//        output: <prefix>.kmer.freq.cz, <prefix>.kmer.freq.cz.len, <prefix>.kmer.freq.stat   (prefix defaults to <reads.lib>)
 #include <unistd.h>
 #include <zlib.h>
 #include <atomic>
@@ -32,6 +36,7 @@
 #include <vector>
 
 #include "cli_common.h"
+#include "kmer_spectrum.h"
 #include "reads_io.h"
 
 static const uint64_t kBlockKmers = 8ull * 1024 * 1024;  // SrcBlockSize, correct_error/main_parallel_senior.cpp:71
@@ -199,6 +204,22 @@ int main(int argc, char **argv)
 	}
 	fclose(fz);
 	cerr << "wrote " << cz << " (" << n_blocks << " blocks, " << bits << "-bit format)" << endl;
+
+	// the spectrum of the same table: individuals = the windows counted, species = the non-zero counters
+	uint64_t hist[256];
+	rc = comm ? dbgk_comm_kfreq_spectrum(comm, hist) : dbgk_kfreq_spectrum(h, 0, total, hist);
+	if (rc) die("dbgk_kfreq_spectrum", rc);
+	uint64_t species = 0;
+	for (int f = 1; f < 256; f++) species += hist[f];
+	if (species != st.count) {
+		cerr << "k-mer spectrum: " << species << " non-zero counters, but " << st.count << " distinct k-mers were counted" << endl;
+		return 1;
+	}
+	const string stat = prefix + ".kmer.freq.stat";
+	ofstream fstat(stat.c_str());
+	write_kmer_spectrum(fstat, k, 255, hist, st.stored_kmers);
+	fstat.close();
+	if (!fstat) { cerr << "fail to write " << stat << endl; return 1; }
 	if (comm) dbgk_comm_destroy(comm);
 	else dbgk_destroy(h);
 	return 0;

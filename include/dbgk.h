@@ -364,6 +364,12 @@ int dbgk_kfreq_export_bits(dbgk_handle *h, uint32_t cutoff, uint64_t first_byte,
  * dbgk_kfreq_device_counts: the handle's 4^k counters in device memory (what a peer sends).          */
 int dbgk_kfreq_merge_counts(dbgk_handle *h, const uint8_t *d_counts, uint64_t first_kmer, uint64_t n);
 int dbgk_kfreq_device_counts(dbgk_handle *h, uint8_t **d_counts, uint64_t *n);
+/* The k-mer frequency spectrum, computed on the device (additions to ABI 7): hist[c] = number of k-mer values v in
+ * [first_kmer, first_kmer + n) whose counter equals c (c = 255: 255 or more); the 256 bins sum to n.  Any first_kmer
+ * and n inside 4^k; errors as for dbgk_kfreq_export_counts.                                                       */
+int dbgk_kfreq_spectrum(dbgk_handle *h, uint64_t first_kmer, uint64_t n, uint64_t hist[256]);
+/* device time in ms of the histogram kernel of the handle's last dbgk_kfreq_spectrum (0 before the first, and for n = 0) */
+int dbgk_kfreq_spectrum_ms(dbgk_handle *h, double *ms);
 
 /* ---- SEEDIDX engine: the contig k-mer index of the link_scaffold module ----------
  * chop_contig_to_kmerset (link_scaffold/map_func.cpp:119-173): push the contig sequences with
@@ -536,6 +542,8 @@ int dbgk_comm_wide_export_host_table_links(dbgk_comm *c, uint64_t host_size, dbg
  * two exports read every range from its owner; stats.count = distinct canonical k-mers of the whole job.     */
 int dbgk_comm_kfreq_export_counts(dbgk_comm *c, uint64_t first_kmer, uint64_t n, uint8_t *host_out);
 int dbgk_comm_kfreq_export_bits(dbgk_comm *c, uint32_t cutoff, uint64_t first_byte, uint64_t n_bytes, uint8_t *host_out);
+/* dbgk_kfreq_spectrum of the whole table: every member over the range it owns, summed (additions to ABI 7) */
+int dbgk_comm_kfreq_spectrum(dbgk_comm *c, uint64_t hist[256]);
 
 /* ---- utilities --------------------------------------------------------------------------------- */
 
@@ -617,6 +625,15 @@ int dbgk_corr_export_bits(dbgk_corr *c, uint64_t first_byte, uint64_t n_bytes, u
  * bytes): every read after correction, untrimmed, at its input offset; out_rec: n records.  Input order is kept. */
 int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *offsets, uint64_t n, char *out_seq, dbgk_corr_rec *out_rec);
 int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out);
+/* simulate_lowfreq_kmer's scan (correct_error/simulate_lowfreq_kmer.cpp:71-119; additions to ABI 7) against the loaded
+ * table, which must be marked on both strands as every table of this section is.  Sequence i = seq[offsets[i],
+ * offsets[i+1]) (offsets[0] == 0, any length).  Site t of a sequence of L >= 2k - 1 bases is the fragment
+ * seq[t * skip, t * skip + 2k - 1) for every t * skip <= L - (2k - 1); its middle base becomes (code + 1) mod 4
+ * (ACGT = 0..3 in either case, N and any other byte = 0) and hist[number of its k windows absent from the table]++.
+ * hist (k + 1 entries) is overwritten.  skip == 0: DBGK_ERR_ARG.  dbgk_corr_batch_stats is left as it was.          */
+int dbgk_corr_mutation_scan(dbgk_corr *c, const char *seq, const uint64_t *offsets, uint64_t n_seqs, uint32_t skip, uint64_t *hist);
+/* device time in ms of the scan kernel of the last dbgk_corr_mutation_scan (0 before the first, and for a scan without sites) */
+int dbgk_corr_mutation_scan_ms(dbgk_corr *c, double *ms);
 
 /* ---- MAP: map_reads / map_pair of the link_scaffold module on the GPU (additions to ABI 7) ----------------------------------
  * The reference maps every read onto the contigs with a seed search over the contig k-mer index (get_align_seed,
