@@ -99,6 +99,15 @@ class CorrStats(C.Structure):
                 ("ms_overflow", C.c_double)]
 
 
+CORR_COMPACT_TILE = 4096  # DBGK_CORR_COMPACT_TILE
+
+
+class CorrCompactInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("reads", "result_reads", "result_bases", "trimmed_reads", "trimmed_bases", "deleted_reads",
+                                          "one_base", "tree", "node_limit_hits", "by_classify", "by_correct", "by_overflow")] + \
+               [("ms_scan", C.c_double), ("ms_gather", C.c_double)]
+
+
 class MapParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("seed_kmers", C.c_int32), ("min_read_len", C.c_int32), ("second_alignment", C.c_int32),
                 ("min_identity", C.c_double)]
@@ -362,6 +371,12 @@ SYMBOLS = [
     ("dbgk_corr_batch_stats", _i, [_vp, C.POINTER(CorrStats)]),
     ("dbgk_corr_mutation_scan", _i, [_vp, _vp, _vp, _u64, C.c_uint32, _vp]),
     ("dbgk_corr_mutation_scan_ms", _i, [_vp, C.POINTER(C.c_double)]),
+    ("dbgk_corr_reads_device", _i, [_vp, _vp, _vp, _u64, _vp]),
+    ("dbgk_corr_compact", _i, [_vp, C.POINTER(CorrCompactInfo)]),
+    ("dbgk_corr_compact_from", _i, [_vp, _vp, _vp, _vp, _u64, C.POINTER(CorrCompactInfo)]),
+    ("dbgk_corr_compact_results", _i, [_vp, _vp, _vp]),
+    ("dbgk_corr_compact_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("dbgk_push_corrected", _i, [_vp, _vp]),
     ("dbgk_map_create", _i, [C.POINTER(MapParams), _i, C.POINTER(_vp)]),
     ("dbgk_map_destroy", _i, [_vp]),
     ("dbgk_map_set_contigs", _i, [_vp, _vp, _vp, _u64]),
@@ -632,6 +647,10 @@ class Graph:
         buf = DeviceBuffer(self, ((n_bases + 15) // 16) * 4 + 64)
         _chk(lib().dbgk_pack_bases_device(self._h, d_bases, n_bases, buf.ptr), "dbgk_pack_bases_device")
         return buf
+
+    def push_corrected(self, corrector):
+        """the corrector's compact batch (Corrector.compact) pushed where it lies on the device (dbgk_push_corrected)"""
+        _chk(lib().dbgk_push_corrected(self._h, corrector._h), "dbgk_push_corrected")
 
     def finalize(self):
         st = Stats()
@@ -1170,6 +1189,52 @@ class Corrector:
         _chk(lib().dbgk_corr_reads(self._h, bases.ctypes.data, offsets.ctypes.data, n, out.ctypes.data, rec.ctypes.data),
              "dbgk_corr_reads")
         return out[:bases.size], rec[:n]
+
+    def correct_device(self, d_bases, offsets):
+        """correct() for bases already on the device (pointer, 16-byte aligned; offsets on the host) -> records; the corrected
+        bytes stay on the device for compact()"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        rec = np.zeros(max(n, 1), dtype=CORR_REC_DTYPE)
+        _chk(lib().dbgk_corr_reads_device(self._h, d_bases, offsets.ctypes.data, n, rec.ctypes.data), "dbgk_corr_reads_device")
+        return rec[:n]
+
+    @staticmethod
+    def _info(info):
+        return {f: getattr(info, f) for f, _ in CorrCompactInfo._fields_}
+
+    def compact(self):
+        """the last batch trimmed and packed back to back on the device -> the counters and device times (dbgk_corr_compact_info)"""
+        info = CorrCompactInfo()
+        _chk(lib().dbgk_corr_compact(self._h, C.byref(info)), "dbgk_corr_compact")
+        return self._info(info)
+
+    def compact_from(self, bases, offsets, recs):
+        """compact() of a batch held on the host: what correct() returned (untrimmed bytes, offsets, records)"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs, dtype=CORR_REC_DTYPE)
+        n = len(offsets) - 1
+        if len(recs) != n or int(offsets[-1]) > bases.size:
+            raise ValueError("one record per read, and the last offset inside the bases")
+        info = CorrCompactInfo()
+        _chk(lib().dbgk_corr_compact_from(self._h, bases.ctypes.data, offsets.ctypes.data, recs.ctypes.data, n, C.byref(info)),
+             "dbgk_corr_compact_from")
+        return self._info(info)
+
+    def compact_device(self):
+        """-> (device pointer of the compact bases, device pointer of the n + 1 offsets, reads, bases)"""
+        b, o, n, nb = _vp(), _vp(), _u64(), _u64()
+        _chk(lib().dbgk_corr_compact_device(self._h, C.byref(b), C.byref(o), C.byref(n), C.byref(nb)), "dbgk_corr_compact_device")
+        return b.value, o.value, int(n.value), int(nb.value)
+
+    def compact_to_host(self):
+        """-> (compact bases uint8, offsets uint64[n + 1])"""
+        _, _, n, nb = self.compact_device()
+        bases = np.empty(max(nb, 1), dtype=np.uint8)
+        offsets = np.empty(n + 1, dtype=np.uint64)
+        _chk(lib().dbgk_corr_compact_results(self._h, bases.ctypes.data, offsets.ctypes.data), "dbgk_corr_compact_results")
+        return bases[:nb], offsets
 
     def batch_stats(self):
         s = CorrStats()

@@ -26,6 +26,7 @@
 #include "dbgk_wide_links_patch.h"
 #include "dbgk_wide_partition.h"
 #include "dbgk_correct.h"
+#include "dbgk_corr_emit.h"
 #include "dbgk_spectrum.h"
 #include "dbgk_map.h"
 #include "dbgk_clean.h"

@@ -19,7 +19,27 @@ struct dbgk_corr {
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	dbgk_corr_stats last{};
 	double ms_mut_scan = 0;       // device time of the last k_mut_scan
+	// output stage (dbgk_corr_emit.h): the batch d_out / d_off / d_rec hold, and its compact form
+	bool have_batch = false;      // the last dbgk_corr_reads* / dbgk_corr_compact_from succeeded: batch_n reads are resident
+	uint64_t batch_n = 0;
+	bool have_compact = false;
+	uint8_t *c_bases = nullptr;   // 16-byte vectors, the pad of the last one 0
+	uint64_t *c_off = nullptr;    // batch_n + 1 compact offsets
+	uint32_t *c_len = nullptr;
+	void *c_tmp = nullptr;        // the scan's temporary storage
+	unsigned long long *c_ctr = nullptr; // corr::EC_COUNT counters
+	uint64_t c_cap_bytes = 0, c_cap_reads = 0, c_tmp_bytes = 0;
+	uint64_t c_n = 0, c_total = 0;
+	hipEvent_t c_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // length + scan: [0] .. [1]; gather: [2] .. [3]
+	hipEvent_t c_done = nullptr;  // the compact batch is complete (recorded on `stream`)
+	hipEvent_t c_read = nullptr;  // a graph handle has read it (recorded on that handle's stream by dbgk_push_corrected)
+	bool c_lent = false;          // c_read is pending: waited for before the compact buffers are written, regrown or freed
+	dbgk_corr_compact_info c_info{};
 };
+
+// dbgk_sort.hip
+extern "C" int dbgk_internal_scan_lengths(void *tmp, size_t *tmp_bytes, const uint32_t *d_len, uint64_t *d_offsets, uint64_t n_items,
+                                          hipStream_t stream);
 
 static int corr_use(dbgk_corr *c)
 {
@@ -60,6 +80,12 @@ extern "C" int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr
 	if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
 	for (int i = 0; !rc && i < 4; ++i)
 		if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	for (int i = 0; !rc && i < 4; ++i)
+		if (hipEventCreate(&c->c_ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (!rc && (hipEventCreateWithFlags(&c->c_done, hipEventDisableTiming) != hipSuccess ||
+	            hipEventCreateWithFlags(&c->c_read, hipEventDisableTiming) != hipSuccess))
+		rc = DBGK_ERR_HIP;
+	if (!rc && hipMalloc(&c->c_ctr, corr::EC_COUNT * sizeof(unsigned long long)) != hipSuccess) rc = DBGK_ERR_NOMEM;
 	if (!rc && hipMalloc(&c->tab, c->tab_words * 4) != hipSuccess) rc = DBGK_ERR_NOMEM;
 	if (!rc && hipMalloc(&c->d_cnt, 4 * sizeof(uint64_t)) != hipSuccess) rc = DBGK_ERR_NOMEM;
 	if (!rc && hipMemsetAsync(c->tab, 0, c->tab_words * 4, c->stream) != hipSuccess) rc = DBGK_ERR_HIP;
@@ -77,7 +103,11 @@ extern "C" int dbgk_corr_destroy(dbgk_corr *c)
 	if (!c) return DBGK_ERR_ARG;
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	if (c->c_lent) (void)hipEventSynchronize(c->c_read); // a graph handle may still be reading the compact batch
 	corr_free_batch(c);
+	(void)hipFree(c->c_bases); (void)hipFree(c->c_off); (void)hipFree(c->c_len); (void)hipFree(c->c_tmp); (void)hipFree(c->c_ctr);
+	for (hipEvent_t e : {c->c_ev[0], c->c_ev[1], c->c_ev[2], c->c_ev[3], c->c_done, c->c_read})
+		if (e) (void)hipEventDestroy(e);
 	(void)hipFree(c->d_scratch);
 	(void)hipFree(c->tab);
 	(void)hipFree(c->d_cnt);
@@ -174,11 +204,9 @@ extern "C" int dbgk_corr_export_bits(dbgk_corr *c, uint64_t first_byte, uint64_t
 // frontier bound of a tree over d cycles: a node is its path, and a path is fixed by its <= 2 edits (4 bases each)
 static uint64_t corr_frontier_bound(uint64_t d) { return 1 + 4 * d + 8 * d * (d > 0 ? d - 1 : 0); }
 
-extern "C" int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *offsets, uint64_t n, char *out_seq,
-                               dbgk_corr_rec *out_rec)
+// validation of a batch's offsets and the batch buffers, grown on demand: what dbgk_corr_reads does before its upload
+static int corr_batch_begin(dbgk_corr *c, const uint64_t *offsets, uint64_t n)
 {
-	if (!c || !offsets || (n && (!out_rec || !seq || !out_seq))) return DBGK_ERR_ARG;
-	if (!c->sealed) return DBGK_ERR_STATE;
 	if (offsets[0] != 0 || n >= (1ull << 32)) return DBGK_ERR_ARG;
 	uint64_t max_len = 0;
 	for (uint64_t i = 0; i < n; ++i) {
@@ -188,6 +216,7 @@ extern "C" int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *of
 	if (max_len >= (1ull << 29)) return DBGK_ERR_ARG;
 	c->last = dbgk_corr_stats{};
 	c->last.reads = n;
+	c->have_batch = c->have_compact = false;
 	if (!n) return DBGK_OK;
 	int rc = corr_use(c);
 	if (rc) return rc;
@@ -204,23 +233,29 @@ extern "C" int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *of
 			return DBGK_ERR_NOMEM;
 		}
 	}
+	return DBGK_OK;
+}
+
+// The body of dbgk_corr_reads between its upload and its download: the three kernels over the n >= 1 reads of d_in (device memory,
+// read only), whose offsets are in c->d_off already (queued on the stream) and on the host.  Corrected bytes -> c->d_out,
+// records -> c->d_rec; the stream is NOT idle on return when the overflow kernel ran.
+static int corr_batch_kernels(dbgk_corr *c, const uint8_t *d_in, const uint64_t *offsets, uint64_t n, uint32_t *h_cnt)
+{
 	uint32_t *cnt = (uint32_t *)(c->d_cnt + 2); // [0] work list length, [1] overflow list length
-	HIPCHK(hipMemcpyAsync(c->d_seq, seq, nb, hipMemcpyHostToDevice, c->stream));
-	HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemsetAsync(cnt, 0, 8, c->stream));
 	const uint32_t nr = (uint32_t)n;
 	const unsigned grid_cls = (unsigned)std::min<uint64_t>((n + 3) / 4, (uint64_t)c->n_cu * 32);
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
-	hipLaunchKernelGGL(corr::k_corr_classify, dim3(grid_cls), dim3(256), 0, c->stream, (const uint8_t *)c->d_seq, c->d_off, nr, c->cp,
+	hipLaunchKernelGGL(corr::k_corr_classify, dim3(grid_cls), dim3(256), 0, c->stream, d_in, c->d_off, nr, c->cp,
 	                   c->tab, c->d_out, c->d_rec, c->d_work, cnt);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(c->ev[1], c->stream));
 	const unsigned grid_fix = (unsigned)std::min<uint64_t>(n, (uint64_t)c->n_cu * 32);
-	hipLaunchKernelGGL(corr::k_corr_fix, dim3(grid_fix), dim3(corr::kWave), 0, c->stream, (const uint8_t *)c->d_seq, c->d_off, c->cp,
+	hipLaunchKernelGGL(corr::k_corr_fix, dim3(grid_fix), dim3(corr::kWave), 0, c->stream, d_in, c->d_off, c->cp,
 	                   c->tab, c->d_out, c->d_rec, c->d_work, c->d_ovf, cnt);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(c->ev[2], c->stream));
-	uint32_t h_cnt[2] = {0, 0};
+	h_cnt[0] = h_cnt[1] = 0;
 	HIPCHK(hipMemcpyAsync(h_cnt, cnt, 8, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	float ms = 0;
@@ -246,15 +281,19 @@ extern "C" int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *of
 			c->cap_scratch = waves * slice;
 		}
 		HIPCHK(hipEventRecord(c->ev[2], c->stream));
-		hipLaunchKernelGGL(corr::k_corr_overflow, dim3((unsigned)waves), dim3(corr::kWave), 0, c->stream, (const uint8_t *)c->d_seq,
+		hipLaunchKernelGGL(corr::k_corr_overflow, dim3((unsigned)waves), dim3(corr::kWave), 0, c->stream, d_in,
 		                   c->d_off, c->cp, c->tab, c->d_out, c->d_rec, c->d_ovf, h_cnt[1], c->d_scratch, slice, (uint32_t)ol, (uint32_t)cap);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(c->ev[3], c->stream));
 	}
-	HIPCHK(hipMemcpyAsync(out_seq, c->d_out, nb, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(out_rec, c->d_rec, n * sizeof(dbgk_corr_rec), hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
+	return DBGK_OK;
+}
+
+// after the download (the stream is idle): the overflow kernel's time, the capacity check and the batch counters
+static int corr_batch_end(dbgk_corr *c, const dbgk_corr_rec *out_rec, uint64_t n, const uint32_t *h_cnt)
+{
 	if (h_cnt[1]) {
+		float ms = 0;
 		HIPCHK(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
 		c->last.ms_overflow = ms;
 	}
@@ -269,7 +308,47 @@ extern "C" int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *of
 		c->last.by_overflow += r.path == 2;
 		c->last.node_limit_hits += r.node_limit_hits;
 	}
+	c->have_batch = true;
+	c->batch_n = n;
 	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_reads(dbgk_corr *c, const char *seq, const uint64_t *offsets, uint64_t n, char *out_seq,
+                               dbgk_corr_rec *out_rec)
+{
+	if (!c || !offsets || (n && (!out_rec || !seq || !out_seq))) return DBGK_ERR_ARG;
+	if (!c->sealed) return DBGK_ERR_STATE;
+	int rc = corr_batch_begin(c, offsets, n);
+	if (rc) return rc;
+	const uint32_t none[2] = {0, 0};
+	if (!n) return corr_batch_end(c, out_rec, 0, none);
+	const uint64_t nb = offsets[n];
+	HIPCHK(hipMemcpyAsync(c->d_seq, seq, nb, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+	uint32_t h_cnt[2];
+	rc = corr_batch_kernels(c, c->d_seq, offsets, n, h_cnt);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(out_seq, c->d_out, nb, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(out_rec, c->d_rec, n * sizeof(dbgk_corr_rec), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return corr_batch_end(c, out_rec, n, h_cnt);
+}
+
+extern "C" int dbgk_corr_reads_device(dbgk_corr *c, const char *d_seq, const uint64_t *offsets, uint64_t n, dbgk_corr_rec *out_rec)
+{
+	if (!c || !offsets || (n && (!out_rec || !d_seq)) || ((uintptr_t)d_seq & 15u)) return DBGK_ERR_ARG;
+	if (!c->sealed) return DBGK_ERR_STATE;
+	int rc = corr_batch_begin(c, offsets, n);
+	if (rc) return rc;
+	const uint32_t none[2] = {0, 0};
+	if (!n) return corr_batch_end(c, out_rec, 0, none);
+	HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+	uint32_t h_cnt[2];
+	rc = corr_batch_kernels(c, (const uint8_t *)d_seq, offsets, n, h_cnt);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(out_rec, c->d_rec, n * sizeof(dbgk_corr_rec), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return corr_batch_end(c, out_rec, n, h_cnt);
 }
 
 extern "C" int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out)
@@ -277,4 +356,181 @@ extern "C" int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out)
 	if (!c || !out) return DBGK_ERR_ARG;
 	*out = c->last;
 	return DBGK_OK;
+}
+
+// ---- output stage: compact batch on the device, hand-over to a graph handle (kernels in dbgk_corr_emit.h) ------------------------
+
+// the compact buffers are about to be written (free_them: regrown or freed): a graph handle that was given them has to be done
+static int corr_compact_reclaim(dbgk_corr *c, bool free_them)
+{
+	if (!c->c_lent) return DBGK_OK;
+	if (free_them) {
+		HIPCHK(hipEventSynchronize(c->c_read));
+		c->c_lent = false;
+	} else {
+		HIPCHK(hipStreamWaitEvent(c->stream, c->c_read, 0)); // (stays lent: a later regrow or free still has to wait on the host)
+	}
+	return DBGK_OK;
+}
+
+static int corr_compact_run(dbgk_corr *c, dbgk_corr_compact_info *out)
+{
+	const uint64_t n = c->batch_n;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	c->have_compact = false;
+	rc = corr_compact_reclaim(c, n > c->c_cap_reads || !c->c_off);
+	if (rc) return rc;
+	if (n > c->c_cap_reads || !c->c_off) {
+		(void)hipFree(c->c_off); (void)hipFree(c->c_len);
+		c->c_off = nullptr; c->c_len = nullptr;
+		c->c_cap_reads = 0;
+		const uint64_t cap = std::max<uint64_t>(n, 1 << 14);
+		if (hipMalloc(&c->c_off, (cap + 1) * 8) != hipSuccess || hipMalloc(&c->c_len, (cap + 1) * 4) != hipSuccess) return DBGK_ERR_NOMEM;
+		c->c_cap_reads = cap;
+	}
+	size_t need = 0;
+	if (n && dbgk_internal_scan_lengths(nullptr, &need, c->c_len, c->c_off, n + 1, c->stream)) return DBGK_ERR_HIP;
+	if (need > c->c_tmp_bytes) {
+		HIPCHK(hipStreamSynchronize(c->stream));
+		(void)hipFree(c->c_tmp);
+		c->c_tmp = nullptr;
+		c->c_tmp_bytes = 0;
+		if (hipMalloc(&c->c_tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
+		c->c_tmp_bytes = need;
+	}
+	HIPCHK(hipMemsetAsync(c->c_ctr, 0, corr::EC_COUNT * sizeof(unsigned long long), c->stream));
+	HIPCHK(hipEventRecord(c->c_ev[0], c->stream));
+	if (n) {
+		const unsigned grid = (unsigned)std::min<uint64_t>((n + corr::kEmitBlock) / corr::kEmitBlock, (uint64_t)c->n_cu * 16);
+		hipLaunchKernelGGL(corr::k_corr_out_len, dim3(grid), dim3(corr::kEmitBlock), 0, c->stream, c->d_off, c->d_rec, (uint32_t)n, c->c_len,
+		                   c->c_ctr);
+		HIPCHK(hipGetLastError());
+		size_t bytes = c->c_tmp_bytes;
+		if (dbgk_internal_scan_lengths(c->c_tmp, &bytes, c->c_len, c->c_off, n + 1, c->stream)) return DBGK_ERR_HIP;
+	} else {
+		HIPCHK(hipMemsetAsync(c->c_off, 0, 8, c->stream));
+	}
+	HIPCHK(hipEventRecord(c->c_ev[1], c->stream));
+	unsigned long long ctr[corr::EC_COUNT];
+	uint64_t total = 0;
+	HIPCHK(hipMemcpyAsync(&total, c->c_off + n, 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(ctr, c->c_ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream)); // the total sizes the compact buffer
+	const uint64_t want = ((total + 15) & ~15ull) + 64; // whole vectors, and room for the 16-byte reads of the graph kernels behind the end
+	if (want > c->c_cap_bytes) {
+		rc = corr_compact_reclaim(c, true);
+		if (rc) return rc;
+		(void)hipFree(c->c_bases);
+		c->c_bases = nullptr;
+		c->c_cap_bytes = 0;
+		const uint64_t cap = std::max<uint64_t>(want, 1 << 20);
+		if (hipMalloc(&c->c_bases, cap) != hipSuccess) return DBGK_ERR_NOMEM;
+		c->c_cap_bytes = cap;
+	}
+	if (total) {
+		const uint64_t tiles = (total + DBGK_CORR_COMPACT_TILE - 1) / DBGK_CORR_COMPACT_TILE;
+		const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)c->n_cu * 64);
+		HIPCHK(hipEventRecord(c->c_ev[2], c->stream)); // directly in front of the kernel: the copies, the host round trip and an allocation lie before it
+		hipLaunchKernelGGL(corr::k_corr_gather, dim3(grid), dim3(corr::kEmitBlock), 0, c->stream, (const uint8_t *)c->d_out, c->d_off, c->d_rec,
+		                   c->c_off, (uint32_t)n, total, reinterpret_cast<uint4 *>(c->c_bases));
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(c->c_ev[3], c->stream));
+	}
+	HIPCHK(hipEventRecord(c->c_done, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	float ms_scan = 0, ms_gather = 0;
+	HIPCHK(hipEventElapsedTime(&ms_scan, c->c_ev[0], c->c_ev[1]));
+	if (total) HIPCHK(hipEventElapsedTime(&ms_gather, c->c_ev[2], c->c_ev[3]));
+	dbgk_corr_compact_info &I = c->c_info;
+	I = dbgk_corr_compact_info{};
+	I.reads = n;
+	I.result_reads = ctr[corr::EC_RESULT_READS];
+	I.result_bases = ctr[corr::EC_RESULT_BASES];
+	I.trimmed_reads = ctr[corr::EC_TRIMMED_READS];
+	I.trimmed_bases = ctr[corr::EC_TRIMMED_BASES];
+	I.deleted_reads = ctr[corr::EC_DELETED_READS];
+	I.one_base = ctr[corr::EC_ONE_BASE];
+	I.tree = ctr[corr::EC_TREE];
+	I.node_limit_hits = ctr[corr::EC_NODE_LIMIT_HITS];
+	I.by_classify = ctr[corr::EC_BY_CLASSIFY];
+	I.by_correct = ctr[corr::EC_BY_CORRECT];
+	I.by_overflow = ctr[corr::EC_BY_OVERFLOW];
+	I.ms_scan = ms_scan;
+	I.ms_gather = ms_gather; // (0 when nothing is kept: no launch)
+	c->c_n = n;
+	c->c_total = total;
+	c->have_compact = true;
+	*out = I;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_compact(dbgk_corr *c, dbgk_corr_compact_info *out)
+{
+	if (!c || !out) return DBGK_ERR_ARG;
+	if (!c->have_batch) return DBGK_ERR_STATE;
+	return corr_compact_run(c, out);
+}
+
+extern "C" int dbgk_corr_compact_from(dbgk_corr *c, const char *seq, const uint64_t *offsets, const dbgk_corr_rec *rec, uint64_t n,
+                                      dbgk_corr_compact_info *out)
+{
+	if (!c || !offsets || !out || (n && (!rec || (!seq && offsets[n] != 0)))) return DBGK_ERR_ARG;
+	int rc = corr_batch_begin(c, offsets, n);
+	if (rc) return rc;
+	if (n) {
+		if (offsets[n]) HIPCHK(hipMemcpyAsync(c->d_out, seq, offsets[n], hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipMemcpyAsync(c->d_rec, rec, n * sizeof(dbgk_corr_rec), hipMemcpyHostToDevice, c->stream));
+		HIPCHK(hipStreamSynchronize(c->stream)); // the caller's buffers are free on return
+	}
+	const uint32_t none[2] = {0, 0};
+	rc = corr_batch_end(c, rec, n, none);
+	if (rc) return rc;
+	return corr_compact_run(c, out);
+}
+
+extern "C" int dbgk_corr_compact_results(dbgk_corr *c, char *bases, uint64_t *offsets)
+{
+	if (!c || !offsets) return DBGK_ERR_ARG;
+	if (!c->have_compact) return DBGK_ERR_STATE;
+	if (!bases && c->c_total) return DBGK_ERR_ARG;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	if (c->c_total) HIPCHK(hipMemcpyAsync(bases, c->c_bases, c->c_total, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(offsets, c->c_off, (c->c_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_compact_device(dbgk_corr *c, const char **d_bases, const uint64_t **d_offsets, uint64_t *n_reads, uint64_t *n_bases)
+{
+	if (!c || !d_bases || !d_offsets || !n_reads || !n_bases) return DBGK_ERR_ARG;
+	if (!c->have_compact) return DBGK_ERR_STATE;
+	*d_bases = (const char *)c->c_bases;
+	*d_offsets = c->c_off;
+	*n_reads = c->c_n;
+	*n_bases = c->c_total;
+	return DBGK_OK;
+}
+
+// launch_batch queues every kernel that reads the pushed pointers on the handle's stream (the record engines keep records, the
+// others their table: no engine keeps the pointers), so the event recorded behind the push covers every reader and no dbgk_sync
+// is needed for any engine.
+extern "C" int dbgk_push_corrected(dbgk_handle *h, dbgk_corr *c)
+{
+	if (!h || !c) return DBGK_ERR_ARG;
+	if (h->device != c->device) return DBGK_ERR_ARG;
+	if (!c->have_compact || h->finalized) return DBGK_ERR_STATE;
+	int rc = use_device(h);
+	if (rc) return rc;
+	HIPCHK(hipStreamWaitEvent(h->stream, c->c_done, 0));
+	// c_read is ONE event: a push into another handle re-records it.  That handle's stream first waits for the earlier record, so
+	// the new one lies behind every reader so far, whichever handles they were pushed to.
+	if (c->c_lent) HIPCHK(hipStreamWaitEvent(h->stream, c->c_read, 0));
+	rc = dbgk_push_reads_device(h, (const char *)c->c_bases, c->c_off, c->c_n, c->c_total);
+	// (also after a failed push: part of its work may have been queued)
+	if (hipEventRecord(c->c_read, h->stream) == hipSuccess) c->c_lent = true;
+	else if (rc == DBGK_OK) rc = DBGK_ERR_HIP;
+	return rc;
 }

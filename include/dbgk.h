@@ -635,6 +635,51 @@ int dbgk_corr_mutation_scan(dbgk_corr *c, const char *seq, const uint64_t *offse
 /* device time in ms of the scan kernel of the last dbgk_corr_mutation_scan (0 before the first, and for a scan without sites) */
 int dbgk_corr_mutation_scan_ms(dbgk_corr *c, double *ms);
 
+/* The corrected reads stay on the device (additions to ABI 7).  The COMPACT batch is what the command line writes as sequence
+ * lines, without the text: read i trimmed to deleted ? 0 : L - left_trim - right_trim bytes from byte left_trim on (a record
+ * that trims more than its read holds -- the kernels write none for a read they keep -- gives 0), the reads back to back in
+ * input order, a deleted read of length 0 at its place (offsets[i + 1] == offsets[i], so pairs stay pairs).  On the device the
+ * bases start on a 16-byte boundary and fill whole 16-byte vectors, the pad of the last one 0; the offsets are n + 1 64-bit
+ * values.  The gather kernel works in tiles of DBGK_CORR_COMPACT_TILE output bytes.                                         */
+#define DBGK_CORR_COMPACT_TILE 4096
+typedef struct dbgk_corr_compact_info {
+	uint64_t reads;             /* reads of the batch, deleted ones included                                        */
+	uint64_t result_reads;      /* num_result_reads / num_result_bases of <file>.correct.stat                       */
+	uint64_t result_bases;
+	uint64_t trimmed_reads;     /* num_trimmed_reads / num_trimmed_bases (kept reads only)                          */
+	uint64_t trimmed_bases;
+	uint64_t deleted_reads;
+	uint64_t one_base;          /* num_corrected_bases_by_Fast_method / _by_BBtree_method (kept reads only)         */
+	uint64_t tree;
+	uint64_t node_limit_hits;   /* as dbgk_corr_stats: all reads                                                    */
+	uint64_t by_classify, by_correct, by_overflow;
+	double ms_scan;             /* device time of the length kernel + the scan, and of the gather                   */
+	double ms_gather;
+} dbgk_corr_compact_info;
+/* dbgk_corr_reads for reads already in device memory of the handle's GPU: d_seq (16-byte aligned, offsets[n] bytes, not
+ * written) is read where it lies.  offsets are HOST memory as above; out_rec is written as above, the corrected bytes stay
+ * on the device for dbgk_corr_compact.  The call returns when the batch is done.                                            */
+int dbgk_corr_reads_device(dbgk_corr *c, const char *d_seq, const uint64_t *offsets, uint64_t n, dbgk_corr_rec *out_rec);
+/* the compact batch of the handle's last batch (dbgk_corr_reads, dbgk_corr_reads_device, dbgk_corr_compact_from); before any:
+ * DBGK_ERR_STATE.  Returns when it is complete.                                                                             */
+int dbgk_corr_compact(dbgk_corr *c, dbgk_corr_compact_info *out);
+/* the same for a batch the caller holds on the host -- what an earlier dbgk_corr_reads returned: untrimmed corrected bytes,
+ * offsets (checked as there), records.  It becomes the handle's batch; no table is needed.                                  */
+int dbgk_corr_compact_from(dbgk_corr *c, const char *seq, const uint64_t *offsets, const dbgk_corr_rec *rec, uint64_t n,
+                           dbgk_corr_compact_info *out);
+/* host copy of the compact batch: offsets[n] bytes (without the pad) and n + 1 offsets                                      */
+int dbgk_corr_compact_results(dbgk_corr *c, char *bases, uint64_t *offsets);
+/* the compact batch where it lies; valid until the next dbgk_corr_reads*, dbgk_corr_compact* or dbgk_corr_destroy on c       */
+int dbgk_corr_compact_device(dbgk_corr *c, const char **d_bases, const uint64_t **d_offsets, uint64_t *n_reads, uint64_t *n_bases);
+/* dbgk_push_reads_device of c's compact batch into h (any engine that call serves, KFREQ included), ordered by events: h's
+ * stream waits for the compaction, and c waits for the event recorded on h's stream behind the push before it overwrites,
+ * regrows or frees the compact buffers -- so c may be used again at once.  Every kernel that reads the pushed pointers is
+ * queued on h's stream by the push itself (the record engines keep records, no engine keeps the pointers), so that event
+ * covers them all and the call does not end with a dbgk_sync.  One compact batch may be pushed into several handles (a KFREQ
+ * handle and a graph, say): each push makes h's stream wait for the event of the push before it, so the latest event lies
+ * behind every reader.  Handles on different devices: DBGK_ERR_ARG; no compact batch, or h finalized: DBGK_ERR_STATE.       */
+int dbgk_push_corrected(dbgk_handle *h, dbgk_corr *c);
+
 /* ---- MAP: map_reads / map_pair of the link_scaffold module on the GPU (additions to ABI 7) ----------------------------------
  * The reference maps every read onto the contigs with a seed search over the contig k-mer index (get_align_seed,
  * link_scaffold/map_func.cpp:181-237) and a gap-free extension with a mismatch count (extend_align_region, :241-299).  A mapper
