@@ -5,6 +5,10 @@ what the goldens of tests/golden/clean_cases are reproduced with on the CPU and 
     clean_adapter.cpp:174-231   the adapter loop, cutting, RemoveShort           -> clean_adapter
     clean_adapter.cpp:234-268   the contaminant file                              -> read_fasta
     clean_lowqual.cpp:65-188    error sum, break points, longest block            -> lowqual_block, clean_lowqual
+
+Observers for the edge suite (tests/clean_edge_cases.py): max_cells (every cell that holds the maximum), align_lanes (the
+alignment lane by lane as DESIGN.md section 7d describes the kernel, with one-token mutants), and the break points and
+mutants of lowqual_block.
 """
 import gzip
 import json
@@ -101,6 +105,89 @@ def align_matrix(read, ad):
     while H[i][j] > 0:
         i, j = i - 1, j - 1
     return (best[0], i + 1, best[1], j + 1, best[2])
+
+
+def max_cells(read, ad):
+    """-> (maximum, [(read_end, adapter_end), ...] 1-based, in row-major order): every cell of the reference's matrix that holds the
+    maximum; (0, []) without a positive cell.  The first one is where align_matrix ends."""
+    L, A = len(read), len(ad)
+    prev, top, cells = [0] * (A + 1), 0, []
+    for i in range(1, L + 1):
+        cur = [0] * (A + 1)
+        a = CODE.get(read[i - 1], 4)
+        for j in range(1, A + 1):
+            cur[j] = max(0, prev[j - 1] + (1 if (a < 4 and a == CODE.get(ad[j - 1], 4)) else -2))
+            if cur[j] > top:
+                top, cells = cur[j], [(i, j)]
+            elif cur[j] == top and top:
+                cells.append((i, j))
+        prev = cur
+    return top, cells
+
+
+ALIGN_MUTANTS = ("reset_lt", "first_ge", "fold_no_tie", "fold_re_gt", "fold_d_lt", "reduce_max_end", "reduce_min_diag", "no_128_guard",
+                 "mask_5f")
+
+
+def lane_code(c, mutant=None):
+    """clean_code of csrc/dbgk_clean.h on a byte value: 0..3 for ACGTacgt, 4 for everything else"""
+    u = c & (0x5F if mutant == "mask_5f" else 0xDF)
+    letter = (mutant in ("no_128_guard", "mask_5f") or c < 128) and u in (0x41, 0x43, 0x47, 0x54)
+    return ((c >> 1) ^ (c >> 2)) & 3 if letter else 4
+
+
+def lane_of(read_end, adapter_end, A):
+    """(lane, round) of the diagonal that holds the cell (read_end, adapter_end), both 1-based"""
+    t = (read_end - adapter_end) + A - 1
+    return t % 64, t // 64
+
+
+def align_lanes(read, ad, mutant=None):
+    """align the way DESIGN.md section 7d describes the kernel: read_len + adapter_len - 1 diagonals in rounds of 64, one diagonal
+    per lane; a lane folds the best cell of each of its rounds into one with the three-key tie rule; three reductions over the 64
+    lanes (maximum score, minimum read_end among those, maximum diagonal among those) name the winner.
+    -> {"hit": (score, read_start, read_end, adapter_start, adapter_end), "lane", "round": of the winning diagonal,
+        "ties": [(lane, round, read_end, adapter_end)] of every lane whose folded cell holds the maximum}.
+    `mutant` (one of ALIGN_MUTANTS) changes one token, for tests that ask whether the crafted reads would notice."""
+    L, A = len(read), len(ad)
+    rc = [lane_code(ord(c), mutant) for c in read]
+    ac = [(5 if v == 4 else v) for v in (lane_code(ord(c), mutant) for c in ad)]
+    n_diag = L + A - 1
+    lanes = [[0, 0, 0, 0, 0] for _ in range(64)]                 # bs, be, bst, bd, round of that cell
+    for r0 in range(0, max(n_diag, 0), 64):
+        d_lo = r0 - (A - 1)
+        for lane in range(64):
+            d = d_lo + lane
+            s, st, rs, re_, rst = 0, max(d, 0), 0, 0, 0
+            # positions outside the read hold a code that equals no adapter code: they end a run and start none
+            for i in range(max(d, 0), min(L, d + A)):
+                s += 1 if rc[i] == ac[i - d] else -2
+                if (s < 0) if mutant == "reset_lt" else (s <= 0):
+                    s, st = 0, i + 1
+                elif (s >= rs) if mutant == "first_ge" else (s > rs):
+                    rs, re_, rst = s, i, st
+            bs, be, bst, bd, _ = lanes[lane]
+            if mutant == "fold_no_tie":
+                tie = False
+            elif mutant == "fold_re_gt":
+                tie = re_ > be or (re_ == be and d > bd)
+            elif mutant == "fold_d_lt":
+                tie = re_ < be or (re_ == be and d < bd)
+            else:
+                tie = re_ < be or (re_ == be and d > bd)
+            if rs > bs or (rs == bs and rs > 0 and tie):
+                lanes[lane] = [rs, re_, rst, d, r0 // 64]
+    best = max(v[0] for v in lanes)
+    if best <= 0:
+        return {"hit": (0, 0, 0, 0, 0), "lane": None, "round": None, "ties": []}
+    top = [n for n in range(64) if lanes[n][0] == best]
+    end = (max if mutant == "reduce_max_end" else min)(lanes[n][1] for n in top)
+    tied = [n for n in top if lanes[n][1] == end]
+    diag = (min if mutant == "reduce_min_diag" else max)(lanes[n][3] for n in tied)
+    src = next(n for n in tied if lanes[n][3] == diag)
+    start = lanes[src][2]
+    return {"hit": (best, start + 1, end + 1, start - diag + 1, end - diag + 1), "lane": src, "round": lanes[src][4],
+            "ties": [(n, lanes[n][4], lanes[n][1] + 1, lanes[n][1] - lanes[n][3] + 1) for n in top]}
 
 
 def first_hit(read, adapters, cutoff):
@@ -216,25 +303,38 @@ def error_table(shift):
     return table
 
 
-def lowqual_block(read, qual, cutoff, shift, table=None):
-    """a record with strings of equal length -> (error_sum, start, length, trimmed): the fields of dbgk_lowqual_block"""
+LOWQUAL_MUTANTS = ("break_ge", "longest_ge", "tail_ge", "N_keeps_quality", "n_counts_as_N", "pairwise_sum")
+
+
+def _pairwise(v):
+    return 0.0 if not v else (v[0] if len(v) == 1 else _pairwise(v[:len(v) // 2]) + _pairwise(v[len(v) // 2:]))
+
+
+def lowqual_block(read, qual, cutoff, shift, table=None, breaks=None, mutant=None):
+    """a record with strings of equal length -> (error_sum, start, length, trimmed): the fields of dbgk_lowqual_block.
+    `breaks`, a list, receives the 0-based break points of a trimmed read; `mutant` (one of LOWQUAL_MUTANTS) changes one token."""
     table = table or error_table(shift)
     n = len(read)
-    qs = [shift if read[j] == "N" else ord(qual[j]) for j in range(n)]
+    as_n = ("Nn" if mutant == "n_counts_as_N" else "N") if mutant != "N_keeps_quality" else ""
+    qs = [shift if read[j] in as_n else ord(qual[j]) for j in range(n)]
     err = 0.0
     for v in qs:
         err += table[v]
+    if mutant == "pairwise_sum":
+        err = _pairwise([table[v] for v in qs])
     if not err > cutoff * n:
         return (err, 1 if n else 0, n, 0)
     ae, al, last, ms, ml = 0.0, 0, 0, 0, 0
     for j in range(n):
         ae += table[qs[j]]
         al += 1
-        if ae > cutoff * al:
-            if j - last > ml:
+        if (ae >= cutoff * al) if mutant == "break_ge" else (ae > cutoff * al):
+            if breaks is not None:
+                breaks.append(j)
+            if (j - last >= ml) if mutant == "longest_ge" else (j - last > ml):
                 ml, ms = j - last, last + 1
             ae, al, last = 0.0, 0, j + 1
-    if n - last > ml:
+    if (n - last >= ml) if mutant == "tail_ge" else (n - last > ml):
         ml, ms = n - last, last + 1
     return (err, ms, ml, 1) if 1 <= ms <= n else (err, 0, 0, 1)
 
