@@ -134,6 +134,15 @@ class CleanStats(C.Structure):
                 ("cells", C.c_uint64), ("ms_lds", C.c_double), ("ms_global", C.c_double), ("ms_lowqual", C.c_double)]
 
 
+CLEAN_COMPACT_TILE = 4096  # DBGK_CLEAN_COMPACT_TILE
+CLEAN_KIND_LOWQUAL, CLEAN_KIND_ADAPTER = 0, 1  # DBGK_CLEAN_KIND_*
+
+
+class CleanCompactInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("reads", "raw_bases", "trimmed_reads", "trimmed_bases", "short_reads", "short_bases",
+                                          "clean_reads", "clean_bases")] + [("ms_scan", C.c_double), ("ms_gather", C.c_double)]
+
+
 class LinkParams(C.Structure):
     _fields_ = [("mate_pair", C.c_int32), ("pair_num_cut", C.c_int32), ("insert_size", C.c_int32)]
 
@@ -389,6 +398,13 @@ SYMBOLS = [
     ("dbgk_clean_adapter", _i, [_vp, _vp, _vp, _u64, _vp]),
     ("dbgk_clean_lowqual", _i, [_vp, _vp, _vp, _vp, _u64, C.c_double, C.c_int32, _vp]),
     ("dbgk_clean_batch_stats", _i, [_vp, C.POINTER(CleanStats)]),
+    ("dbgk_clean_lowqual_device", _i, [_vp, _vp, _vp, _vp, _u64, C.c_double, C.c_int32, _vp]),
+    ("dbgk_clean_adapter_device", _i, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    ("dbgk_clean_compact", _i, [_vp, C.c_int32, C.POINTER(CleanCompactInfo)]),
+    ("dbgk_clean_compact_from", _i, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _u64, C.c_int32, C.c_int32, C.POINTER(CleanCompactInfo)]),
+    ("dbgk_clean_compact_results", _i, [_vp, _vp, _vp, _vp]),
+    ("dbgk_clean_compact_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("dbgk_push_cleaned", _i, [_vp, _vp]),
     ("dbgk_link_create", _i, [C.POINTER(LinkParams), _i, C.POINTER(_vp)]),
     ("dbgk_link_destroy", _i, [_vp]),
     ("dbgk_link_set_contigs", _i, [_vp, _vp, _u64]),
@@ -651,6 +667,10 @@ class Graph:
     def push_corrected(self, corrector):
         """the corrector's compact batch (Corrector.compact) pushed where it lies on the device (dbgk_push_corrected)"""
         _chk(lib().dbgk_push_corrected(self._h, corrector._h), "dbgk_push_corrected")
+
+    def push_cleaned(self, cleaner):
+        """the cleaner's compact bases (Cleaner.compact) pushed where they lie on the device (dbgk_push_cleaned)"""
+        _chk(lib().dbgk_push_cleaned(self._h, cleaner._h), "dbgk_push_cleaned")
 
     def finalize(self):
         st = Stats()
@@ -1368,6 +1388,69 @@ class Cleaner:
         _chk(lib().dbgk_clean_lowqual(self._h, bases.ctypes.data if bases.size else None, quals.ctypes.data if quals.size else None,
                                       offsets.ctypes.data, n, error_rate_cutoff, quality_shift, blocks.ctypes.data), "dbgk_clean_lowqual")
         return blocks[:n]
+
+    def lowqual_device(self, d_bases, d_quals, offsets, error_rate_cutoff=0.001, quality_shift=33):
+        """lowqual() for planes already on the device (pointers, 16-byte aligned, readable 16 bytes behind the last read; offsets on
+        the host) -> LOWQUAL_BLOCK_DTYPE[n]; the planes are read again by compact()"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        blocks = np.zeros(max(n, 1), dtype=LOWQUAL_BLOCK_DTYPE)
+        _chk(lib().dbgk_clean_lowqual_device(self._h, d_bases, d_quals, offsets.ctypes.data, n, error_rate_cutoff, quality_shift,
+                                             blocks.ctypes.data), "dbgk_clean_lowqual_device")
+        return blocks[:n]
+
+    def adapter_device(self, d_bases, d_quals, offsets):
+        """adapter() for bases already on the device; d_quals (or None) only travels into the compact batch -> ADAPTER_HIT_DTYPE[n]"""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        hits = np.zeros(max(n, 1), dtype=ADAPTER_HIT_DTYPE)
+        _chk(lib().dbgk_clean_adapter_device(self._h, d_bases, d_quals, offsets.ctypes.data, n, hits.ctypes.data),
+             "dbgk_clean_adapter_device")
+        return hits[:n]
+
+    @staticmethod
+    def _info(info):
+        return {f: getattr(info, f) for f, _ in CleanCompactInfo._fields_}
+
+    def compact(self, min_len=75):
+        """the last batch cut as its program cuts it and packed back to back on the device -> the .stat counters and device times
+        (dbgk_clean_compact_info)"""
+        info = CleanCompactInfo()
+        _chk(lib().dbgk_clean_compact(self._h, min_len, C.byref(info)), "dbgk_clean_compact")
+        return self._info(info)
+
+    def compact_from(self, kind, bases, quals, offsets, recs, quality_shift=33, min_len=75):
+        """compact() of a batch held on the host: reads, qualities (or None) and the records of an earlier adapter() / lowqual();
+        kind is CLEAN_KIND_ADAPTER or CLEAN_KIND_LOWQUAL"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        quals = None if quals is None else np.ascontiguousarray(quals, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        recs = np.ascontiguousarray(recs, dtype=LOWQUAL_BLOCK_DTYPE if kind == CLEAN_KIND_LOWQUAL else ADAPTER_HIT_DTYPE)
+        n = len(offsets) - 1
+        if len(recs) != n or int(offsets[-1]) > bases.size or (quals is not None and quals.size != bases.size):
+            raise ValueError("one record per read, the last offset inside the bases, and as many qualities as bases")
+        info = CleanCompactInfo()
+        _chk(lib().dbgk_clean_compact_from(self._h, kind, bases.ctypes.data if bases.size else None,
+                                           quals.ctypes.data if quals is not None and quals.size else None, offsets.ctypes.data,
+                                           recs.ctypes.data if n else None, n, quality_shift, min_len, C.byref(info)), "dbgk_clean_compact_from")
+        return self._info(info)
+
+    def compact_device(self):
+        """-> (device pointer of the compact bases, of the qualities or None, of the n + 1 offsets, reads, bases)"""
+        b, q, o, n, nb = _vp(), _vp(), _vp(), _u64(), _u64()
+        _chk(lib().dbgk_clean_compact_device(self._h, C.byref(b), C.byref(q), C.byref(o), C.byref(n), C.byref(nb)),
+             "dbgk_clean_compact_device")
+        return b.value, q.value, o.value, int(n.value), int(nb.value)
+
+    def compact_to_host(self):
+        """-> (compact bases uint8, compact qualities uint8 or None, offsets uint64[n + 1])"""
+        _, q, _, n, nb = self.compact_device()
+        bases = np.empty(max(nb, 1), dtype=np.uint8)
+        quals = np.empty(max(nb, 1), dtype=np.uint8) if q else None
+        offsets = np.empty(n + 1, dtype=np.uint64)
+        _chk(lib().dbgk_clean_compact_results(self._h, bases.ctypes.data, quals.ctypes.data if q else None, offsets.ctypes.data),
+             "dbgk_clean_compact_results")
+        return bases[:nb], (quals[:nb] if q else None), offsets
 
     def batch_stats(self):
         s = CleanStats()

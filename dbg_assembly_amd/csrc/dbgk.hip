@@ -30,6 +30,7 @@
 #include "dbgk_spectrum.h"
 #include "dbgk_map.h"
 #include "dbgk_clean.h"
+#include "dbgk_clean_emit.h"
 #include "dbgk_link.h"
 #include "dbgk_fill.h"
 #include "dbgk_super.h"

@@ -776,6 +776,62 @@ int dbgk_clean_lowqual(dbgk_clean *c, const char *bases, const char *quals, cons
                        double error_rate_cutoff, int32_t quality_shift, dbgk_lowqual_block *out);
 int dbgk_clean_batch_stats(dbgk_clean *c, dbgk_clean_stats *out);
 
+/* The cleaned reads stay on the device (additions to ABI 7).  The COMPACT batch is what the two programs write as lines 2 and 4
+ * of every record, without the text.  After a lowqual batch the quality of every byte 'N' of a read becomes (char)quality_shift,
+ * and a read with `trimmed` is its bytes [start - 1, start - 1 + length), or nothing when start == 0; after an adapter batch a
+ * read with adapter >= 0 is its first read_start - 1 bytes and no quality is rewritten.  In both a result shorter than min_len
+ * becomes empty, and a record that points outside its read (the kernels write none) gives length 0: no byte outside a read is
+ * ever copied.  The reads lie back to back in input order, an emptied read of length 0 at its place (pairs stay pairs); bases
+ * and qualities are two planes under one set of n + 1 64-bit offsets.  Each plane starts on a 16-byte boundary and fills whole
+ * 16-byte vectors, the pad of the last one 0: the layout of dbgk_corr_compact.  The gather kernel works in tiles of
+ * DBGK_CLEAN_COMPACT_TILE output bytes of each plane.                                                                        */
+#define DBGK_CLEAN_COMPACT_TILE 4096
+#define DBGK_CLEAN_KIND_LOWQUAL 0   /* the records are dbgk_lowqual_block                                                     */
+#define DBGK_CLEAN_KIND_ADAPTER 1   /* the records are dbgk_adapter_hit                                                       */
+typedef struct dbgk_clean_compact_info {
+	/* the integer columns of the .stat file of the program the batch came from (one batch = one file).  With m the length of a
+	 * read's result before the short-read filter: trimmed_bases adds L - m per trimmed read, which on the kernels' records is
+	 * clean_adapter's read_len - read_start + 1 per hit and clean_lowqual's seq_len - length per trimmed read; clean_reads counts
+	 * every read that is not short after an adapter batch (empty ones included when min_len is 0), only non-empty reads after a
+	 * lowqual batch.                                                                                                           */
+	uint64_t reads, raw_bases;
+	uint64_t trimmed_reads, trimmed_bases;
+	uint64_t short_reads, short_bases;
+	uint64_t clean_reads, clean_bases;
+	double ms_scan;             /* device time of the length kernel + the scan, and of the gather                            */
+	double ms_gather;
+} dbgk_clean_compact_info;
+/* dbgk_clean_lowqual / dbgk_clean_adapter for a batch already in device memory of the handle's GPU: d_bases and d_quals (16-byte
+ * aligned, never written) are read where they lie and must be readable for 16 bytes behind offsets[n], as the handle's own
+ * batch buffers are (the kernels load whole dwords); they must stay valid until the batch has been compacted.  offsets are HOST
+ * memory; out gets the n records as above.  d_quals of the adapter call may be null: the compact batch then has no quality
+ * plane.  Passing the handle's own compact planes is DBGK_ERR_ARG: a chain of two stages uses two handles.  The calls return
+ * when the batch is done.                                                                                                    */
+int dbgk_clean_lowqual_device(dbgk_clean *c, const char *d_bases, const char *d_quals, const uint64_t *offsets, uint64_t n_reads,
+                              double error_rate_cutoff, int32_t quality_shift, dbgk_lowqual_block *out);
+int dbgk_clean_adapter_device(dbgk_clean *c, const char *d_bases, const char *d_quals, const uint64_t *offsets, uint64_t n_reads,
+                              dbgk_adapter_hit *out);
+/* the compact batch of the handle's last batch (any of the four calls above, or dbgk_clean_compact_from); before any:
+ * DBGK_ERR_STATE.  min_len >= 0 is the programs' -r.  Returns when it is complete.                                           */
+int dbgk_clean_compact(dbgk_clean *c, int32_t min_len, dbgk_clean_compact_info *out);
+/* the same for a batch the caller holds on the host: reads, qualities (may be null: no quality plane) and the records of an
+ * earlier call, `kind` naming their type; quality_shift is used by DBGK_CLEAN_KIND_LOWQUAL only.  It becomes the handle's batch. */
+int dbgk_clean_compact_from(dbgk_clean *c, int32_t kind, const char *bases, const char *quals, const uint64_t *offsets, const void *recs,
+                            uint64_t n_reads, int32_t quality_shift, int32_t min_len, dbgk_clean_compact_info *out);
+/* host copy of the compact batch: offsets[n] bytes of each plane (without the pad) and n + 1 offsets.  Any of the three may be
+ * null; quals of a batch without a quality plane: DBGK_ERR_ARG.                                                              */
+int dbgk_clean_compact_results(dbgk_clean *c, char *bases, char *quals, uint64_t *offsets);
+/* the compact batch where it lies (*d_quals null without a quality plane); valid until the handle's next batch, next compact
+ * or dbgk_clean_destroy                                                                                                      */
+int dbgk_clean_compact_device(dbgk_clean *c, const char **d_bases, const char **d_quals, const uint64_t **d_offsets, uint64_t *n_reads,
+                              uint64_t *n_bases);
+/* dbgk_push_reads_device of c's compact bases into h (any engine that call serves, KFREQ included), ordered by events as
+ * dbgk_push_corrected is: h's stream waits for the compaction, and c waits for the event recorded on h's stream behind the push
+ * before it overwrites, regrows or frees the compact buffers -- so c may be used again at once.  One compact batch may be pushed
+ * into several handles: each push makes h's stream wait for the event of the push before it, so the latest event lies behind
+ * every reader.  Handles on different devices: DBGK_ERR_ARG; no compact batch, or h finalized: DBGK_ERR_STATE.                */
+int dbgk_push_cleaned(dbgk_handle *h, dbgk_clean *c);
+
 /* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
  * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
  * links between contigs and walks the unambiguous ones into scaffolds.  Contig c (0-based, in the order of the contig file) is node
