@@ -103,39 +103,83 @@ __device__ __forceinline__ uint32_t divmod_u64_u32(uint64_t h, const Div32Magic 
 	return r2 >> g.s;
 }
 
-// h = q * d + r for d < 2^31 with m = floor(2^64 / d) (ModMagic): mulhi(h, m) is q or q - 1, so the
+// h = q * d + r for 2 <= d < 2^31 with m = floor(2^64 / d) (ModMagic): mulhi(h, m) is q or q - 1, so the
 // estimate's remainder is < 2d < 2^32 and 32-bit wrap-around arithmetic gives it exactly.  Integer
 // multiplies issue at full rate on gfx950 (profiles/ubench/alu_rate.hip), which makes this ~13
 // instructions against ~35 for the two 2-by-1 steps above.
-__device__ __forceinline__ uint32_t divmod_magic_small(uint64_t h, uint64_t m, uint32_t d, uint64_t &q_out)
+// The fix-up is ONE carry: r + (2^32 - d) carries out exactly when r >= d, its sum is r - d (a huge value when r < d, so the
+// remainder is the minimum of the two), and the carry goes into the quotient's last 32-bit addend b before the one 64-bit
+// add that the multiply-high ends with anyway -- b <= m >> 32 <= 2^31, so b + 1 cannot wrap.  (No compare, no select, no
+// second 64-bit add: seven instructions behind the multiplies instead of ten.)
+// Host-callable (tests/test_divmod_hash_host.py checks it against 128-bit division on the CPU).
+__host__ __device__ __forceinline__ uint32_t divmod_magic_small(uint64_t h, uint64_t m, uint32_t d, uint64_t &q_out)
 {
 	const uint32_t h0 = (uint32_t)h, h1 = (uint32_t)(h >> 32), m0 = (uint32_t)m, m1 = (uint32_t)(m >> 32);
-	const uint64_t t1 = (uint64_t)h1 * m0 + __umulhi(h0, m0);
+#if defined(__HIP_DEVICE_COMPILE__)
+	const uint32_t hh = __umulhi(h0, m0);
+#else
+	const uint32_t hh = (uint32_t)(((uint64_t)h0 * m0) >> 32);
+#endif
+	const uint64_t t1 = (uint64_t)h1 * m0 + hh;
 	const uint64_t t2 = (uint64_t)h0 * m1 + (uint32_t)t1;
-	uint64_t q = (uint64_t)h1 * m1 + (t1 >> 32) + (t2 >> 32);
-	uint32_t r = h0 - (uint32_t)q * d;
-	const bool fix = r >= d;
-	r = fix ? r - d : r;
-	q += fix ? 1u : 0u;
-	q_out = q;
-	return r;
+	const uint64_t a = (uint64_t)h1 * m1 + (t1 >> 32); // mulhi(h, m) = a + b
+	const uint32_t b = (uint32_t)(t2 >> 32);
+	const uint32_t r = h0 - ((uint32_t)a + b) * d;
+	uint32_t r1;
+	const bool fix = __builtin_uadd_overflow(r, 0u - d, &r1);
+	q_out = a + (uint64_t)(b + (fix ? 1u : 0u));
+	return r < r1 ? r : r1;
 }
 
 // ---- hash_code (kmerSet.h:105-116) and its inverse ------------------------------------------
+// k += ~(k << n) is k - (k << n) - 1: one 64-bit subtraction with the borrow-in set.  Left to the compiler it is the shift, two
+// v_not and a 64-bit add (n = 32: one v_not and the add); as a borrow chain it is the shift and two v_subb (n = 32: two
+// subtractions in all, lo - 1 and hi - lo - borrow).  gfx950 wants two wait states between a VALU write of VCC and a VALU
+// read of it as the borrow, hence the s_nop inside the chain.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <uint32_t N>
+__device__ __forceinline__ uint64_t hash_sub_shl(uint64_t k)
+{
+	if constexpr (N == 32u) {
+		const uint32_t lo = (uint32_t)k, hi = (uint32_t)(k >> 32);
+		unsigned int b1, b2;
+		const uint32_t lo2 = __builtin_subc(lo, 1u, 0u, &b1);
+		const uint32_t hi2 = __builtin_subc(hi, lo, b1, &b2);
+		return ((uint64_t)hi2 << 32) | lo2;
+	} else {
+		uint64_t s = k << N;
+		asm("" : "+v"(s)); // (one 64-bit shift; taken apart it is a shift and a v_alignbit)
+		uint32_t lo, hi;
+		asm("s_mov_b64 vcc, -1\n\tv_subb_co_u32 %0, vcc, %2, %3, vcc\n\ts_nop 1\n\tv_subb_co_u32 %1, vcc, %4, %5, vcc"
+		    : "=&v"(lo), "=v"(hi)
+		    : "v"((uint32_t)k), "v"((uint32_t)s), "v"((uint32_t)(k >> 32)), "v"((uint32_t)(s >> 32))
+		    : "vcc");
+		return ((uint64_t)hi << 32) | lo;
+	}
+}
+#endif
+
 __host__ __device__ __forceinline__ uint64_t hash_code(uint64_t k)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
+	k = hash_sub_shl<32>(k);
+	k ^= (k >> 22);
+	k = hash_sub_shl<13>(k);
+	k ^= (k >> 8);
+	asm("v_lshl_add_u64 %0, %1, 3, %1" : "=v"(k) : "v"(k)); // k += k << 3 in one instruction (the compiler emits a 64-bit multiply by 9)
+	k ^= (k >> 15);
+	k = hash_sub_shl<27>(k);
+	k ^= (k >> 31);
+#else
 	k += ~(k << 32);
 	k ^= (k >> 22);
 	k += ~(k << 13);
 	k ^= (k >> 8);
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm("v_lshl_add_u64 %0, %1, 3, %1" : "=v"(k) : "v"(k)); // k += k << 3 in one instruction (the compiler emits a 64-bit multiply by 9)
-#else
 	k += (k << 3);
-#endif
 	k ^= (k >> 15);
 	k += ~(k << 27);
 	k ^= (k >> 31);
+#endif
 	return k;
 }
 

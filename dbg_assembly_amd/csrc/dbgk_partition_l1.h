@@ -24,13 +24,18 @@ namespace dbgk {
 // which still holds the sorted records of the tile before -- the ranks are taken in `hist` (one of two histograms), and mid(i) runs
 // in front of position i: the caller copies one run of the tile before out of the stage buffer there, its LDS read and its store in
 // the shadow of the position's arithmetic
+// ZERO_POSSIBLE = false (SPECIAL or ROLL32 forms at k >= 31, chosen per wave and tile by the caller, l1_no_zero_key): no window of the
+// wave can have the canonical key 0 -- none of the packed words its lanes funnel their windows from is all A / N or all T -- so the
+// positions carry no test for it: no 64-bit compare, no zero flag, and the bucket word straight from the slot.  Returns false.
 struct NoMid { __device__ __forceinline__ void operator()(uint32_t) const {} };
-template <int WIDE_D, int NPOS = 16, class LDS = ScatterLds, bool SPECIAL = false, bool ROLL32 = SPECIAL, bool IN_REGS = false, class Mid = NoMid>
+template <int WIDE_D, int NPOS = 16, class LDS = ScatterLds, bool SPECIAL = false, bool ROLL32 = SPECIAL, bool IN_REGS = false, bool ZERO_POSSIBLE = true,
+          class Mid = NoMid>
 __device__ __forceinline__ bool l1_positions(LDS &L, const PartGeom &G, Chunk16 c, uint32_t tid, uint64_t head_mask, uint32_t rc_shift,
                                              uint32_t rel_mask, uint32_t q_shift, uint32_t (&bkt)[16], uint64_t *rec = nullptr,
                                              uint32_t hist_off = 0u, Mid mid = Mid()) // hist_off: the histogram in use, in words from L.hist
 {
 	static_assert(!IN_REGS || SPECIAL || ROLL32 || WIDE_D == 3, "records in registers: regular tiles of a graph handle, or a KFREQ handle with direct blocks (nothing to patch)");
+	static_assert(ZERO_POSSIBLE || ((SPECIAL || ROLL32) && WIDE_D != 3), "the positions without the zero-key test: the 32-bit-roll forms of a graph handle");
 	uint32_t *const hh = L.hist + (IN_REGS ? hist_off : 0u);
 	// The per-position path assumes both neighbours exist; the ~2 % of positions at a read's
 	// first / last window are patched afterwards (rare per lane, so the loop stays lean).
@@ -109,8 +114,9 @@ __device__ __forceinline__ bool l1_positions(LDS &L, const PartGeom &G, Chunk16 
 			L.stage[i * kL1Threads + tid] = ((uint64_t)rec_hi << 32) | rec_lo;
 		}
 		const bool valid = SPECIAL ? true : (bool)((c.valid >> i) & 1u);
-		const bool zero = key == 0ull;
-		if constexpr (IN_REGS) { // (a select per position into one register: with the copy-out's branches between the positions the compiler
+		const bool zero = ZERO_POSSIBLE ? key == 0ull : false;
+		if constexpr (!ZERO_POSSIBLE) { // (nothing to note)
+		} else if constexpr (IN_REGS) { // (a select per position into one register: with the copy-out's branches between the positions the compiler
 			// would keep fifteen condition masks alive and OR them behind the loop)
 			zero_acc = zero ? 1u : zero_acc;
 			asm volatile("" : "+v"(zero_acc));
@@ -423,6 +429,22 @@ __device__ __forceinline__ uint32_t funnel_left(uint32_t hi, uint32_t lo, uint32
 	return sh ? ((hi << sh) | (lo >> (32u - sh))) : hi;
 }
 
+// The zero-key test per wave and tile instead of per position.  A canonical key is 0 only if its window is k times A / N (kbit = 0) or
+// k times T (rc = 0), and a run of k >= 31 equal bases covers a whole aligned group of 16 bases, one packed word: so no window of a
+// lane has key 0 unless one of the (16-aligned) packed words the lane funnels its windows from is 0x00000000 or 0xFFFFFFFF.
+// Conservative: a run that ends at a read boundary, or sixteen equal bases that are no run of k, only send the wave down the path
+// with the per-position test.  ASCII batches are packed on the way into LDS (N -> code 0) and are covered by the same words.
+// l1_word_runs: x + 1 is 0 or 1 for exactly those two words; the minimum over the lane's five words
+__device__ __forceinline__ uint32_t l1_word_runs(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4)
+{
+	return min(min(min(x0 + 1u, x1 + 1u), min(x2 + 1u, x3 + 1u)), x4 + 1u);
+}
+// (wave-uniform) true: the wave's positions need no zero-key test (l1_positions<..., ZERO_POSSIBLE = false>)
+__device__ __forceinline__ bool l1_no_zero_key(uint32_t k, uint32_t word_runs)
+{
+	return k >= 31u && __builtin_amdgcn_ballot_w64(word_runs < 2u) == 0ull;
+}
+
 // the side node of key 0 for one lane, from its decoded window (rare path, rolled)
 __device__ __forceinline__ void l1_key0_from_chunk(Chunk16 c, uint64_t head_mask, uint32_t rc_shift, uint32_t kf, Counters *ctr)
 {
@@ -722,7 +744,7 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 		for (int j = 0; j < SLds::kBpt; j++) L.hist[hist_off + SLds::kBpt * tid + j] = 0;
 	};
 	// a lane's window of 16 positions out of the tile's packed words
-	auto decode = [&](const RawU &raw) {
+	auto decode = [&](const RawU &raw, uint32_t *word_runs = nullptr) { // word_runs: l1_word_runs of the lane's packed words
 		const uint64_t p = raw.p;                        // flat position of the lane's first window
 		// the packed stream starts one base earlier (left neighbour) -- except at position 0, and (regular tiles, whose byte
 		// range starts ON a read start) for a read's first chunk, whose first window has no left neighbour anyway
@@ -734,6 +756,7 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 		const uint32_t rel = live ? (uint32_t)(s0 - raw.B0) : 0u;
 		const uint32_t d = min(rel >> 4, (uint32_t)kPkWords - 5u), sh = 2u * (rel & 15u);
 		const uint32_t x0 = UL.pk[d], x1 = UL.pk[d + 1], x2 = UL.pk[d + 2], x3 = UL.pk[d + 3], x4 = UL.pk[d + 4];
+		if (word_runs) *word_runs = l1_word_runs(x0, x1, x2, x3, x4);
 		const uint32_t X0 = funnel_left(x0, x1, sh), X1 = funnel_left(x1, x2, sh), X2 = funnel_left(x2, x3, sh), X3 = funnel_left(x3, x4, sh);
 		// stream Y starts at position p (X starts at p - 1 unless p == 0)
 		const uint32_t adv = no_prev ? 0u : 2u;
@@ -755,6 +778,7 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 	// a KFREQ handle with direct blocks (WIDE_D == 3, equal-length reads of any length: 32-bit records).
 	constexpr bool kRec32 = WIDE_D == 3;
 	constexpr bool kPipe = !LIN && DBG == 0 && (REG || K17 || (kRec32 && !RAGGED));
+	constexpr bool kZeroPerWave = K17 && !kRec32; // the 32-bit-roll forms of a graph handle: the zero-key test per wave and tile (k >= 31, l1_no_zero_key)
 	if constexpr (kPipe) {
 		L1Pipe<kRec32> pp(L, UL.gbase, G, P, ctr);
 		const uint32_t tid = pp.tid;
@@ -763,12 +787,21 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 			lds_barrier();
 		}
 		for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-			const Chunk16 c = decode(raw);
+			uint32_t word_runs = 0u;
+			const Chunk16 c = decode(raw, &word_runs);
 			uint32_t bkt[16];
 			uint64_t rec[16];
 			uint64_t slow = 0ull;
-			const bool zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur,
-			                                                                    [&](uint32_t i) { pp.copy_run(i, slow); });
+			auto mid = [&](uint32_t i) { pp.copy_run(i, slow); };
+			bool zero_seen;
+			if constexpr (kZeroPerWave) {
+				if (l1_no_zero_key(k, word_runs))
+					zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, false>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+				else
+					zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+			} else {
+				zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+			}
 			pp.copy_rest((uint32_t)C, slow); // (more than 16 C buckets; the full ones)
 			if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
 			if constexpr (!REG) { // (regular tiles: fetch works from the tile index alone)
@@ -816,12 +849,21 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 			lds_barrier();
 		}
 		for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-			const Chunk16 c = decode(raw);
+			uint32_t word_runs = 0u;
+			const Chunk16 c = decode(raw, &word_runs);
 			uint32_t bkt[16];
 			uint64_t rec[16];
 			uint32_t slow = 0u;
-			const bool zero_seen = l1_positions<WIDE_D, C, SLds, false, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, 0u,
-			                                                                     [&](uint32_t i) { copy_elem(i, slow); });
+			auto mid = [&](uint32_t i) { copy_elem(i, slow); };
+			bool zero_seen;
+			if constexpr (kRec32) {
+				zero_seen = l1_positions<WIDE_D, C, SLds, false, true, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, 0u, mid);
+			} else {
+				if (l1_no_zero_key(k, word_runs))
+					zero_seen = l1_positions<WIDE_D, C, SLds, false, true, true, false>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, 0u, mid);
+				else
+					zero_seen = l1_positions<WIDE_D, C, SLds, false, true, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, 0u, mid);
+			}
 			if (slow) copy_slow(slow);
 			if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
 			r0 += stride_r;
@@ -1139,7 +1181,7 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch
 		for (int j = 0; j < ScatterLds::kBpt; j++) L.hist[hist_off + ScatterLds::kBpt * tid + j] = 0;
 	};
 	// the lane's read -- the number of entries that begin at or before this lane -- and its window of C positions
-	auto decode = [&](uint64_t tile, const PrefixTile &Mx, uint32_t sb) {
+	auto decode = [&](uint64_t tile, const PrefixTile &Mx, uint32_t sb, uint32_t *word_runs = nullptr) { // word_runs: l1_word_runs of the lane's packed words
 		const uint32_t tid = fresh_tid();
 		const uint64_t lane_first = tile * kL1Threads, lane_end = min(lane_first + (uint64_t)kL1Threads, n_lanes);
 		const bool live = lane_first + tid < lane_end;
@@ -1176,6 +1218,7 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch
 			x0 = rb.packed[min(wi, last)]; x1 = rb.packed[min(wi + 1u, last)]; x2 = rb.packed[min(wi + 2u, last)];
 			x3 = rb.packed[min(wi + 3u, last)]; x4 = rb.packed[min(wi + 4u, last)];
 		}
+		if (word_runs) *word_runs = l1_word_runs(x0, x1, x2, x3, x4);
 		const uint32_t X0 = funnel_left(x0, x1, sh), X1 = funnel_left(x1, x2, sh), X2 = funnel_left(x2, x3, sh), X3 = funnel_left(x3, x4, sh);
 		const uint32_t adv = no_prev ? 0u : 2u;
 		const uint32_t Y0 = funnel_left(X0, X1, adv), Y1 = funnel_left(X1, X2, adv), Y2 = funnel_left(X2, X3, adv), Y3 = X3 << adv;
@@ -1206,12 +1249,21 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch
 			lds_barrier();
 		}
 		for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-			const Chunk16 c = decode(tile, M, sb);
+			uint32_t word_runs = 0u;
+			const Chunk16 c = decode(tile, M, sb, &word_runs);
 			uint32_t bkt[16];
 			uint64_t rec[16];
 			uint64_t slow = 0ull;
-			const bool zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur,
-			                                                                           [&](uint32_t i) { pp.copy_run(i, slow); });
+			auto mid = [&](uint32_t i) { pp.copy_run(i, slow); };
+			bool zero_seen;
+			if constexpr (WIDE_D == 3) {
+				zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, true, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+			} else { // the zero-key test per wave and tile (k >= 31, l1_no_zero_key)
+				if (l1_no_zero_key(k, word_runs))
+					zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, true, true, false>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+				else
+					zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, true, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+			}
 			pp.copy_rest((uint32_t)C, slow);
 			if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
 			// next tile: its words and entries travel across the barrier and the tail; the meta data of the tile after it as well
