@@ -299,6 +299,36 @@ __device__ __forceinline__ void scan_hist_per_wave(LDS &L, uint32_t n_buckets, u
 	}
 }
 
+// Inclusive prefix sum over the 64 lanes of a wave with DPP: four shifts inside the rows of 16, the last lane of row 0 / 2 broadcast
+// into row 1 / 3, the last lane of row 1 into rows 2 and 3 -- one VALU instruction per step, where __shfl_up is an LDS permute, a wait
+// for it and a select.  (Lanes a step does not reach add the `old` operand, 0.)
+__device__ __forceinline__ uint32_t wave_scan_inclusive_dpp(uint32_t v)
+{
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); // row_shr:1
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); // row_shr:2
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); // row_shr:4
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); // row_shr:8
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); // row_bcast:15 into rows 1 and 3
+	v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); // row_bcast:31 into rows 2 and 3
+	return v;
+}
+
+// scan_hist_per_wave for n_buckets <= 256 (every table for which level 1 takes the wave-per-bucket form with few buckets; cfg2: 144), as
+// straight-line code: lane l owns the four buckets [4 l, 4 l + 4) whatever n_buckets is -- buckets beyond n_buckets hold zero, the
+// histogram is cleared up to kMaxB -- reads them with one 16-byte load, scans the sums with DPP and writes the four first indices with
+// one 16-byte store from the same registers: no loop, no guard, no second read of the histogram, no LDS round trip inside the scan.
+constexpr uint32_t kScanStraightB = 256;
+template <class LDS>
+__device__ __forceinline__ void scan_hist_per_wave_256(LDS &L, uint32_t hist_off = 0u)
+{
+	static_assert(LDS::kMaxB >= (int)kScanStraightB && offsetof(LDS, hist) % 16 == 0 && offsetof(LDS, lbase) % 16 == 0, "16-byte LDS accesses of whole entries");
+	const uint32_t lane = fresh_tid() & 63u;
+	const uint4 v = *reinterpret_cast<const uint4 *>(L.hist + hist_off + 4u * lane); // (hist_off: a multiple of four words)
+	const uint32_t sum = (v.x + v.y) + (v.z + v.w);
+	const uint32_t run = wave_scan_inclusive_dpp(sum) - sum;
+	*reinterpret_cast<uint4 *>(L.lbase + 4u * lane) = make_uint4(run, run + v.x, run + v.x + v.y, run + v.x + v.y + v.z);
+}
+
 // Phases of the workgroup-wide bucket scatter of one tile (<= 16 records per thread).
 //   br[u] = (bucket << 16) | rank-within-bucket, bucket >= kMaxBuckets = no record
 

@@ -426,7 +426,11 @@ struct UniformLdsLin {
 
 __device__ __forceinline__ uint32_t funnel_left(uint32_t hi, uint32_t lo, uint32_t sh) // ({hi,lo} << sh) >> 32, sh in 0..30 (even)
 {
-	return sh ? ((hi << sh) | (lo >> (32u - sh))) : hi;
+	// (v_alignbit takes its shift modulo 32, so sh = 0 needs the select; written with shifts and an OR the compiler makes a funnel
+	// shift of it that is defined for every amount -- three instructions -- and still keeps the select: four per call instead of two)
+	uint32_t f = __builtin_amdgcn_alignbit(hi, lo, 32u - sh);
+	asm volatile("" : "+v"(f)); // a select, not a branch around the one instruction
+	return sh ? f : hi;
 }
 
 // The zero-key test per wave and tile instead of per position.  A canonical key is 0 only if its window is k times A / N (kbit = 0) or
@@ -483,6 +487,7 @@ struct L1Pipe {
 	static constexpr uint32_t kHist2 = (uint32_t)((offsetof(ScatterLds, desc) - offsetof(ScatterLds, hist)) / 4u);
 	static_assert(sizeof(ScatterLds::desc) >= sizeof(ScatterLds::hist), "the second histogram lives in the descriptor array");
 	static_assert(kL1MaxB <= kL1Threads, "thread b reserves bucket b");
+	static_assert(kHist2 % 4u == 0u, "scan_hist_per_wave_256 reads either histogram sixteen bytes at a time");
 	ScatterLds &L;
 	uint32_t *const gbase; // LDS, >= n1 words: a bucket's reserved place, from the thread that reserved it to the wave that copies the run
 	const PartGeom &G;
@@ -589,7 +594,8 @@ struct L1Pipe {
 		const uint32_t c_t = tid < G.n1 ? L.hist[cur + tid] : 0u;
 		const uint32_t g_t = c_t ? atomicAdd(&cnt[tid * G.n_sub], c_t) : 0u;
 		const uint32_t c_mine = lane < per_wave ? L.hist[cur + mine] : 0u;
-		scan_hist_per_wave(L, G.n1, cur);
+		if (G.n1 <= kScanStraightB) scan_hist_per_wave_256(L, cur); // (kernel-uniform) four buckets per lane, straight-line
+		else scan_hist_per_wave(L, G.n1, cur);
 		d_lo = (c_mine << 16) | (lane < per_wave ? L.lbase[mine] : 0u);
 		if (SURE && __builtin_amdgcn_ballot_w64(zero_seen) == 0ull) { // (wave-uniform) every record of every lane has a bucket
 			uint32_t at[C];
@@ -745,6 +751,34 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 	};
 	// a lane's window of 16 positions out of the tile's packed words
 	auto decode = [&](const RawU &raw, uint32_t *word_runs = nullptr) { // word_runs: l1_word_runs of the lane's packed words
+		if constexpr (REG && FULL) {
+			// Regular tiles that fill their lanes: every lane is live and every window valid, the lane's place in the tile's byte range
+			// is (its read in the tile) * L + C * chunk whatever the tile, and the masks depend on the chunk alone (first, last, other).
+			// No clamps, no `live` selects, nothing 64 bits wide, and nothing of the tile's RawU but its packed words.
+			const uint32_t t = fresh_tid();
+			const uint32_t cc = t & (U.Q - 1u);
+			const bool first = cc == 0u, last = cc == U.Q - 1u;
+			// (the packed stream starts one base before the lane's first window, the left neighbour -- except in a read's first chunk,
+			// whose first window has none; d + 4 <= tile_blocks + 2 < kPkWords: a tile is at most 1024 * 16 * (1 + (k - 1) / W) bases)
+			const uint32_t rel = (t >> U.lq) * U.L + (uint32_t)C * cc - (first ? 0u : 1u);
+			const uint32_t d = rel >> 4, sh = 2u * (rel & 15u);
+			const uint32_t x0 = UL.pk[d], x1 = UL.pk[d + 1], x2 = UL.pk[d + 2], x3 = UL.pk[d + 3], x4 = UL.pk[d + 4];
+			if (word_runs) *word_runs = l1_word_runs(x0, x1, x2, x3, x4);
+			const uint32_t X0 = funnel_left(x0, x1, sh), X1 = funnel_left(x1, x2, sh), X2 = funnel_left(x2, x3, sh), X3 = funnel_left(x3, x4, sh);
+			const uint32_t adv = first ? 0u : 2u;
+			const uint32_t Y0 = funnel_left(X0, X1, adv), Y1 = funnel_left(X1, X2, adv), Y2 = funnel_left(X2, X3, adv), Y3 = X3 << adv;
+			Chunk16 c;
+			c.lw = first ? (X0 >> 2) : X0;
+			c.kbit = ((((uint64_t)Y0 << 32) | Y1)) >> (64u - 2u * k);
+			c.rc = revcomp_kbit(c.kbit, (int)k);
+			const bool k32 = (k >> 4) == 2u; // (regular tiles: 17 <= k <= 32, the entering bases p + k .. p + k + 15 start in word 1, at k = 32 in word 2)
+			const uint32_t wsh = 2u * (k & 15u);
+			c.nb = funnel_left(k32 ? Y2 : Y1, k32 ? Y3 : Y2, wsh);
+			c.valid = (1u << C) - 1u;
+			c.has_r = last ? (1u << (C - 1)) - 1u : (1u << C) - 1u; // the read's last window has no right neighbour
+			c.has_l = first ? 0xFFFEu : 0xFFFFu;                    // its first window no left one
+			return c;
+		}
 		const uint64_t p = raw.p;                        // flat position of the lane's first window
 		// the packed stream starts one base earlier (left neighbour) -- except at position 0, and (regular tiles, whose byte
 		// range starts ON a read start) for a read's first chunk, whose first window has no left neighbour anyway
