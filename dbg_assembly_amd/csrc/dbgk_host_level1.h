@@ -2,92 +2,92 @@
 // one batch on the device: which level-1 / insert kernel form a batch takes (launch_batch) and its pre-passes
 #pragma once
 
-// queue mark + insert for a batch that is already in device memory
-// The lane-per-chunk-of-valid-windows level-1 kernel (k_extract_scatter_uniform) applies when nothing is
-// trimmed (longest read <= maxReadLen), the longest read has at least 64 windows (a tile's byte range
-// must fit its LDS image) and either
-//   * every read has that length and they lie back to back from offset 0 (EQUAL), or
-//   * lengths differ, but giving every read the lane count of the longest one still needs fewer lane
-//     slots than the flat kernel has positions (RAGGED: reads mostly full length, some shorter).
-// Returns 0 = flat kernel, 1 = equal, 2 = ragged; fills U.
-// lin (out): the linear level-1 form (8 windows per lane, linear copy-out) is to be used -- many level-1 buckets
-static int uniform_mode(const dbgk_handle *h, int64_t uniform_len, uint64_t len_max, uint64_t n_reads, uint64_t n_bases, int has_long,
-                        UniformGeom &U, bool &c15, bool &lin, bool &lin12)
+#include "dbgk_l1_form.h"
+
+// the decision (dbgk_l1_form.h) sees the kernels' tile geometry through this
+constexpr L1Limits kL1Limits{(uint32_t)kL1Threads, (uint32_t)kPkWords, kPrefixMaxW, kPrefixPipeMaxB, (uint32_t)kWL1Threads, kWPkWords, kWPipePkWords};
+static_assert(DBGK_L1_THREADS != 1024 || DBGK_L1_MAXB != 1024 || kL1Limits == L1Limits{}, "dbgk_l1_form.h: the defaults of L1Limits are the product build's geometry");
+
+// The launch tables: a row per instantiation of dbgk_l1_form.h's lists -- the form, the kernel, its dynamic LDS bytes.
+template <class Fn>
+struct L1Row {
+	L1Form form;
+	Fn fn;
+	uint32_t lds;
+};
+template <int DBG, int WIDE_D, int C, bool RAGGED, bool LIN, bool... REST>
+constexpr uint32_t uniform_lds() { return LIN ? sizeof(UniformLdsLin<LIN ? C : 8>) : sizeof(UniformLds); }
+#define DBGK_ROW(...) {l1_uniform(__VA_ARGS__), &k_extract_scatter_uniform<__VA_ARGS__>, uniform_lds<__VA_ARGS__>()},
+static const L1Row<decltype(&k_extract_scatter_uniform<>)> kL1UniformRows[] = {DBGK_L1_UNIFORM_ROWS(DBGK_ROW)};
+#undef DBGK_ROW
+#define DBGK_ROW(...) {l1_prefix(__VA_ARGS__), &k_extract_scatter_prefix<__VA_ARGS__>, sizeof(PrefixLds)},
+static const L1Row<decltype(&k_extract_scatter_prefix<>)> kL1PrefixRows[] = {DBGK_L1_PREFIX_ROWS(DBGK_ROW)};
+#undef DBGK_ROW
+#define DBGK_ROW(...) {l1_flat(__VA_ARGS__), &k_extract_scatter<__VA_ARGS__>, sizeof(ScatterLds)},
+static const L1Row<decltype(&k_extract_scatter<false>)> kL1FlatRows[] = {DBGK_L1_FLAT_ROWS(DBGK_ROW)};
+#undef DBGK_ROW
+#define DBGK_ROW(...) {l1_flat_lin(__VA_ARGS__), &k_extract_scatter_lin<__VA_ARGS__>, sizeof(ScatterLdsLin<8>)},
+static const L1Row<decltype(&k_extract_scatter_lin<false>)> kL1FlatLinRows[] = {DBGK_L1_FLAT_LIN_ROWS(DBGK_ROW)};
+#undef DBGK_ROW
+#define DBGK_ROW(...) {l1_wide_flat(__VA_ARGS__), &k_wide_scatter_l1<__VA_ARGS__>, sizeof(WL1Lds)},
+static const L1Row<decltype(&k_wide_scatter_l1<false, 0>)> kL1WideFlatRows[] = {DBGK_L1_WIDE_FLAT_ROWS(DBGK_ROW)};
+#undef DBGK_ROW
+#define DBGK_ROW(WD, PIPE) {l1_wide_uniform(WD, PIPE), &k_wide_scatter_l1_uniform<WD, PIPE>, PIPE ? sizeof(WL1PipeLds) : sizeof(WL1Lds)},
+static const L1Row<decltype(&k_wide_scatter_l1_uniform<0>)> kL1WideUniformRows[] = {DBGK_L1_WIDE_UNIFORM_ROWS(DBGK_ROW)};
+#undef DBGK_ROW
+
+// kernels with more than 64 KiB of dynamic LDS have to say so: every row of the tables
+template <class Fn, size_t N>
+static int l1_set_lds_attrs(const L1Row<Fn> (&rows)[N])
 {
-	lin = lin12 = false;
-	static const bool off = DBGK_EXPERIMENT_ENV("DBGK_L1_FLAT") != nullptr; // force the general kernel
-	static const int dbg_mode = DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE") ? atoi(DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE")) : 0;
-	if (off || has_long || n_reads == 0) return 0;
-	if (dbg_mode && (uniform_len != 150 || h->cfg.kmer_size != 31 || h->geom.size >= (1ull << 31))) return 0; // debug builds: cfg2's shape only
-	const uint64_t L = uniform_len > 0 ? (uint64_t)uniform_len : len_max, k = (uint64_t)h->cfg.kmer_size;
-	if (L > (uint64_t)h->cfg.max_read_len || L < k + 63 || L >= (1ull << 24)) return 0;
-	const uint32_t W = (uint32_t)(L - k + 1);
-	// 16 or 15 windows per lane, whichever leaves fewer empty slots at the end of a full-length read (W = 120: 15 -> none)
-	const uint32_t q16 = (W + 15u) / 16u, q15 = (W + 14u) / 15u;
-	c15 = q15 * 15u - W < q16 * 16u - W;
-	const uint64_t Q = c15 ? q15 : q16, C = c15 ? 15 : 16;
-	if (Q >= 2048 || n_reads * Q >= (1ull << 32)) return 0;
-	if (((uint64_t)kL1Threads / Q + 2) * L + 96 > (uint64_t)kPkWords * 16) return 0; // bytes a tile of kL1Threads lanes can touch
-	U.L = (uint32_t)L;
-	U.W = W;
-	U.Q = (uint32_t)Q;
-	U.qmagic = ((1u << 22) + U.Q - 1u) / U.Q;
-	U.n_lanes = n_reads * Q;
-	U.lq = 0;
-	U.tile_blocks = 0; // 0: no regular tiles
-	// (the regular form also assumes k >= 17 -- the rolls then only touch the high words -- and a graph handle: no KFREQ neighbour
-	// codes; reads that fill their lanes exactly, Q C == W, take its FULL instantiation, the others test every position's validity)
-	if ((Q & (Q - 1)) == 0 && Q <= (uint64_t)kL1Threads && (((uint64_t)kL1Threads / Q) * L) % 16 == 0 &&
-	    ((uint64_t)kL1Threads / Q) * L / 16 + 8 <= (uint64_t)kPkWords && k >= 17 && !h->kfreq) {
-		while ((1ull << U.lq) < Q) U.lq++;
-		U.tile_blocks = (uint32_t)(((uint64_t)kL1Threads / Q) * L / 16);
-	}
-	int mode;
-	if (uniform_len > 0) mode = n_bases == n_reads * L ? 1 : 0;
-	else mode = (double)(n_reads * Q * C) <= 0.93 * (double)n_bases ? 2 : 0; // mostly full-length reads: the ragged form
-	if (mode == 0) return 0;
-	// Many level-1 buckets (big tables; every rank of a multi-GPU job partitions by the GLOBAL table's buckets): the linear
-	// form, 12 (or 8) windows per lane.  Measured on cfg2's reads, level 1 in ms, wave-per-bucket / linear with 8 / with 12
-	// windows: n1 = 143: 5.57 / 6.76 / 6.05, 573: 8.13 / 7.57 / 6.81, 1023: 10.61 / 7.76 / 6.99 (287: 6.34 / 6.77 / -).
-	// DBGK_L1_LINEAR=0/1 forces the choice.
-	const int force = dbgk_hook("l1_linear") ? atoi(dbgk_hook("l1_linear")) : -1; // (read per batch: tests switch it)
-	// 12 or 8 windows per lane, whichever leaves fewer empty slots at the end of a read (W = 120: both none -> 12)
-	const uint64_t q12 = (W + 11u) / 12u, q8 = (W + 7u) / 8u;
-	lin12 = q12 * 12u - W <= q8 * 8u - W;
-	if (const char *e = DBGK_EXPERIMENT_ENV("DBGK_L1_LINEAR_C")) lin12 = atoi(e) == 12; // measurements
-	const uint64_t QL = lin12 ? q12 : q8, CL = lin12 ? 12 : 8;
-	bool fits = QL < 2048 && n_reads * QL < (1ull << 32) && ((uint64_t)kL1Threads / QL + 2) * L + 96 <= (uint64_t)kPkWords * 16;
-	if (mode == 2) fits = fits && (double)(n_reads * QL * CL) <= 0.93 * (double)n_bases;
-	// (round 5, both forms pipelined, profiles/r05_l1_forms_by_buckets.txt, wave-per-bucket / linear with 12 windows: n1 = 144: 4.34 / 5.08,
-	// 287: 4.80 / 5.26, 573: 6.83 / 5.87, 1023: 12.27 / 6.11 -- the lines cross near 330)
-	if (fits && (force == 1 || (force < 0 && h->geom.n1 > 320u))) {
-		lin = true;
-		U.tile_blocks = 0;
-		U.Q = (uint32_t)QL;
-		U.qmagic = ((1u << 22) + U.Q - 1u) / U.Q;
-		U.n_lanes = n_reads * QL;
-	}
-	return mode;
+	for (const L1Row<Fn> &r : rows)
+		HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(r.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds));
+	return DBGK_OK;
+}
+static int l1_register_lds(bool wide)
+{
+	int rc;
+	if (wide) return (rc = l1_set_lds_attrs(kL1WideFlatRows)) ? rc : l1_set_lds_attrs(kL1WideUniformRows);
+	if ((rc = l1_set_lds_attrs(kL1UniformRows)) || (rc = l1_set_lds_attrs(kL1PrefixRows)) || (rc = l1_set_lds_attrs(kL1FlatRows))) return rc;
+	return l1_set_lds_attrs(kL1FlatLinRows);
 }
 
-// WIDE record path: can this batch take the equal-length level-1 kernel (k_wide_scatter_l1_uniform)?
-static int wide_uniform_mode(const dbgk_handle *h, int64_t uniform_len, uint64_t n_reads, uint64_t n_bases, int has_long, WUniformGeom &U)
+// launch the row of `form` with that row's LDS size; a form without a row is an error, never another kernel
+template <class Fn, size_t N, class... Args>
+static int l1_launch(const L1Row<Fn> (&rows)[N], const L1Form &form, uint64_t grid, int threads, hipStream_t stream, Args... args)
 {
-	static const bool off = DBGK_EXPERIMENT_ENV("DBGK_L1_FLAT") != nullptr; // force the general kernel
-	if (off || has_long || n_reads == 0 || uniform_len <= 0) return 0;
-	const uint64_t L = (uint64_t)uniform_len, k = (uint64_t)h->cfg.kmer_size;
-	if (L > (uint64_t)h->cfg.max_read_len || L < k || L >= (1ull << 24) || n_bases != n_reads * L) return 0;
-	const uint32_t W = (uint32_t)(L - k + 1);
-	const uint64_t Q = (W + 7u) / 8u;
-	if (Q >= 2048 || n_reads * Q >= (1ull << 40)) return 0;
-	if (((uint64_t)kWL1Threads / Q + 2) * L + 96 > (uint64_t)(kWPkWords - 8u) * 16) return 0; // bytes a tile of 1024 lanes can touch
-	if ((double)(n_reads * Q * 8) > 0.93 * (double)n_bases) return 0; // (k small against L: the flat kernel wastes little)
-	U.L = (uint32_t)L;
-	U.W = W;
-	U.Q = (uint32_t)Q;
-	U.qmagic = ((1u << 22) + U.Q - 1u) / U.Q;
-	U.n_lanes = n_reads * Q;
-	return 1;
+	for (const L1Row<Fn> &r : rows)
+		if (r.form == form) {
+			hipLaunchKernelGGL(r.fn, dim3((uint32_t)grid), dim3(threads), r.lds, stream, args...);
+			return DBGK_OK;
+		}
+	char text[192];
+	l1_form_text(form, text, sizeof text);
+	g_last_error = std::string("no level-1 kernel for the form ") + text;
+	return DBGK_ERR_ARG;
+}
+
+// the handle's part of the facts, the hooks and the experiment switches: read once per batch
+static L1Facts l1_facts(const dbgk_handle *h, bool wrec)
+{
+	L1Facts f;
+	f.lim = kL1Limits;
+	f.part = h->part; f.seed = h->seed; f.kfreq = h->kfreq; f.wide = h->wide; f.wrec = wrec;
+	f.kmer_size = h->cfg.kmer_size;
+	f.max_read_len = (uint64_t)h->cfg.max_read_len;
+	f.n1 = h->geom.n1; f.kf = h->geom.kf; f.geom_size = h->geom.size; f.size = h->size;
+	auto hook_int = [](const char *name) { const char *v = dbgk_hook(name); return v ? atoi(v) : -1; };
+	f.l1_linear = hook_int("l1_linear");
+	f.l1_prefix = hook_int("l1_prefix");
+	f.l1_plain = dbgk_hook("l1_plain") != nullptr;
+	f.wide_l1_plain = dbgk_hook("wide_l1_plain") != nullptr;
+	f.l1_flat = DBGK_EXPERIMENT_ENV("DBGK_L1_FLAT") != nullptr;
+	const char *dbg = DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE"), *lin_c = DBGK_EXPERIMENT_ENV("DBGK_L1_LINEAR_C");
+	f.dbg_set = dbg != nullptr;
+	f.dbg_mode = dbg ? atoi(dbg) : 0;
+	f.no_reg = DBGK_EXPERIMENT_ENV("DBGK_L1_NO_REG") != nullptr;
+	f.lin_c = lin_c ? (atoi(lin_c) == 12 ? 12 : 8) : 0;
+	return f;
 }
 
 // scratch of the prefix form for a batch of n_reads reads / n_bases bases (grown as needed; the stream is idle when it grows)
@@ -124,6 +124,65 @@ static int ensure_prefix_scratch(dbgk_handle *h, uint64_t n_reads, uint64_t n_ba
 
 static int early_l2(dbgk_handle *h);
 
+// the lane prefix of a batch for the prefix form: three short kernels over the offsets, then the tiles' descriptors
+template <int CC>
+static void launch_prefix_passes(dbgk_handle *h, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases)
+{
+	const uint32_t n_blocks = (uint32_t)((n_reads + kPrefixBlock * kPrefixItems - 1) / (kPrefixBlock * kPrefixItems));
+	const uint32_t tiles_max = (uint32_t)std::min<uint64_t>((n_bases / 15 + n_reads) / kL1Threads + 1, h->pf_cap_tiles);
+	const uint32_t k = (uint32_t)h->cfg.kmer_size, max_len = (uint32_t)h->cfg.max_read_len;
+	hipLaunchKernelGGL((k_prefix_count<CC>), dim3(n_blocks), dim3(kPrefixBlock), 0, h->stream, d_offsets, n_reads, k, max_len, h->pf_bsum);
+	hipLaunchKernelGGL(k_prefix_blocks, dim3(1), dim3(kPrefixBlock), 0, h->stream, h->pf_bsum, n_blocks, h->pf_tot);
+	hipLaunchKernelGGL((k_prefix_emit<CC>), dim3(n_blocks), dim3(kPrefixBlock), 0, h->stream, d_offsets, n_reads, k, max_len, h->pf_bsum, h->pf_ent,
+	                   h->pf_tile_first, h->d_ctr);
+	hipLaunchKernelGGL((k_prefix_tiles<CC>), dim3((tiles_max + 255) / 256), dim3(256), 0, h->stream, h->pf_ent, h->pf_tile_first, h->pf_tot, k, n_bases,
+	                   h->pf_tiles);
+}
+
+// level 1 of the record engines: the launches of the batch's plan, each through its family's table
+static int launch_l1(dbgk_handle *h, const L1Plan &plan, const ReadBatch &rb, const uint64_t *d_offsets, uint64_t n_reads)
+{
+	for (int i = 0; i < plan.n; i++) {
+		const L1Launch &l = plan.launch[i];
+		const L1Geom &g = l.geom;
+		const bool wide = l.form.family == L1Family::WideFlat || l.form.family == L1Family::WideUniform;
+		const uint64_t wgs = (uint64_t)h->n_cu * (wide ? 1 : l1_wgs_per_cu()); // 140 KiB of LDS and more: one workgroup per CU
+		const uint64_t grid = l.tiles ? std::min(l.tiles, wgs) : wgs;
+		int rc = DBGK_ERR_ARG;
+		switch (l.form.family) {
+		case L1Family::Uniform: {
+			ReadBatch r = rb;
+			if (l.n_reads != n_reads) { // regular tiles / the reads behind them: equal lengths, the launch's own reads
+				if (r.packed) r.packed += l.first_read * g.L / 16; // (a whole number of words: a tile is a multiple of 16 bases)
+				else r.bases += l.first_read * g.L;
+				r.n_bases = l.n_reads * g.L;
+			}
+			rc = l1_launch(kL1UniformRows, l.form, grid, kL1Threads, h->stream, r, UniformGeom{g.L, g.W, g.Q, g.qmagic, g.n_lanes, g.lq, g.tile_blocks},
+			               d_offsets, h->geom, h->store, h->d_ctr);
+			break;
+		}
+		case L1Family::Prefix:
+			rc = l1_launch(kL1PrefixRows, l.form, grid, kL1Threads, h->stream, rb, h->pf_ent, h->pf_tiles, h->pf_tot, h->geom, h->store, h->d_ctr);
+			break;
+		case L1Family::Flat:
+			rc = l1_launch(kL1FlatRows, l.form, grid, kL1Threads, h->stream, rb, h->geom, h->store, h->d_ctr);
+			break;
+		case L1Family::FlatLin:
+			rc = l1_launch(kL1FlatLinRows, l.form, grid, kL1Threads, h->stream, rb, h->geom, h->store, h->d_ctr);
+			break;
+		case L1Family::WideFlat:
+			rc = l1_launch(kL1WideFlatRows, l.form, grid, kWL1Threads, h->stream, rb, h->wgeom, h->wstore, h->wref(), h->d_ctr);
+			break;
+		case L1Family::WideUniform:
+			rc = l1_launch(kL1WideUniformRows, l.form, grid, kWL1Threads, h->stream, rb, WUniformGeom{g.L, g.W, g.Q, g.qmagic, g.n_lanes}, h->wgeom,
+			               h->wstore, h->wref(), h->d_ctr);
+			break;
+		}
+		if (rc) return rc;
+	}
+	return DBGK_OK;
+}
+
 static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                         uint64_t n_bases, uint32_t *d_start, uint32_t *d_dead, int has_long /* 0,1 or -1 = ask device */,
                         int64_t uniform_len = -1 /* every read this long; 0 = lengths differ; -1 = ask device */,
@@ -144,9 +203,6 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 	// The read-boundary bitmaps are what the general kernels navigate by; the PARTITION engine's level-1 kernel for
 	// (nearly) equal-length reads does without them, so for such a batch only the statistics are taken.  A device
 	// batch tells its shape only after those statistics: the bitmaps follow in a second pass if they are needed.
-	UniformGeom U{};
-	bool c15 = false, lin8 = false, lin12 = false;
-	int umode = -1; // not decided yet
 	auto mark_bits = [&](int with_stats) -> int {
 		HIPCHK(hipMemsetAsync(d_start, 0, words * 4, h->stream));
 		if (has_long != 0) HIPCHK(hipMemsetAsync(d_dead, 0, words * 4, h->stream));
@@ -155,9 +211,20 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 		return DBGK_OK;
 	};
 	const bool wrec = h->wide && h->wpart && !h->wbuilt; // WIDE handle that is still collecting records
-	WUniformGeom WU{};
-	auto decide_umode = [&]() {
-		return wrec ? wide_uniform_mode(h, uniform_len, n_reads, n_bases, has_long, WU) : uniform_mode(h, uniform_len, len_max, n_reads, n_bases, has_long, U, c15, lin8, lin12);
+	L1Facts facts = l1_facts(h, wrec);
+	facts.n_reads = n_reads;
+	facts.n_bases = n_bases;
+	facts.packed = d_packed != nullptr;
+	L1Plan plan{};
+	int umode = -1; // not decided yet
+	bool use_prefix = false; // the prefix form (prefix_wanted) instead of the flat or the ragged one
+	auto decide = [&]() { // (the batch's shape is known)
+		facts.has_long = has_long;
+		facts.uniform_len = uniform_len;
+		facts.len_max = len_max;
+		plan = l1_plan(facts);
+		umode = plan.umode;
+		use_prefix = plan.prefix;
 	};
 	// A batch of equal-length reads that came WITHOUT offsets (dbgk_push_reads_packed_uniform*): the equal-length level-1 forms of the
 	// PARTITION / WIDE record engines never look at offsets -- the totals are added by a one-thread kernel and nothing else runs in
@@ -179,39 +246,22 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 		return DBGK_OK;
 	};
 	const bool may_skip_bits = (h->part && !h->seed) || wrec;
-	// The PREFIX form of level 1 (k_extract_scatter_prefix: every read exactly the lanes its windows need, reads of any lengths,
-	// trimmed ones included) takes what would otherwise go through the flat kernel -- a fifth of whose positions straddle a
-	// read boundary at 150 bases and k = 31 -- and the batches of the ragged form as well; not with many level-1 buckets (the
-	// linear forms), not for reads of more than 4 M windows.  DBGK_L1_PREFIX=0 switches it off (ragged / flat as before).
-	const int prefix_env = dbgk_hook("l1_prefix") ? atoi(dbgk_hook("l1_prefix")) : -1; // (read per batch: tests switch it)
-	bool use_prefix = false;
-	auto prefix_wanted = [&](int um) {
-		static const bool flat_only = DBGK_EXPERIMENT_ENV("DBGK_L1_FLAT") != nullptr;
-		static const bool dbg = DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE") != nullptr;
-		const int force_lin = dbgk_hook("l1_linear") ? atoi(dbgk_hook("l1_linear")) : -1;
-		if (!h->part || h->seed || wrec || flat_only || dbg || prefix_env == 0) return false;
-		if (force_lin == 1 || (force_lin < 0 && h->geom.n1 > 320u)) return false;
-		if (len_max > (uint64_t)kPrefixMaxW || n_bases / 15 + n_reads >= (1ull << 32)) return false;
-		return um == 0 || um == 2; // (measured on cfg2t, level 1 per step: prefix 5.32 ms, ragged 5.72, flat 6.05 + 0.14 of bitmaps: profiles/r04_cfg2t_level1_forms_ab.json)
-	};
-	if (may_skip_bits && has_long >= 0 && uniform_len >= 0) {
-		umode = decide_umode();
-		use_prefix = prefix_wanted(umode);
-	}
+	if (may_skip_bits && has_long >= 0 && uniform_len >= 0) decide();
 	if (no_offsets && umode == 1) { // (umode 1 = equal lengths, nothing trimmed: every read has uniform_len - k + 1 windows)
 		const unsigned long long w = uniform_len >= h->cfg.kmer_size ? (unsigned long long)(uniform_len - h->cfg.kmer_size + 1) * n_reads : 0ull;
 		hipLaunchKernelGGL(k_add_totals, dim3(1), dim3(64), 0, h->stream, h->d_ctr, w, w);
-	} else if (no_offsets) {
-		rc = make_offsets();
-		if (rc) return rc;
-	}
-	if (no_offsets && umode == 1) {
-	} else if (may_skip_bits && (umode > 0 || umode < 0 || use_prefix)) {
-		hipLaunchKernelGGL(k_mark, dim3(grid_for(h, n_reads)), dim3(kBlock), 0, h->stream, d_offsets, n_reads, n_bases, h->cfg.kmer_size,
-		                   h->cfg.max_read_len, (uint32_t *)nullptr, (uint32_t *)nullptr, h->d_ctr, 1); // statistics only
 	} else {
-		rc = mark_bits(1);
-		if (rc) return rc;
+		if (no_offsets) {
+			rc = make_offsets();
+			if (rc) return rc;
+		}
+		if (may_skip_bits && (umode != 0 || use_prefix)) {
+			hipLaunchKernelGGL(k_mark, dim3(grid_for(h, n_reads)), dim3(kBlock), 0, h->stream, d_offsets, n_reads, n_bases, h->cfg.kmer_size,
+			                   h->cfg.max_read_len, (uint32_t *)nullptr, (uint32_t *)nullptr, h->d_ctr, 1); // statistics only
+		} else {
+			rc = mark_bits(1);
+			if (rc) return rc;
+		}
 	}
 	if (h->seed && n_bases)
 		hipLaunchKernelGGL(k_mark_n, dim3(grid_for(h, (n_bases + 31) >> 5)), dim3(kBlock), 0, h->stream, d_bases, n_bases, d_dead);
@@ -226,8 +276,7 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 		}
 	}
 	if (may_skip_bits && umode < 0) {
-		umode = decide_umode();
-		use_prefix = prefix_wanted(umode);
+		decide();
 		if (umode == 0 && !use_prefix) { // the general kernel after all: it needs the bitmaps
 			rc = mark_bits(0);
 			if (rc) return rc;
@@ -246,36 +295,10 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 	if (rc) return rc;
 	if (h->seed) {
 		hipLaunchKernelGGL(k_seed_insert, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, d_offsets, n_reads, id_base, h->tref(), h->d_ctr);
-	} else if (wrec && umode > 0) {
-		h->uniform_launches++;
-		const int grid = (int)std::min<uint64_t>((WU.n_lanes + kWL1Threads - 1) / kWL1Threads, (uint64_t)h->n_cu);
-		const int wd = h->size >= (1ull << 32) ? 2 : (h->size >= (1ull << 31) ? 1 : 0); // how hash / size is computed
-		// the pipelined form keeps a tile's packed words beside the stage buffer: taken when the bytes a tile of 1024 lanes can touch fit there
-		const bool wpipe = !dbgk_hook("wide_l1_plain") &&
-		                   ((uint64_t)kWL1Threads / WU.Q + 2) * WU.L + 96 <= (uint64_t)(kWPipePkWords - 8u) * 16;
-#define DBGK_LAUNCH_WIDE_L1U(WD)                                                                                                                    \
-	do {                                                                                                                                            \
-		if (wpipe)                                                                                                                                  \
-			hipLaunchKernelGGL((k_wide_scatter_l1_uniform<WD, true>), dim3(grid), dim3(kWL1Threads), sizeof(WL1PipeLds), h->stream, rb, WU, h->wgeom, \
-			                   h->wstore, h->wref(), h->d_ctr);                                                                                     \
-		else                                                                                                                                        \
-			hipLaunchKernelGGL((k_wide_scatter_l1_uniform<WD, false>), dim3(grid), dim3(kWL1Threads), sizeof(WL1Lds), h->stream, rb, WU, h->wgeom,    \
-			                   h->wstore, h->wref(), h->d_ctr);                                                                                     \
-	} while (0)
-		if (wd == 2) DBGK_LAUNCH_WIDE_L1U(2); else if (wd == 1) DBGK_LAUNCH_WIDE_L1U(1); else DBGK_LAUNCH_WIDE_L1U(0);
-#undef DBGK_LAUNCH_WIDE_L1U
 	} else if (wrec) {
-		const int grid = (int)std::min<uint64_t>((n_chunks + kWL1Threads - 1) / kWL1Threads, (uint64_t)h->n_cu);
-		const int wd = h->size >= (1ull << 32) ? 2 : (h->size >= (1ull << 31) ? 1 : 0); // how hash / size is computed
-#define DBGK_LAUNCH_WIDE_L1(DEAD, WD)                                                                                                          \
-	hipLaunchKernelGGL((k_wide_scatter_l1<DEAD, WD>), dim3(grid), dim3(kWL1Threads), sizeof(WL1Lds), h->stream, rb, h->wgeom, h->wstore, h->wref(), \
-	                   h->d_ctr)
-		if (has_long) {
-			if (wd == 2) DBGK_LAUNCH_WIDE_L1(true, 2); else if (wd == 1) DBGK_LAUNCH_WIDE_L1(true, 1); else DBGK_LAUNCH_WIDE_L1(true, 0);
-		} else {
-			if (wd == 2) DBGK_LAUNCH_WIDE_L1(false, 2); else if (wd == 1) DBGK_LAUNCH_WIDE_L1(false, 1); else DBGK_LAUNCH_WIDE_L1(false, 0);
-		}
-#undef DBGK_LAUNCH_WIDE_L1
+		if (umode > 0) h->uniform_launches++;
+		rc = launch_l1(h, plan, rb, d_offsets, n_reads);
+		if (rc) return rc;
 	} else if (h->wide) {
 		rc = wide_ensure_zero(h);
 		if (rc) return rc;
@@ -288,175 +311,22 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 			hipLaunchKernelGGL(k_extract_count<true>, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, reinterpret_cast<uint32_t *>(h->counts));
 		else
 			hipLaunchKernelGGL(k_extract_count<false>, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, reinterpret_cast<uint32_t *>(h->counts));
-	} else if (h->part && use_prefix) {
-		// lane prefix of the batch (three short kernels over the offsets), the batch itself as 2-bit words, then level 1
-		h->prefix_launches++;
-		rc = ensure_prefix_scratch(h, n_reads, n_bases, d_packed == nullptr);
-		if (rc) return rc;
-		if (!d_packed) {
-			hipLaunchKernelGGL(k_pack_bases, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, d_bases, n_bases, h->pf_packed, h->d_ctr);
-			rb.packed = h->pf_packed;
-		}
-		const uint32_t W_max = (uint32_t)std::min<uint64_t>(len_max, (uint64_t)h->cfg.max_read_len) >= (uint32_t)h->cfg.kmer_size
-		                           ? (uint32_t)std::min<uint64_t>(len_max, (uint64_t)h->cfg.max_read_len) - (uint32_t)h->cfg.kmer_size + 1u : 1u;
-		const bool pc15 = (W_max + 14u) / 15u * 15u - W_max < (W_max + 15u) / 16u * 16u - W_max; // 15 or 16 windows per lane: fewer empty slots for a full-length read
-		const uint32_t n_blocks = (uint32_t)((n_reads + kPrefixBlock * kPrefixItems - 1) / (kPrefixBlock * kPrefixItems));
-		const uint32_t tiles_max = (uint32_t)std::min<uint64_t>((n_bases / 15 + n_reads) / kL1Threads + 1, h->pf_cap_tiles);
-		const int wide = (h->geom.kf == 2u || h->geom.size >= (1ull << 32)) ? 2 : (h->geom.size >= (1ull << 31) ? 1 : 0);
-		const int grid_p = (int)((uint64_t)h->n_cu * l1_wgs_per_cu());
-#define DBGK_LAUNCH_PREFIX(WIDE, CC)                                                                                                              \
-	do {                                                                                                                                          \
-		hipLaunchKernelGGL((k_prefix_count<CC>), dim3(n_blocks), dim3(kPrefixBlock), 0, h->stream, d_offsets, n_reads, (uint32_t)h->cfg.kmer_size,   \
-		                   (uint32_t)h->cfg.max_read_len, h->pf_bsum);                                                                            \
-		hipLaunchKernelGGL(k_prefix_blocks, dim3(1), dim3(kPrefixBlock), 0, h->stream, h->pf_bsum, n_blocks, h->pf_tot);                          \
-		hipLaunchKernelGGL((k_prefix_emit<CC>), dim3(n_blocks), dim3(kPrefixBlock), 0, h->stream, d_offsets, n_reads, (uint32_t)h->cfg.kmer_size,    \
-		                   (uint32_t)h->cfg.max_read_len, h->pf_bsum, h->pf_ent, h->pf_tile_first, h->d_ctr);                                     \
-		hipLaunchKernelGGL((k_prefix_tiles<CC>), dim3((tiles_max + 255) / 256), dim3(256), 0, h->stream, h->pf_ent, h->pf_tile_first, h->pf_tot,    \
-		                   (uint32_t)h->cfg.kmer_size, n_bases, h->pf_tiles);                                                                     \
-		if (h->cfg.kmer_size >= 17 && h->geom.kf != 2u && h->geom.n1 <= kPrefixPipeMaxB && !dbgk_hook("l1_plain")) /* the pipelined tile loop */   \
-			hipLaunchKernelGGL((k_extract_scatter_prefix<WIDE, CC, true>), dim3(grid_p), dim3(kL1Threads), sizeof(PrefixLds), h->stream, rb, h->pf_ent, \
-			                   h->pf_tiles, h->pf_tot, h->geom, h->store, h->d_ctr);                                                              \
-		else                                                                                                                                      \
-			hipLaunchKernelGGL((k_extract_scatter_prefix<WIDE, CC, false>), dim3(grid_p), dim3(kL1Threads), sizeof(PrefixLds), h->stream, rb, h->pf_ent, \
-			                   h->pf_tiles, h->pf_tot, h->geom, h->store, h->d_ctr);                                                              \
-	} while (0)
-		if (pc15) { if (wide == 2) DBGK_LAUNCH_PREFIX(2, 15); else if (wide == 1) DBGK_LAUNCH_PREFIX(1, 15); else DBGK_LAUNCH_PREFIX(0, 15); }
-		else { if (wide == 2) DBGK_LAUNCH_PREFIX(2, 16); else if (wide == 1) DBGK_LAUNCH_PREFIX(1, 16); else DBGK_LAUNCH_PREFIX(0, 16); }
-#undef DBGK_LAUNCH_PREFIX
-	} else if (h->part && umode > 0) {
-		h->uniform_launches++;
-		const int wide = (h->geom.kf == 2u || h->geom.size >= (1ull << 32)) ? 2 : (h->geom.size >= (1ull << 31) ? 1 : 0); // (direct blocks: the 64-bit slot path)
-		const bool ragged = umode == 2;
-		// equal lengths, ragged: the pipelined tile loop (32-bit rolls; 64-bit records -- a KFREQ handle with direct blocks has its own instantiation)
-		const bool k17 = h->cfg.kmer_size >= 17 && h->geom.kf != 2u && !dbgk_hook("l1_plain");
-#define DBGK_LAUNCH_UNIFORM(WIDE, CC, RAG)                                                                                                   \
-	hipLaunchKernelGGL((k_extract_scatter_uniform<0, WIDE, CC, RAG>), dim3(grid), dim3(kL1Threads), sizeof(UniformLds), h->stream, rb, U, \
-	                   d_offsets, h->geom, h->store, h->d_ctr)
-#define DBGK_LAUNCH_UNIFORM_K17(WIDE, CC, RAG)                                                                                                    \
-	hipLaunchKernelGGL((k_extract_scatter_uniform<0, WIDE, CC, RAG, false, false, false, true, true>), dim3(grid), dim3(kL1Threads), sizeof(UniformLds), \
-	                   h->stream, rb, U, d_offsets, h->geom, h->store, h->d_ctr)
-#define DBGK_LAUNCH_UNIFORM_W(WIDE)                                    \
-	do {                                                               \
-		if (k17 && c15 && ragged) DBGK_LAUNCH_UNIFORM_K17(WIDE, 15, true); \
-		else if (k17 && ragged) DBGK_LAUNCH_UNIFORM_K17(WIDE, 16, true);   \
-		else if (k17 && c15) DBGK_LAUNCH_UNIFORM_K17(WIDE, 15, false);     \
-		else if (k17) DBGK_LAUNCH_UNIFORM_K17(WIDE, 16, false);            \
-		else if (c15 && ragged) DBGK_LAUNCH_UNIFORM(WIDE, 15, true);       \
-		else if (ragged) DBGK_LAUNCH_UNIFORM(WIDE, 16, true);              \
-		else if (c15) DBGK_LAUNCH_UNIFORM(WIDE, 15, false);                \
-		else DBGK_LAUNCH_UNIFORM(WIDE, 16, false);                     \
-	} while (0)
-#define DBGK_LAUNCH_UNIFORM8(WIDE, CC, RAG)                                                                                                               \
-	do {                                                                                                                                                  \
-		if (k17) /* the pipelined linear form */                                                                                                          \
-			hipLaunchKernelGGL((k_extract_scatter_uniform<0, WIDE, CC, RAG, true, false, false, true, true>), dim3(grid), dim3(kL1Threads),                \
-			                   sizeof(UniformLdsLin<CC>), h->stream, rb, U, d_offsets, h->geom, h->store, h->d_ctr);                                      \
-		else                                                                                                                                              \
-			hipLaunchKernelGGL((k_extract_scatter_uniform<0, WIDE, CC, RAG, true>), dim3(grid), dim3(kL1Threads), sizeof(UniformLdsLin<CC>), h->stream, rb, \
-			                   U, d_offsets, h->geom, h->store, h->d_ctr);                                                                                \
-	} while (0)
-		static const int dbg_mode_u = DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE") ? atoi(DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE")) : 0;
-		static const bool no_reg = DBGK_EXPERIMENT_ENV("DBGK_L1_NO_REG") != nullptr; // A/B: the general form everywhere
-		bool rest_only = false;
-		if (!dbg_mode_u && !no_reg && !dbgk_hook("l1_plain") && umode == 1 && !lin8 && U.tile_blocks) {
-			// regular tiles: kL1Threads / Q whole reads each, from a 16-byte boundary; the reads behind the last whole tile
-			// (fewer than kL1Threads / Q) go through the general form below
-			const uint64_t reads_per_tile = (uint64_t)kL1Threads / U.Q, full_tiles = n_reads / reads_per_tile;
-			if (full_tiles) {
-				UniformGeom UR = U;
-				UR.n_lanes = full_tiles * kL1Threads;
-				ReadBatch rr = rb;
-				rr.n_bases = full_tiles * reads_per_tile * U.L;
-				const int grid_r = (int)std::min<uint64_t>(full_tiles, (uint64_t)h->n_cu * l1_wgs_per_cu());
-				const bool full = (uint64_t)U.Q * (c15 ? 15u : 16u) == (uint64_t)U.W; // the reads fill their lanes exactly
-#define DBGK_LAUNCH_REG(WIDE, CC, PK)                                                                                                                  \
-	do {                                                                                                                                               \
-		if (full)                                                                                                                                      \
-			hipLaunchKernelGGL((k_extract_scatter_uniform<0, WIDE, CC, false, false, true, PK, true>), dim3(grid_r), dim3(kL1Threads), sizeof(UniformLds),  \
-			                   h->stream, rr, UR, d_offsets, h->geom, h->store, h->d_ctr);                                                            \
-		else                                                                                                                                           \
-			hipLaunchKernelGGL((k_extract_scatter_uniform<0, WIDE, CC, false, false, true, PK, false>), dim3(grid_r), dim3(kL1Threads), sizeof(UniformLds), \
-			                   h->stream, rr, UR, d_offsets, h->geom, h->store, h->d_ctr);                                                            \
-	} while (0)
-				if (d_packed) {
-					if (c15) { if (wide == 2) DBGK_LAUNCH_REG(2, 15, true); else if (wide == 1) DBGK_LAUNCH_REG(1, 15, true); else DBGK_LAUNCH_REG(0, 15, true); }
-					else { if (wide == 2) DBGK_LAUNCH_REG(2, 16, true); else if (wide == 1) DBGK_LAUNCH_REG(1, 16, true); else DBGK_LAUNCH_REG(0, 16, true); }
-				} else if (c15) { if (wide == 2) DBGK_LAUNCH_REG(2, 15, false); else if (wide == 1) DBGK_LAUNCH_REG(1, 15, false); else DBGK_LAUNCH_REG(0, 15, false); }
-				else { if (wide == 2) DBGK_LAUNCH_REG(2, 16, false); else if (wide == 1) DBGK_LAUNCH_REG(1, 16, false); else DBGK_LAUNCH_REG(0, 16, false); }
-#undef DBGK_LAUNCH_REG
-				const uint64_t done_reads = full_tiles * reads_per_tile;
-				if (d_packed) rb.packed += done_reads * U.L / 16; // (a whole number of words: a tile is a multiple of 16 bases)
-				else rb.bases += done_reads * U.L;
-				rb.n_bases -= done_reads * U.L;
-				U.n_lanes = (n_reads - done_reads) * U.Q;
-				rest_only = U.n_lanes == 0;
-			}
-		}
-		const uint64_t n_tiles_rest = (U.n_lanes + kL1Threads - 1) / kL1Threads;
-		const int grid = (int)std::min<uint64_t>(std::max<uint64_t>(n_tiles_rest, 1), (uint64_t)h->n_cu * l1_wgs_per_cu());
-		if (rest_only) {
-		}
-#ifdef DBGK_EXPERIMENTS
-		else if (dbg_mode_u == 1)   // timing experiments on cfg2's shape (C = 15, equal lengths, size < 2^31): results are wrong
-			hipLaunchKernelGGL((k_extract_scatter_uniform<1, 0, 15, false>), dim3(grid), dim3(kL1Threads), sizeof(UniformLds), h->stream, rb, U, d_offsets, h->geom, h->store, h->d_ctr);
-		else if (dbg_mode_u == 2)
-			hipLaunchKernelGGL((k_extract_scatter_uniform<2, 0, 15, false>), dim3(grid), dim3(kL1Threads), sizeof(UniformLds), h->stream, rb, U, d_offsets, h->geom, h->store, h->d_ctr);
-		else if (dbg_mode_u == 3)
-			hipLaunchKernelGGL((k_extract_scatter_uniform<3, 0, 15, false>), dim3(grid), dim3(kL1Threads), sizeof(UniformLds), h->stream, rb, U, d_offsets, h->geom, h->store, h->d_ctr);
-#endif
-		else if (lin8 && lin12 && ragged) {
-			if (wide == 2) DBGK_LAUNCH_UNIFORM8(2, 12, true); else if (wide == 1) DBGK_LAUNCH_UNIFORM8(1, 12, true); else DBGK_LAUNCH_UNIFORM8(0, 12, true);
-		} else if (lin8 && lin12) {
-			if (wide == 2) DBGK_LAUNCH_UNIFORM8(2, 12, false); else if (wide == 1) DBGK_LAUNCH_UNIFORM8(1, 12, false); else DBGK_LAUNCH_UNIFORM8(0, 12, false);
-		} else if (lin8 && ragged) {
-			if (wide == 2) DBGK_LAUNCH_UNIFORM8(2, 8, true); else if (wide == 1) DBGK_LAUNCH_UNIFORM8(1, 8, true); else DBGK_LAUNCH_UNIFORM8(0, 8, true);
-		} else if (lin8) {
-			if (wide == 2) DBGK_LAUNCH_UNIFORM8(2, 8, false); else if (wide == 1) DBGK_LAUNCH_UNIFORM8(1, 8, false); else DBGK_LAUNCH_UNIFORM8(0, 8, false);
-		} else if (wide == 2 && h->geom.kf == 2u && !ragged) { // KFREQ, direct blocks: the instantiation without hash, division and neighbour codes
-			if (c15) DBGK_LAUNCH_UNIFORM(3, 15, false); else DBGK_LAUNCH_UNIFORM(3, 16, false);
-		} else if (wide == 2) DBGK_LAUNCH_UNIFORM_W(2);
-		else if (wide == 1) DBGK_LAUNCH_UNIFORM_W(1);
-		else DBGK_LAUNCH_UNIFORM_W(0);
-#undef DBGK_LAUNCH_UNIFORM8
-#undef DBGK_LAUNCH_UNIFORM_W
-#undef DBGK_LAUNCH_UNIFORM_K17
-#undef DBGK_LAUNCH_UNIFORM
 	} else if (h->part) {
-		const uint64_t n_tiles = (n_chunks + kL1Threads - 1) / kL1Threads;
-		const int grid = (int)std::min<uint64_t>(n_tiles, (uint64_t)h->n_cu * l1_wgs_per_cu()); // 140 KiB of LDS: one workgroup per CU
-		static const int dbg_mode = DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE") ? atoi(DBGK_EXPERIMENT_ENV("DBGK_DEBUG_MODE")) : 0;
-		const int wide_d = (h->geom.kf == 2u || h->geom.size >= (1ull << 32)) ? 2 : (h->geom.size >= (1ull << 31) ? 1 : 0); // how hash / size is computed
-		const int force_lin = dbgk_hook("l1_linear") ? atoi(dbgk_hook("l1_linear")) : -1;
-		if (!dbg_mode && (force_lin == 1 || (force_lin < 0 && h->geom.n1 > 320u))) { // many level-1 buckets: the linear form
-#define DBGK_LAUNCH_FLAT_LIN(DEAD, WD)                                                                                                       \
-	hipLaunchKernelGGL((k_extract_scatter_lin<DEAD, WD>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLdsLin<8>), h->stream, rb, h->geom, h->store, \
-	                   h->d_ctr)
-			if (has_long) {
-				if (wide_d == 2) DBGK_LAUNCH_FLAT_LIN(true, 2); else if (wide_d == 1) DBGK_LAUNCH_FLAT_LIN(true, 1); else DBGK_LAUNCH_FLAT_LIN(true, 0);
-			} else {
-				if (wide_d == 2) DBGK_LAUNCH_FLAT_LIN(false, 2); else if (wide_d == 1) DBGK_LAUNCH_FLAT_LIN(false, 1); else DBGK_LAUNCH_FLAT_LIN(false, 0);
+		if (use_prefix) {
+			// lane prefix of the batch (three short kernels over the offsets), the batch itself as 2-bit words, then level 1
+			h->prefix_launches++;
+			rc = ensure_prefix_scratch(h, n_reads, n_bases, d_packed == nullptr);
+			if (rc) return rc;
+			if (!d_packed) {
+				hipLaunchKernelGGL(k_pack_bases, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, d_bases, n_bases, h->pf_packed, h->d_ctr);
+				rb.packed = h->pf_packed;
 			}
-#undef DBGK_LAUNCH_FLAT_LIN
-		} else if (wide_d == 2 && has_long)
-			hipLaunchKernelGGL((k_extract_scatter<true, 0, 2>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-		else if (wide_d == 2)
-			hipLaunchKernelGGL((k_extract_scatter<false, 0, 2>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-		else if (wide_d && has_long)
-			hipLaunchKernelGGL((k_extract_scatter<true, 0, 1>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-		else if (wide_d)
-			hipLaunchKernelGGL((k_extract_scatter<false, 0, 1>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-#ifdef DBGK_EXPERIMENTS
-		else if (dbg_mode == 1)
-			hipLaunchKernelGGL((k_extract_scatter<false, 1>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-		else if (dbg_mode == 2)
-			hipLaunchKernelGGL((k_extract_scatter<false, 2>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-		else if (dbg_mode == 3)
-			hipLaunchKernelGGL((k_extract_scatter<false, 3>), dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-#endif
-		else if (has_long)
-			hipLaunchKernelGGL(k_extract_scatter<true>, dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
-		else
-			hipLaunchKernelGGL(k_extract_scatter<false>, dim3(grid), dim3(kL1Threads), sizeof(ScatterLds), h->stream, rb, h->geom, h->store, h->d_ctr);
+			if (plan.launch[0].form.c == 15) launch_prefix_passes<15>(h, d_offsets, n_reads, n_bases);
+			else launch_prefix_passes<16>(h, d_offsets, n_reads, n_bases);
+		} else if (umode > 0)
+			h->uniform_launches++;
+		rc = launch_l1(h, plan, rb, d_offsets, n_reads);
+		if (rc) return rc;
 	} else if (h->track) {
 		if (has_long)
 			hipLaunchKernelGGL((k_extract_insert<true, true>), dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, h->tref(), h->d_ctr,

@@ -203,6 +203,8 @@ static int plan_partition(dbgk_handle *h)
 }
 
 // allocate the record stores of the PARTITION engine (geometry already planned)
+static int l1_register_lds(bool wide); // dbgk_host_level1.h: the dynamic LDS sizes of the level-1 launch tables
+
 static int setup_partition(dbgk_handle *h)
 {
 	if (!h->part) return DBGK_OK;
@@ -266,58 +268,13 @@ static int setup_partition(dbgk_handle *h)
 		h->s_fin.inbox = h->mid;
 		h->s_fin.inbox_cnt = h->cnt_mid;
 	}
-#define DBGK_UNIFORM_ATTRS(W)                                                  \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, false>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, true>), sizeof(UniformLds));  \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, false>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, true>), sizeof(UniformLds));  \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, false, false, false, false, true, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, false, false, false, false, true, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, true, false, false, false, true, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, true, false, false, false, true, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, false, false, true, false, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, false, false, true, false, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, false, false, true, true, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, false, false, true, true, true>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, false, false, true, false, false>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, false, false, true, false, false>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 16, false, false, true, true, false>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 15, false, false, true, true, false>), sizeof(UniformLds)); \
-	DBGK_LDS_ATTR((k_extract_scatter<true, 0, W>), sizeof(ScatterLds));              \
-	DBGK_LDS_ATTR((k_extract_scatter<false, 0, W>), sizeof(ScatterLds))
+	int rc = l1_register_lds(false); // every level-1 form of dbgk_l1_form.h's lists
+	if (rc) return rc;
 #ifdef DBGK_EXPERIMENTS // timing experiments (DBGK_DEBUG_MODE, results are wrong): not in the product library
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<1, 0, 15, false>), sizeof(UniformLds));
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<2, 0, 15, false>), sizeof(UniformLds));
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<3, 0, 15, false>), sizeof(UniformLds));
-	DBGK_LDS_ATTR((k_extract_scatter<false, 1>), sizeof(ScatterLds));
-	DBGK_LDS_ATTR((k_extract_scatter<false, 2>), sizeof(ScatterLds));
-	DBGK_LDS_ATTR((k_extract_scatter<false, 3>), sizeof(ScatterLds));
 	DBGK_LDS_ATTR((k_scatter_l2<1>), sizeof(ScatterLdsL2));
 	DBGK_LDS_ATTR((k_scatter_l2<2>), sizeof(ScatterLdsL2));
 	DBGK_LDS_ATTR((k_scatter_l2<3>), sizeof(ScatterLdsL2));
 #endif
-	DBGK_UNIFORM_ATTRS(0);
-	DBGK_UNIFORM_ATTRS(1);
-	DBGK_UNIFORM_ATTRS(2);
-#define DBGK_LIN_ATTRS(W)                                                                          \
-	DBGK_LDS_ATTR((k_extract_scatter_lin<false, W>), sizeof(ScatterLdsLin<8>));                   \
-	DBGK_LDS_ATTR((k_extract_scatter_lin<true, W>), sizeof(ScatterLdsLin<8>));                    \
-	DBGK_LIN_ATTRS_U(W)
-#define DBGK_LIN_ATTRS_U(W)                                                                          \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 8, false, true>), sizeof(UniformLdsLin<8>));   \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 8, true, true>), sizeof(UniformLdsLin<8>));    \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 12, false, true>), sizeof(UniformLdsLin<12>)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 12, true, true>), sizeof(UniformLdsLin<12>)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 8, false, true, false, false, true, true>), sizeof(UniformLdsLin<8>));   \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 8, true, true, false, false, true, true>), sizeof(UniformLdsLin<8>));    \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 12, false, true, false, false, true, true>), sizeof(UniformLdsLin<12>)); \
-	DBGK_LDS_ATTR((k_extract_scatter_uniform<0, W, 12, true, true, false, false, true, true>), sizeof(UniformLdsLin<12>))
-	DBGK_LIN_ATTRS(0);
-	DBGK_LIN_ATTRS(1);
-	DBGK_LIN_ATTRS(2);
-#undef DBGK_LIN_ATTRS
-#undef DBGK_LIN_ATTRS_U
-#undef DBGK_UNIFORM_ATTRS
 	DBGK_LDS_ATTR((k_scatter_l2<0>), sizeof(ScatterLdsL2));
 	DBGK_LDS_ATTR((k_scatter_l2<0, kMaxBuckets, true>), sizeof(ScatterLdsL2));
 	DBGK_LDS_ATTR((k_scatter_l2<0, 2048>), sizeof(ScatterLdsL2T<2048>));

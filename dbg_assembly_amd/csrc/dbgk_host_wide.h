@@ -98,6 +98,8 @@ static bool plan_wide_partition(dbgk_handle *h, bool *err)
 	return true;
 }
 
+static int l1_register_lds(bool wide); // dbgk_host_level1.h: the dynamic LDS sizes of the level-1 launch tables
+
 static int setup_wide_partition(dbgk_handle *h)
 {
 	const WPartGeom &G = h->wgeom;
@@ -126,18 +128,8 @@ static int setup_wide_partition(dbgk_handle *h)
 	HIPCHK(hipMemsetAsync(P.cnt1, 0, (size_t)G.n_l1 * 4, h->stream));
 	HIPCHK(hipMemsetAsync(P.ovf_n, 0, 16, h->stream));
 	HIPCHK(hipMemsetAsync(P.outgoing_n, 0, 8, h->stream));
-	DBGK_LDS_ATTR((k_wide_scatter_l1<false, 0>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1<true, 0>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1<false, 1>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1<true, 1>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1<false, 2>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1<true, 2>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1_uniform<0, false>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1_uniform<1, false>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1_uniform<2, false>), sizeof(WL1Lds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1_uniform<0, true>), sizeof(WL1PipeLds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1_uniform<1, true>), sizeof(WL1PipeLds));
-	DBGK_LDS_ATTR((k_wide_scatter_l1_uniform<2, true>), sizeof(WL1PipeLds));
+	const int rc = l1_register_lds(true); // every WIDE level-1 form of dbgk_l1_form.h's lists
+	if (rc) return rc;
 	DBGK_LDS_ATTR(k_wide_scatter_l2<1024>, sizeof(WL2Lds<1024>));
 	DBGK_LDS_ATTR(k_wide_scatter_l2<2048>, sizeof(WL2Lds<2048>));
 	DBGK_LDS_ATTR((k_wide_build_regions<true, false>), sizeof(WBuildLds));

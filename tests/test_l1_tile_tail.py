@@ -23,7 +23,7 @@ from helpers import set_hooks
 
 READ_LEN, N_READS, K = 150, 300, 31
 N1S = (64, 65, 128, 129, 144, 192, 193, 256, 257)
-N1_LINEAR_ABOVE = 320   # (dbgk_host_level1.h) tables with more level-1 buckets take the linear form
+N1_LINEAR_ABOVE = 320   # (kL1LinearAboveN1, dbgk_l1_form.h) tables with more level-1 buckets take the linear form
 
 
 def _reads(seed, with_poly_a=False):
