@@ -26,11 +26,10 @@
 #include "dbgk_wide_links_patch.h"
 #include "dbgk_wide_partition.h"
 #include "dbgk_correct.h"
-#include "dbgk_corr_emit.h"
 #include "dbgk_spectrum.h"
 #include "dbgk_map.h"
 #include "dbgk_clean.h"
-#include "dbgk_clean_emit.h"
+#include "dbgk_emit.h"
 #include "dbgk_link.h"
 #include "dbgk_fill.h"
 #include "dbgk_super.h"
@@ -469,6 +468,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_misc.h"
 #include "dbgk_comm.h"
 #include "dbgk_host_wide_links.h"
+#include "dbgk_host_emit.h"
 #include "dbgk_host_correct.h"
 #include "dbgk_host_spectrum.h"
 #include "dbgk_host_map.h"

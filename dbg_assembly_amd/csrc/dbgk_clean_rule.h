@@ -1,5 +1,5 @@
 // dbgk_clean_rule.h -- CLEAN, output stage: what a record makes of its read, and the numbers of the .stat file.  No HIP in here: the
-// length kernel (dbgk_clean_emit.h) and the host's argument checks (dbgk_host_clean.h) share it, and tests/clean_rule_test.cpp
+// length kernel (dbgk_emit.h) and the host's argument checks (dbgk_host_clean.h) share it, and tests/clean_rule_test.cpp
 // runs it as a plain program under the address and undefined-behaviour sanitizers.
 //
 // The rule is the loop of the two programs (host/clean_lowqual.cpp:85-117, host/clean_adapter.cpp:152-177) with one addition: a

@@ -22,26 +22,13 @@ struct dbgk_clean {
 	uint64_t cap_bytes = 0, cap_qual = 0, cap_reads = 0;
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	dbgk_clean_stats last{};
-	// output stage (dbgk_clean_emit.h): the batch whose offsets and records d_off / d_out hold, and its compact form
+	// output stage (dbgk_host_emit.h): the batch whose offsets and records d_off / d_out hold, and its compact form
 	bool have_batch = false;      // the last batch call succeeded: batch_n reads of b_seq / b_qual are resident
 	uint64_t batch_n = 0;
 	int32_t batch_kind = 0;       // DBGK_CLEAN_KIND_*: what d_out holds
 	int32_t batch_shift = 0;      // the quality shift of a lowqual batch
 	const uint8_t *b_seq = nullptr, *b_qual = nullptr; // d_seq / d_qual, or the caller's planes of a _device call; b_qual null: no quality plane
-	bool have_compact = false, c_has_qual = false;
-	uint8_t *c_bases = nullptr, *c_quals = nullptr; // 16-byte vectors, the pad of the last one 0; one capacity
-	uint64_t *c_off = nullptr;    // batch_n + 1 compact offsets
-	uint64_t *c_src = nullptr;    // where each read's result starts in b_seq / b_qual
-	uint32_t *c_len = nullptr;
-	void *c_tmp = nullptr;        // the scan's temporary storage
-	unsigned long long *c_ctr = nullptr; // cleank::EC_COUNT counters
-	uint64_t c_cap_bytes = 0, c_cap_reads = 0, c_tmp_bytes = 0;
-	uint64_t c_n = 0, c_total = 0;
-	hipEvent_t c_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // length + scan: [0] .. [1]; gather: [2] .. [3]
-	hipEvent_t c_done = nullptr;  // the compact batch is complete (recorded on `stream`)
-	hipEvent_t c_read = nullptr;  // a graph handle has read it (recorded on that handle's stream by dbgk_push_cleaned)
-	bool c_lent = false;          // c_read is pending: waited for before the compact buffers are written, regrown or freed
-	dbgk_clean_compact_info c_info{};
+	EmitStage emit;
 };
 
 static_assert(sizeof(dbgk_adapter_hit) == 24 && sizeof(cleank::AdapterHit) == 24, "dbgk_adapter_hit is six int32");
@@ -79,13 +66,8 @@ extern "C" int dbgk_clean_create(int device, dbgk_clean **out)
 	if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
 	for (int i = 0; !rc && i < 4; ++i)
 		if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 4; ++i)
-		if (hipEventCreate(&c->c_ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && (hipEventCreateWithFlags(&c->c_done, hipEventDisableTiming) != hipSuccess ||
-	            hipEventCreateWithFlags(&c->c_read, hipEventDisableTiming) != hipSuccess))
-		rc = DBGK_ERR_HIP;
-	if (!rc && (hipMalloc(&c->d_ctr, sizeof(cleank::CleanCounters)) != hipSuccess || hipMalloc(&c->d_table, 256 * sizeof(double)) != hipSuccess ||
-	            hipMalloc(&c->c_ctr, cleank::EC_COUNT * sizeof(unsigned long long)) != hipSuccess))
+	if (!rc) rc = emit_create(c->emit, emitk::CleanRule<DBGK_CLEAN_KIND_LOWQUAL>::kCounters, false); // (both kinds count the same seven)
+	if (!rc && (hipMalloc(&c->d_ctr, sizeof(cleank::CleanCounters)) != hipSuccess || hipMalloc(&c->d_table, 256 * sizeof(double)) != hipSuccess))
 		rc = DBGK_ERR_NOMEM;
 	if (rc) {
 		dbgk_clean_destroy(c);
@@ -100,12 +82,10 @@ extern "C" int dbgk_clean_destroy(dbgk_clean *c)
 	if (!c) return DBGK_ERR_ARG;
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	if (c->c_lent) (void)hipEventSynchronize(c->c_read); // a graph handle may still be reading the compact batch
+	emit_destroy(c->emit);
 	clean_free_batch(c);
 	(void)hipFree(c->d_ad); (void)hipFree(c->d_ad_off); (void)hipFree(c->d_table); (void)hipFree(c->d_ctr);
-	(void)hipFree(c->c_bases); (void)hipFree(c->c_quals); (void)hipFree(c->c_off); (void)hipFree(c->c_src); (void)hipFree(c->c_len);
-	(void)hipFree(c->c_tmp); (void)hipFree(c->c_ctr);
-	for (hipEvent_t e : {c->ev[0], c->ev[1], c->ev[2], c->ev[3], c->c_ev[0], c->c_ev[1], c->c_ev[2], c->c_ev[3], c->c_done, c->c_read})
+	for (hipEvent_t e : c->ev)
 		if (e) (void)hipEventDestroy(e);
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	delete c;
@@ -142,7 +122,7 @@ extern "C" int dbgk_clean_set_adapters(dbgk_clean *c, const char *bases, const u
 	return DBGK_OK;
 }
 
-// The batch buffers are the handle's INPUT side only: the compact batch and a pending push live in buffers of their own (c_*), and a
+// The batch buffers are the handle's INPUT side only: the compact batch and a pending push live in buffers of their own (emit), and a
 // gather has finished when dbgk_clean_compact returns, so regrowing here never frees what either still needs.
 static int clean_ensure_batch(dbgk_clean *c, uint64_t n_bytes, uint64_t n_reads, bool with_qual)
 {
@@ -169,8 +149,8 @@ static bool clean_device_plane_ok(const dbgk_clean *c, const char *p)
 {
 	if ((uintptr_t)p & 15u) return false;
 	const uint8_t *u = (const uint8_t *)p;
-	for (const uint8_t *own : {c->c_bases, c->c_quals})
-		if (u && own && u >= own && u < own + c->c_cap_bytes) return false;
+	for (const uint8_t *own : {c->emit.bases, c->emit.quals})
+		if (u && own && u >= own && u < own + c->emit.cap_bytes) return false;
 	return true;
 }
 
@@ -198,7 +178,7 @@ static int clean_adapter_run(dbgk_clean *c, const char *bases, bool on_device, c
 	if (!c->adapters_set) return DBGK_ERR_STATE;
 	c->last = dbgk_clean_stats{};
 	c->last.reads = n_reads;
-	c->have_batch = c->have_compact = false;
+	c->have_batch = c->emit.have = false;
 	if (!n_reads) {
 		clean_batch_is(c, DBGK_CLEAN_KIND_ADAPTER, 0, 0, nullptr, nullptr);
 		return DBGK_OK;
@@ -278,7 +258,7 @@ static int clean_lowqual_run(dbgk_clean *c, const char *bases, const char *quals
 	if (on_device && (!clean_device_plane_ok(c, bases) || !clean_device_plane_ok(c, quals))) return DBGK_ERR_ARG;
 	c->last = dbgk_clean_stats{};
 	c->last.reads = n_reads;
-	c->have_batch = c->have_compact = false;
+	c->have_batch = c->emit.have = false;
 	if (!n_reads) {
 		clean_batch_is(c, DBGK_CLEAN_KIND_LOWQUAL, quality_shift, 0, nullptr, nullptr);
 		return DBGK_OK;
@@ -338,124 +318,38 @@ extern "C" int dbgk_clean_batch_stats(dbgk_clean *c, dbgk_clean_stats *out)
 	return DBGK_OK;
 }
 
-// ---- output stage: compact batch on the device, hand-over to a graph handle (kernels in dbgk_clean_emit.h) -----------------------
+// ---- output stage: compact batch on the device, hand-over to a graph handle (dbgk_host_emit.h, kernels in dbgk_emit.h) ------------
 
-// the compact buffers are about to be written (free_them: regrown or freed): a graph handle that was given them has to be done
-static int clean_compact_reclaim(dbgk_clean *c, bool free_them)
+template <int KIND>
+static void clean_launch_len(dbgk_clean *c, uint32_t min_len, unsigned grid, uint32_t *len, uint64_t *src, unsigned long long *ctr)
 {
-	if (!c->c_lent) return DBGK_OK;
-	if (free_them) {
-		HIPCHK(hipEventSynchronize(c->c_read));
-		c->c_lent = false;
-	} else {
-		HIPCHK(hipStreamWaitEvent(c->stream, c->c_read, 0)); // (stays lent: a later regrow or free still has to wait on the host)
-	}
-	return DBGK_OK;
-}
-
-template <bool QUAL, bool SUBST>
-static void clean_launch_gather(dbgk_clean *c, unsigned grid, uint64_t total)
-{
-	hipLaunchKernelGGL((cleank::k_clean_gather<QUAL, SUBST>), dim3(grid), dim3(cleank::kEmitBlock), 0, c->stream, c->b_seq, c->b_qual, c->c_src,
-	                   c->c_off, (uint32_t)c->batch_n, total, (uint32_t)c->batch_shift * 0x01010101u, reinterpret_cast<uint4 *>(c->c_bases),
-	                   reinterpret_cast<uint4 *>(c->c_quals));
+	using R = emitk::CleanRule<KIND>;
+	hipLaunchKernelGGL(emitk::k_emit_out_len<R>, dim3(grid), dim3(emitk::kEmitBlock), 0, c->stream, c->d_off, R{c->d_out, min_len}, (uint32_t)c->batch_n,
+	                   len, src, ctr);
 }
 
 static int clean_compact_run(dbgk_clean *c, uint32_t min_len, dbgk_clean_compact_info *out)
 {
-	const uint64_t n = c->batch_n;
-	const bool with_qual = c->b_qual != nullptr;
+	using R = emitk::CleanRule<DBGK_CLEAN_KIND_LOWQUAL>; // (the counters of both kinds)
+	const bool lowqual = c->batch_kind == DBGK_CLEAN_KIND_LOWQUAL;
 	HIPCHK(hipSetDevice(c->device));
-	c->have_compact = false;
-	const bool grow_reads = n > c->c_cap_reads || !c->c_off;
-	int rc = clean_compact_reclaim(c, grow_reads);
+	auto launch_len = [&](unsigned grid, uint32_t *len, uint64_t *src, unsigned long long *ctr) {
+		if (lowqual) clean_launch_len<DBGK_CLEAN_KIND_LOWQUAL>(c, min_len, grid, len, src, ctr);
+		else clean_launch_len<DBGK_CLEAN_KIND_ADAPTER>(c, min_len, grid, len, src, ctr);
+	};
+	unsigned long long ctr[R::EC_COUNT];
+	dbgk_clean_compact_info I{};
+	int rc = emit_run(c->emit, c->stream, c->n_cu, c->batch_n, c->b_seq, c->b_qual, lowqual, (uint32_t)c->batch_shift * 0x01010101u, launch_len, ctr,
+	                  &I.ms_scan, &I.ms_gather);
 	if (rc) return rc;
-	if (grow_reads) {
-		(void)hipFree(c->c_off); (void)hipFree(c->c_len); (void)hipFree(c->c_src);
-		c->c_off = nullptr; c->c_len = nullptr; c->c_src = nullptr;
-		c->c_cap_reads = 0;
-		const uint64_t cap = std::max<uint64_t>(n, 1 << 14);
-		if (hipMalloc(&c->c_off, (cap + 1) * 8) != hipSuccess || hipMalloc(&c->c_len, (cap + 1) * 4) != hipSuccess ||
-		    hipMalloc(&c->c_src, cap * 8) != hipSuccess)
-			return DBGK_ERR_NOMEM;
-		c->c_cap_reads = cap;
-	}
-	size_t need = 0;
-	if (n && dbgk_internal_scan_lengths(nullptr, &need, c->c_len, c->c_off, n + 1, c->stream)) return DBGK_ERR_HIP;
-	if (need > c->c_tmp_bytes) {
-		HIPCHK(hipStreamSynchronize(c->stream));
-		(void)hipFree(c->c_tmp);
-		c->c_tmp = nullptr;
-		c->c_tmp_bytes = 0;
-		if (hipMalloc(&c->c_tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-		c->c_tmp_bytes = need;
-	}
-	HIPCHK(hipMemsetAsync(c->c_ctr, 0, cleank::EC_COUNT * sizeof(unsigned long long), c->stream));
-	HIPCHK(hipEventRecord(c->c_ev[0], c->stream));
-	if (n) {
-		const unsigned grid = (unsigned)std::min<uint64_t>((n + cleank::kEmitBlock) / cleank::kEmitBlock, (uint64_t)c->n_cu * 16);
-		if (c->batch_kind == DBGK_CLEAN_KIND_LOWQUAL)
-			hipLaunchKernelGGL(cleank::k_clean_out_len<DBGK_CLEAN_KIND_LOWQUAL>, dim3(grid), dim3(cleank::kEmitBlock), 0, c->stream, c->d_off,
-			                   (const void *)c->d_out, (uint32_t)n, min_len, c->c_len, c->c_src, c->c_ctr);
-		else
-			hipLaunchKernelGGL(cleank::k_clean_out_len<DBGK_CLEAN_KIND_ADAPTER>, dim3(grid), dim3(cleank::kEmitBlock), 0, c->stream, c->d_off,
-			                   (const void *)c->d_out, (uint32_t)n, min_len, c->c_len, c->c_src, c->c_ctr);
-		HIPCHK(hipGetLastError());
-		size_t bytes = c->c_tmp_bytes;
-		if (dbgk_internal_scan_lengths(c->c_tmp, &bytes, c->c_len, c->c_off, n + 1, c->stream)) return DBGK_ERR_HIP;
-	} else {
-		HIPCHK(hipMemsetAsync(c->c_off, 0, 8, c->stream));
-	}
-	HIPCHK(hipEventRecord(c->c_ev[1], c->stream));
-	unsigned long long ctr[cleank::EC_COUNT];
-	uint64_t total = 0;
-	HIPCHK(hipMemcpyAsync(&total, c->c_off + n, 8, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(ctr, c->c_ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream)); // the total sizes the compact planes
-	// whole vectors, and room behind the end for the dword and 16-byte reads of the kernels that take a plane as their input
-	const uint64_t want = ((total + 15) & ~15ull) + 64;
-	if (want > c->c_cap_bytes || (with_qual && !c->c_quals)) {
-		rc = clean_compact_reclaim(c, true);
-		if (rc) return rc;
-		const bool qual = with_qual || c->c_quals; // a handle that has held a quality plane keeps one, as the batch buffers do
-		(void)hipFree(c->c_bases); (void)hipFree(c->c_quals);
-		c->c_bases = c->c_quals = nullptr;
-		const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, c->c_cap_bytes), 1 << 20);
-		c->c_cap_bytes = 0;
-		if (hipMalloc(&c->c_bases, cap) != hipSuccess || (qual && hipMalloc(&c->c_quals, cap) != hipSuccess)) return DBGK_ERR_NOMEM;
-		c->c_cap_bytes = cap;
-	}
-	if (total) {
-		const uint64_t tiles = (total + DBGK_CLEAN_COMPACT_TILE - 1) / DBGK_CLEAN_COMPACT_TILE;
-		const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)c->n_cu * 64);
-		HIPCHK(hipEventRecord(c->c_ev[2], c->stream)); // directly in front of the kernel: the copies, the host round trip and an allocation lie before it
-		if (!with_qual) clean_launch_gather<false, false>(c, grid, total);
-		else if (c->batch_kind == DBGK_CLEAN_KIND_LOWQUAL) clean_launch_gather<true, true>(c, grid, total);
-		else clean_launch_gather<true, false>(c, grid, total);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(c->c_ev[3], c->stream));
-	}
-	HIPCHK(hipEventRecord(c->c_done, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	float ms_scan = 0, ms_gather = 0;
-	HIPCHK(hipEventElapsedTime(&ms_scan, c->c_ev[0], c->c_ev[1]));
-	if (total) HIPCHK(hipEventElapsedTime(&ms_gather, c->c_ev[2], c->c_ev[3]));
-	dbgk_clean_compact_info &I = c->c_info;
-	I = dbgk_clean_compact_info{};
-	I.reads = n;
-	I.raw_bases = ctr[cleank::EC_RAW_BASES];
-	I.trimmed_reads = ctr[cleank::EC_TRIMMED_READS];
-	I.trimmed_bases = ctr[cleank::EC_TRIMMED_BASES];
-	I.short_reads = ctr[cleank::EC_SHORT_READS];
-	I.short_bases = ctr[cleank::EC_SHORT_BASES];
-	I.clean_reads = ctr[cleank::EC_CLEAN_READS];
-	I.clean_bases = ctr[cleank::EC_CLEAN_BASES];
-	I.ms_scan = ms_scan;
-	I.ms_gather = ms_gather; // (0 when nothing is kept: no launch)
-	c->c_n = n;
-	c->c_total = total;
-	c->c_has_qual = with_qual;
-	c->have_compact = true;
+	I.reads = c->batch_n;
+	I.raw_bases = ctr[R::EC_RAW_BASES];
+	I.trimmed_reads = ctr[R::EC_TRIMMED_READS];
+	I.trimmed_bases = ctr[R::EC_TRIMMED_BASES];
+	I.short_reads = ctr[R::EC_SHORT_READS];
+	I.short_bases = ctr[R::EC_SHORT_BASES];
+	I.clean_reads = ctr[R::EC_CLEAN_READS];
+	I.clean_bases = ctr[R::EC_CLEAN_BASES];
 	*out = I;
 	return DBGK_OK;
 }
@@ -478,7 +372,7 @@ extern "C" int dbgk_clean_compact_from(dbgk_clean *c, int32_t kind, const char *
 	if (n_reads && (!recs || (offsets[n_reads] && !bases))) return DBGK_ERR_ARG;
 	c->last = dbgk_clean_stats{};
 	c->last.reads = n_reads;
-	c->have_batch = c->have_compact = false;
+	c->have_batch = c->emit.have = false;
 	HIPCHK(hipSetDevice(c->device));
 	const uint64_t nb = n_reads ? offsets[n_reads] : 0;
 	if (n_reads) {
@@ -500,45 +394,24 @@ extern "C" int dbgk_clean_compact_from(dbgk_clean *c, int32_t kind, const char *
 extern "C" int dbgk_clean_compact_results(dbgk_clean *c, char *bases, char *quals, uint64_t *offsets)
 {
 	if (!c) return DBGK_ERR_ARG;
-	if (!c->have_compact) return DBGK_ERR_STATE;
-	if (quals && !c->c_has_qual) return DBGK_ERR_ARG;
+	if (!c->emit.have) return DBGK_ERR_STATE;
+	if (quals && !c->emit.has_qual) return DBGK_ERR_ARG;
 	HIPCHK(hipSetDevice(c->device));
-	if (bases && c->c_total) HIPCHK(hipMemcpyAsync(bases, c->c_bases, c->c_total, hipMemcpyDeviceToHost, c->stream));
-	if (quals && c->c_total) HIPCHK(hipMemcpyAsync(quals, c->c_quals, c->c_total, hipMemcpyDeviceToHost, c->stream));
-	if (offsets) HIPCHK(hipMemcpyAsync(offsets, c->c_off, (c->c_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	return DBGK_OK;
+	return emit_results(c->emit, c->stream, bases, quals, offsets);
 }
 
 extern "C" int dbgk_clean_compact_device(dbgk_clean *c, const char **d_bases, const char **d_quals, const uint64_t **d_offsets,
                                          uint64_t *n_reads, uint64_t *n_bases)
 {
 	if (!c || !d_bases || !d_quals || !d_offsets || !n_reads || !n_bases) return DBGK_ERR_ARG;
-	if (!c->have_compact) return DBGK_ERR_STATE;
-	*d_bases = (const char *)c->c_bases;
-	*d_quals = c->c_has_qual ? (const char *)c->c_quals : nullptr;
-	*d_offsets = c->c_off;
-	*n_reads = c->c_n;
-	*n_bases = c->c_total;
+	if (!c->emit.have) return DBGK_ERR_STATE;
+	emit_device(c->emit, d_bases, d_quals, d_offsets, n_reads, n_bases);
 	return DBGK_OK;
 }
 
-// as dbgk_push_corrected: the push queues every kernel that reads the pushed pointers on h's stream, so the event recorded behind it
-// covers every reader and no dbgk_sync is needed for any engine
 extern "C" int dbgk_push_cleaned(dbgk_handle *h, dbgk_clean *c)
 {
 	if (!h || !c) return DBGK_ERR_ARG;
 	if (h->device != c->device) return DBGK_ERR_ARG;
-	if (!c->have_compact || h->finalized) return DBGK_ERR_STATE;
-	int rc = use_device(h);
-	if (rc) return rc;
-	HIPCHK(hipStreamWaitEvent(h->stream, c->c_done, 0));
-	// c_read is ONE event: a push into another handle re-records it.  That handle's stream first waits for the earlier record, so
-	// the new one lies behind every reader so far, whichever handles they were pushed to.
-	if (c->c_lent) HIPCHK(hipStreamWaitEvent(h->stream, c->c_read, 0));
-	rc = dbgk_push_reads_device(h, (const char *)c->c_bases, c->c_off, c->c_n, c->c_total);
-	// (also after a failed push: part of its work may have been queued)
-	if (hipEventRecord(c->c_read, h->stream) == hipSuccess) c->c_lent = true;
-	else if (rc == DBGK_OK) rc = DBGK_ERR_HIP;
-	return rc;
+	return emit_push(h, c->emit);
 }

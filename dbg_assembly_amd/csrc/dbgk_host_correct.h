@@ -19,27 +19,11 @@ struct dbgk_corr {
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	dbgk_corr_stats last{};
 	double ms_mut_scan = 0;       // device time of the last k_mut_scan
-	// output stage (dbgk_corr_emit.h): the batch d_out / d_off / d_rec hold, and its compact form
+	// output stage (dbgk_host_emit.h): the batch d_out / d_off / d_rec hold, and its compact form
 	bool have_batch = false;      // the last dbgk_corr_reads* / dbgk_corr_compact_from succeeded: batch_n reads are resident
 	uint64_t batch_n = 0;
-	bool have_compact = false;
-	uint8_t *c_bases = nullptr;   // 16-byte vectors, the pad of the last one 0
-	uint64_t *c_off = nullptr;    // batch_n + 1 compact offsets
-	uint32_t *c_len = nullptr;
-	void *c_tmp = nullptr;        // the scan's temporary storage
-	unsigned long long *c_ctr = nullptr; // corr::EC_COUNT counters
-	uint64_t c_cap_bytes = 0, c_cap_reads = 0, c_tmp_bytes = 0;
-	uint64_t c_n = 0, c_total = 0;
-	hipEvent_t c_ev[4] = {nullptr, nullptr, nullptr, nullptr}; // length + scan: [0] .. [1]; gather: [2] .. [3]
-	hipEvent_t c_done = nullptr;  // the compact batch is complete (recorded on `stream`)
-	hipEvent_t c_read = nullptr;  // a graph handle has read it (recorded on that handle's stream by dbgk_push_corrected)
-	bool c_lent = false;          // c_read is pending: waited for before the compact buffers are written, regrown or freed
-	dbgk_corr_compact_info c_info{};
+	EmitStage emit;
 };
-
-// dbgk_sort.hip
-extern "C" int dbgk_internal_scan_lengths(void *tmp, size_t *tmp_bytes, const uint32_t *d_len, uint64_t *d_offsets, uint64_t n_items,
-                                          hipStream_t stream);
 
 static int corr_use(dbgk_corr *c)
 {
@@ -80,12 +64,7 @@ extern "C" int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr
 	if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
 	for (int i = 0; !rc && i < 4; ++i)
 		if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 4; ++i)
-		if (hipEventCreate(&c->c_ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && (hipEventCreateWithFlags(&c->c_done, hipEventDisableTiming) != hipSuccess ||
-	            hipEventCreateWithFlags(&c->c_read, hipEventDisableTiming) != hipSuccess))
-		rc = DBGK_ERR_HIP;
-	if (!rc && hipMalloc(&c->c_ctr, corr::EC_COUNT * sizeof(unsigned long long)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (!rc) rc = emit_create(c->emit, emitk::CorrRule::kCounters, true);
 	if (!rc && hipMalloc(&c->tab, c->tab_words * 4) != hipSuccess) rc = DBGK_ERR_NOMEM;
 	if (!rc && hipMalloc(&c->d_cnt, 4 * sizeof(uint64_t)) != hipSuccess) rc = DBGK_ERR_NOMEM;
 	if (!rc && hipMemsetAsync(c->tab, 0, c->tab_words * 4, c->stream) != hipSuccess) rc = DBGK_ERR_HIP;
@@ -103,11 +82,8 @@ extern "C" int dbgk_corr_destroy(dbgk_corr *c)
 	if (!c) return DBGK_ERR_ARG;
 	(void)hipSetDevice(c->device);
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	if (c->c_lent) (void)hipEventSynchronize(c->c_read); // a graph handle may still be reading the compact batch
+	emit_destroy(c->emit);
 	corr_free_batch(c);
-	(void)hipFree(c->c_bases); (void)hipFree(c->c_off); (void)hipFree(c->c_len); (void)hipFree(c->c_tmp); (void)hipFree(c->c_ctr);
-	for (hipEvent_t e : {c->c_ev[0], c->c_ev[1], c->c_ev[2], c->c_ev[3], c->c_done, c->c_read})
-		if (e) (void)hipEventDestroy(e);
 	(void)hipFree(c->d_scratch);
 	(void)hipFree(c->tab);
 	(void)hipFree(c->d_cnt);
@@ -216,7 +192,7 @@ static int corr_batch_begin(dbgk_corr *c, const uint64_t *offsets, uint64_t n)
 	if (max_len >= (1ull << 29)) return DBGK_ERR_ARG;
 	c->last = dbgk_corr_stats{};
 	c->last.reads = n;
-	c->have_batch = c->have_compact = false;
+	c->have_batch = c->emit.have = false;
 	if (!n) return DBGK_OK;
 	int rc = corr_use(c);
 	if (rc) return rc;
@@ -358,109 +334,39 @@ extern "C" int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out)
 	return DBGK_OK;
 }
 
-// ---- output stage: compact batch on the device, hand-over to a graph handle (kernels in dbgk_corr_emit.h) ------------------------
-
-// the compact buffers are about to be written (free_them: regrown or freed): a graph handle that was given them has to be done
-static int corr_compact_reclaim(dbgk_corr *c, bool free_them)
-{
-	if (!c->c_lent) return DBGK_OK;
-	if (free_them) {
-		HIPCHK(hipEventSynchronize(c->c_read));
-		c->c_lent = false;
-	} else {
-		HIPCHK(hipStreamWaitEvent(c->stream, c->c_read, 0)); // (stays lent: a later regrow or free still has to wait on the host)
-	}
-	return DBGK_OK;
-}
+// ---- output stage: compact batch on the device, hand-over to a graph handle (dbgk_host_emit.h, kernels in dbgk_emit.h) ------------
 
 static int corr_compact_run(dbgk_corr *c, dbgk_corr_compact_info *out)
 {
-	const uint64_t n = c->batch_n;
+	using R = emitk::CorrRule;
 	int rc = corr_use(c);
 	if (rc) return rc;
-	c->have_compact = false;
-	rc = corr_compact_reclaim(c, n > c->c_cap_reads || !c->c_off);
+	auto launch_len = [&](unsigned grid, uint32_t *len, uint64_t *src, unsigned long long *ctr) {
+		hipLaunchKernelGGL(emitk::k_emit_out_len<R>, dim3(grid), dim3(emitk::kEmitBlock), 0, c->stream, c->d_off, R{c->d_rec}, (uint32_t)c->batch_n,
+		                   len, src, ctr);
+	};
+	// What either gather asks of its source plane (dbgk_emit.h), on d_out:
+	//  - d_out comes from hipMalloc, so it is 16-byte aligned, and corr_batch_begin leaves 16 bytes behind offsets[n]: the aligned
+	//    dwords the gather reads lie inside [off[0] & ~3, off[n]) rounded up to whole dwords, inside the buffer;
+	//  - R::out_len gives 0 whenever left_trim + right_trim >= L, so for every read that holds bytes src .. src + len lies inside
+	//    the read (the src of a read of length 0 is never read);
+	//  - n < 2^32 and every read shorter than 2^29 bytes (corr_batch_begin).
+	unsigned long long ctr[R::EC_COUNT];
+	dbgk_corr_compact_info I{};
+	rc = emit_run(c->emit, c->stream, c->n_cu, c->batch_n, c->d_out, nullptr, false, 0u, launch_len, ctr, &I.ms_scan, &I.ms_gather);
 	if (rc) return rc;
-	if (n > c->c_cap_reads || !c->c_off) {
-		(void)hipFree(c->c_off); (void)hipFree(c->c_len);
-		c->c_off = nullptr; c->c_len = nullptr;
-		c->c_cap_reads = 0;
-		const uint64_t cap = std::max<uint64_t>(n, 1 << 14);
-		if (hipMalloc(&c->c_off, (cap + 1) * 8) != hipSuccess || hipMalloc(&c->c_len, (cap + 1) * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		c->c_cap_reads = cap;
-	}
-	size_t need = 0;
-	if (n && dbgk_internal_scan_lengths(nullptr, &need, c->c_len, c->c_off, n + 1, c->stream)) return DBGK_ERR_HIP;
-	if (need > c->c_tmp_bytes) {
-		HIPCHK(hipStreamSynchronize(c->stream));
-		(void)hipFree(c->c_tmp);
-		c->c_tmp = nullptr;
-		c->c_tmp_bytes = 0;
-		if (hipMalloc(&c->c_tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-		c->c_tmp_bytes = need;
-	}
-	HIPCHK(hipMemsetAsync(c->c_ctr, 0, corr::EC_COUNT * sizeof(unsigned long long), c->stream));
-	HIPCHK(hipEventRecord(c->c_ev[0], c->stream));
-	if (n) {
-		const unsigned grid = (unsigned)std::min<uint64_t>((n + corr::kEmitBlock) / corr::kEmitBlock, (uint64_t)c->n_cu * 16);
-		hipLaunchKernelGGL(corr::k_corr_out_len, dim3(grid), dim3(corr::kEmitBlock), 0, c->stream, c->d_off, c->d_rec, (uint32_t)n, c->c_len,
-		                   c->c_ctr);
-		HIPCHK(hipGetLastError());
-		size_t bytes = c->c_tmp_bytes;
-		if (dbgk_internal_scan_lengths(c->c_tmp, &bytes, c->c_len, c->c_off, n + 1, c->stream)) return DBGK_ERR_HIP;
-	} else {
-		HIPCHK(hipMemsetAsync(c->c_off, 0, 8, c->stream));
-	}
-	HIPCHK(hipEventRecord(c->c_ev[1], c->stream));
-	unsigned long long ctr[corr::EC_COUNT];
-	uint64_t total = 0;
-	HIPCHK(hipMemcpyAsync(&total, c->c_off + n, 8, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(ctr, c->c_ctr, sizeof ctr, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream)); // the total sizes the compact buffer
-	const uint64_t want = ((total + 15) & ~15ull) + 64; // whole vectors, and room for the 16-byte reads of the graph kernels behind the end
-	if (want > c->c_cap_bytes) {
-		rc = corr_compact_reclaim(c, true);
-		if (rc) return rc;
-		(void)hipFree(c->c_bases);
-		c->c_bases = nullptr;
-		c->c_cap_bytes = 0;
-		const uint64_t cap = std::max<uint64_t>(want, 1 << 20);
-		if (hipMalloc(&c->c_bases, cap) != hipSuccess) return DBGK_ERR_NOMEM;
-		c->c_cap_bytes = cap;
-	}
-	if (total) {
-		const uint64_t tiles = (total + DBGK_CORR_COMPACT_TILE - 1) / DBGK_CORR_COMPACT_TILE;
-		const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)c->n_cu * 64);
-		HIPCHK(hipEventRecord(c->c_ev[2], c->stream)); // directly in front of the kernel: the copies, the host round trip and an allocation lie before it
-		hipLaunchKernelGGL(corr::k_corr_gather, dim3(grid), dim3(corr::kEmitBlock), 0, c->stream, (const uint8_t *)c->d_out, c->d_off, c->d_rec,
-		                   c->c_off, (uint32_t)n, total, reinterpret_cast<uint4 *>(c->c_bases));
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(c->c_ev[3], c->stream));
-	}
-	HIPCHK(hipEventRecord(c->c_done, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	float ms_scan = 0, ms_gather = 0;
-	HIPCHK(hipEventElapsedTime(&ms_scan, c->c_ev[0], c->c_ev[1]));
-	if (total) HIPCHK(hipEventElapsedTime(&ms_gather, c->c_ev[2], c->c_ev[3]));
-	dbgk_corr_compact_info &I = c->c_info;
-	I = dbgk_corr_compact_info{};
-	I.reads = n;
-	I.result_reads = ctr[corr::EC_RESULT_READS];
-	I.result_bases = ctr[corr::EC_RESULT_BASES];
-	I.trimmed_reads = ctr[corr::EC_TRIMMED_READS];
-	I.trimmed_bases = ctr[corr::EC_TRIMMED_BASES];
-	I.deleted_reads = ctr[corr::EC_DELETED_READS];
-	I.one_base = ctr[corr::EC_ONE_BASE];
-	I.tree = ctr[corr::EC_TREE];
-	I.node_limit_hits = ctr[corr::EC_NODE_LIMIT_HITS];
-	I.by_classify = ctr[corr::EC_BY_CLASSIFY];
-	I.by_correct = ctr[corr::EC_BY_CORRECT];
-	I.by_overflow = ctr[corr::EC_BY_OVERFLOW];
-	I.ms_scan = ms_scan;
-	I.ms_gather = ms_gather; // (0 when nothing is kept: no launch)
-	c->c_n = n;
-	c->c_total = total;
-	c->have_compact = true;
+	I.reads = c->batch_n;
+	I.result_reads = ctr[R::EC_RESULT_READS];
+	I.result_bases = ctr[R::EC_RESULT_BASES];
+	I.trimmed_reads = ctr[R::EC_TRIMMED_READS];
+	I.trimmed_bases = ctr[R::EC_TRIMMED_BASES];
+	I.deleted_reads = ctr[R::EC_DELETED_READS];
+	I.one_base = ctr[R::EC_ONE_BASE];
+	I.tree = ctr[R::EC_TREE];
+	I.node_limit_hits = ctr[R::EC_NODE_LIMIT_HITS];
+	I.by_classify = ctr[R::EC_BY_CLASSIFY];
+	I.by_correct = ctr[R::EC_BY_CORRECT];
+	I.by_overflow = ctr[R::EC_BY_OVERFLOW];
 	*out = I;
 	return DBGK_OK;
 }
@@ -493,44 +399,24 @@ extern "C" int dbgk_corr_compact_from(dbgk_corr *c, const char *seq, const uint6
 extern "C" int dbgk_corr_compact_results(dbgk_corr *c, char *bases, uint64_t *offsets)
 {
 	if (!c || !offsets) return DBGK_ERR_ARG;
-	if (!c->have_compact) return DBGK_ERR_STATE;
-	if (!bases && c->c_total) return DBGK_ERR_ARG;
+	if (!c->emit.have) return DBGK_ERR_STATE;
+	if (!bases && c->emit.total) return DBGK_ERR_ARG;
 	int rc = corr_use(c);
 	if (rc) return rc;
-	if (c->c_total) HIPCHK(hipMemcpyAsync(bases, c->c_bases, c->c_total, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipMemcpyAsync(offsets, c->c_off, (c->c_n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
-	return DBGK_OK;
+	return emit_results(c->emit, c->stream, bases, nullptr, offsets);
 }
 
 extern "C" int dbgk_corr_compact_device(dbgk_corr *c, const char **d_bases, const uint64_t **d_offsets, uint64_t *n_reads, uint64_t *n_bases)
 {
 	if (!c || !d_bases || !d_offsets || !n_reads || !n_bases) return DBGK_ERR_ARG;
-	if (!c->have_compact) return DBGK_ERR_STATE;
-	*d_bases = (const char *)c->c_bases;
-	*d_offsets = c->c_off;
-	*n_reads = c->c_n;
-	*n_bases = c->c_total;
+	if (!c->emit.have) return DBGK_ERR_STATE;
+	emit_device(c->emit, d_bases, nullptr, d_offsets, n_reads, n_bases);
 	return DBGK_OK;
 }
 
-// launch_batch queues every kernel that reads the pushed pointers on the handle's stream (the record engines keep records, the
-// others their table: no engine keeps the pointers), so the event recorded behind the push covers every reader and no dbgk_sync
-// is needed for any engine.
 extern "C" int dbgk_push_corrected(dbgk_handle *h, dbgk_corr *c)
 {
 	if (!h || !c) return DBGK_ERR_ARG;
 	if (h->device != c->device) return DBGK_ERR_ARG;
-	if (!c->have_compact || h->finalized) return DBGK_ERR_STATE;
-	int rc = use_device(h);
-	if (rc) return rc;
-	HIPCHK(hipStreamWaitEvent(h->stream, c->c_done, 0));
-	// c_read is ONE event: a push into another handle re-records it.  That handle's stream first waits for the earlier record, so
-	// the new one lies behind every reader so far, whichever handles they were pushed to.
-	if (c->c_lent) HIPCHK(hipStreamWaitEvent(h->stream, c->c_read, 0));
-	rc = dbgk_push_reads_device(h, (const char *)c->c_bases, c->c_off, c->c_n, c->c_total);
-	// (also after a failed push: part of its work may have been queued)
-	if (hipEventRecord(c->c_read, h->stream) == hipSuccess) c->c_lent = true;
-	else if (rc == DBGK_OK) rc = DBGK_ERR_HIP;
-	return rc;
+	return emit_push(h, c->emit);
 }

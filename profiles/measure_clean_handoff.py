@@ -8,9 +8,10 @@ batches of 1 M reads; clean_lowqual -e 0.001 -q 33 -r 75, then clean_adapter wit
 
 Each route runs --reps times, interleaved.  Reported:
   1. the device time of the length kernel + scan and of the gather, per stage, summed over the batches of a run;
-  2. the gather's rate (bytes read + bytes written, both planes, per second of k_clean_gather) next to dbgk_measure_copy_bandwidth
-     of the same run and next to k_corr_gather (one plane) on a batch of the same output size -- the first batch, its reads cut to
-     the lengths the two stages left;
+  2. the gather's rate (bytes read + bytes written, both planes, per second of k_emit_gather) next to dbgk_measure_copy_bandwidth
+     of the same run and next to k_emit_gather_lds (one plane, the corrector's gather) on a batch of the same output size -- the
+     first batch, its reads cut to the lengths the two stages left.  (Its JSON key names that kernel as it was called when the first
+     result file was written, k_corr_gather, so that old and new result files compare);
   3. the wall time of each route and of its stages (creating the handles is a stage of its own, the same work in both routes, and
      is left out of the comparison).  The project's rule decides whether the routes separate: the slowest run of the new route
      against the fastest of the old.  The host cut of route (a) is a numpy stand-in for the loops of bin/clean_lowqual and
@@ -32,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "clean_handoff_measure.json")
 FIGURES = ["ms_scan and ms_gather of both stages (3 runs)", "gather GB/s (bytes read + written, two planes)",
-           "copy_bandwidth GB/s of the same run", "k_corr_gather GB/s on a batch of the same output size",
+           "copy_bandwidth GB/s of the same run", "k_emit_gather_lds GB/s on a batch of the same output size",
            "route_a wall_s (3 runs)", "route_b wall_s (3 runs)", "routes_separate"]
 K_FREQ, READ_LEN, MIN_LEN, SHIFT, CUTOFF_E, SCORE = 17, 150, 75, 33, 0.001, 12
 ADAPTER = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCAC"
@@ -191,7 +192,7 @@ def route_b(capi, batches):
 
 
 def corr_gather_same_size(capi, batch):
-    """k_corr_gather on the first batch, its reads cut to the lengths the two cleaning stages leave: one plane of the same output
+    """k_emit_gather_lds on the first batch, its reads cut to the lengths the two cleaning stages leave: one plane of the same output
     size as the adapter stage's compact batch -> (GB/s of bytes read + written, ms, output bytes)"""
     bases, quals, offsets = batch
     n = len(offsets) - 1
@@ -276,7 +277,7 @@ def main():
            "gather_bytes_counted": "per plane the kept bytes read and the 16-byte vectors written; two planes",
            "k_corr_gather_same_output_size": {"gbps": corr_gbps, "ms_gather_best_of_3": corr_ms, "output_bytes": corr_bytes,
                                               "note": "one plane, first batch, reads cut to the lengths both cleaning stages leave"},
-           "gather_time": "ms_gather is the device time of k_clean_gather alone (events directly around the kernel)"}
+           "gather_time": "ms_gather is the device time of k_emit_gather alone (events directly around the kernel)"}
     with open(a.out, "w") as f:
         json.dump(rounded(out), f, indent=1)
         f.write("\n")

@@ -9,7 +9,7 @@ Each route runs --reps times.  Reported per run: the wall time of the whole rout
 stage of its own, the same work in both routes, and is left out of the comparison), and the wall time WITHOUT
 the corrector's own kernels (classify + correct + overflow device ms, which both routes run alike).  The project's rule decides
 whether the routes separate: the slowest run of the new route against the fastest of the old.  Next to it the gather's rate
-(kept bytes read + bytes written per second of k_corr_gather) and dbgk_measure_copy_bandwidth of the same run.  Writes
+(kept bytes read + bytes written per second of k_emit_gather_lds) and dbgk_measure_copy_bandwidth of the same run.  Writes
 profiles/handoff_measure.json; without a GPU it lists the figures that are missing.  Reported, not gated.
 
     python profiles/measure_handoff.py [--reads 10000000] [--genome 5000000] [--reps 3]
@@ -199,7 +199,7 @@ def main():
                                       "routes_separate_without_host_trim charges route (a) nothing for the trim and is the verdict "
                                       "that does not depend on the stand-in"),
            "gather_gbps": gather, "copy_bandwidth_gbps": copy_gbps, "gather_over_copy": [v / copy_gbps for v in gather],
-           "gather_time": "ms_gather is the device time of k_corr_gather alone (events directly around the kernel)"}
+           "gather_time": "ms_gather is the device time of k_emit_gather_lds alone (events directly around the kernel)"}
     if gather and max(gather) < 0.5 * copy_gbps:
         out["gather_bound"] = {
             "observed": "the gather stays below half the copy rate of this run (gather_over_copy)",

@@ -1,4 +1,4 @@
-"""CPU restatement of the cleaner's output stage (csrc/dbgk_clean_emit.h, csrc/dbgk_clean_rule.h) in numpy: what a record makes of its
+"""CPU restatement of the cleaner's output stage (csrc/dbgk_emit.h, csrc/dbgk_clean_rule.h) in numpy: what a record makes of its
 read as the two programs do it (host/clean_lowqual.cpp:85-117, host/clean_adapter.cpp:152-177), the compact offsets, the gather
 of both planes with the N -> shift substitution, and the eight integer columns of the .stat file.  Pinned to the reference by
 tests/test_clean_compact_cpu.py: applied to what tests/clean_restatement.py computes it gives lines 2 and 4 of every record and

@@ -59,6 +59,26 @@ def with_total(rng, total):
     return kept(rng, lens)
 
 
+def pair_rows():
+    """every pair (source start mod 4, destination start mod 4) at output lengths 1, 2, 3, 4, 5 and 17: in front of each target
+    read an untrimmed read moves the destination (and the source), a deleted one the source alone; the target is trimmed by 2
+    bytes on the left and 3 on the right -> (the case, target indices)"""
+    rows, targets, src, dst = [], [], 0, 0
+    for m in (1, 2, 3, 4, 5, 17):
+        for s in range(4):
+            for d in range(4):
+                x = (d - dst) % 4 + 4
+                rows.append((x, 0, 0, 0))
+                src, dst = src + x, dst + x
+                e = (s - src - 2) % 4
+                rows.append((e, 0, 0, 1))
+                src += e
+                targets.append(len(rows))
+                rows.append((2 + m + 3, 2, 3, 0))
+                src, dst = src + 2 + m + 3, dst + m
+    return tuple(np.array(col, dtype=t) for col, t in zip(zip(*rows), (np.int64, np.int64, np.int64, np.uint8))), targets
+
+
 def crafted():
     from dbg_assembly_amd import capi
     T = capi.CORR_COMPACT_TILE
@@ -81,6 +101,7 @@ def crafted():
     # left_trim + right_trim == L on a read that is kept, one that trims more than it holds, and a deleted read with trims
     cases["trims_use_up_the_read"] = join(kept(rng, [50]), (np.array([60, 60, 60]), np.array([25, 50, 10]), np.array([35, 30, 10]), np.array([0, 0, 1], dtype=np.uint8)),
                                           kept(rng, [70]))
+    cases["source_and_destination_mod_4"] = pair_rows()[0]
     res = {}
     with capi.Graph(k=31, table_slots=1009, engine=capi.ENGINE_DIRECT) as g, capi.Corrector(k=9) as c:
         for name, (lens, lts, rts, dele) in cases.items():
@@ -104,6 +125,9 @@ def crafted():
                 dst = want_o[:-1][live] % np.uint64(16)
                 assert set(src.tolist()) == set(range(16)) and set(dst.tolist()) == set(range(16))
                 assert set((src * np.uint64(16) + dst).tolist()) == set(range(256))   # ... independently of each other
+            if name == "source_and_destination_mod_4":
+                seen = {((int(offsets[i]) + int(rec["left_trim"][i])) % 4, int(want_o[i]) % 4, int(want_o[i + 1] - want_o[i])) for i in pair_rows()[1]}
+                assert seen == {(s, d, m) for s in range(4) for d in range(4) for m in (1, 2, 3, 4, 5, 17)}
             if name == "all_deleted":
                 assert nb == 0 and info["deleted_reads"] == 1000 and info["ms_gather"] == 0
             if name == "trims_use_up_the_read":

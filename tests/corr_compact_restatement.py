@@ -1,4 +1,4 @@
-"""CPU restatement of the corrector's output stage (csrc/dbgk_corr_emit.h) in numpy: the length rule of the command line
+"""CPU restatement of the corrector's output stage (csrc/dbgk_emit.h, CorrRule) in numpy: the length rule of the command line
 (host/correct_error_reads.cpp:155), the compact offsets, the gather and the counters of <file>.correct.stat.  Pinned to the
 reference by tests/test_corr_compact_cpu.py: applied to the output of tests/correct_restatement.py it gives the sequence
 lines and the stat numbers of every golden the real reference wrote."""

@@ -31,7 +31,7 @@ def test_crafted_batches_equal_the_restatement_byte_for_byte():
     assert sorted(res) == sorted(["n1", "all_deleted", "lengths_1_100", "total_T", "total_T_plus_1", "total_T_minus_1", "total_15",
                                   "zero_run_3T_inside_a_tile", "zero_run_on_a_tile_boundary", "zero_run_one_byte_past_a_boundary",
                                   "zero_first_and_last", "long_read_spans_three_tiles_0", "long_read_spans_three_tiles_5",
-                                  "trims_use_up_the_read"])
+                                  "trims_use_up_the_read", "source_and_destination_mod_4"])
     assert res["all_deleted"]["bases"] == 0 and res["total_15"]["bases"] == 15
     assert res["long_read_spans_three_tiles_0"]["reads"] == 5
 
