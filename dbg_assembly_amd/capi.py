@@ -143,6 +143,14 @@ class CleanCompactInfo(C.Structure):
                                           "clean_reads", "clean_bases")] + [("ms_scan", C.c_double), ("ms_gather", C.c_double)]
 
 
+PAIR_PAIRED, PAIR_SINGLE = 0, 1  # DBGK_PAIR_*
+
+
+class PairInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_pairs_in", "pair_reads", "pair_bases", "single_reads", "single_bases", "max_len")] + \
+               [("ms_rank", C.c_double), ("ms_gather", C.c_double)]
+
+
 class LinkParams(C.Structure):
     _fields_ = [("mate_pair", C.c_int32), ("pair_num_cut", C.c_int32), ("insert_size", C.c_int32)]
 
@@ -392,6 +400,7 @@ SYMBOLS = [
     ("dbgk_map_set_ramp", _i, [_vp, C.c_uint32]),
     ("dbgk_map_reads", _i, [_vp, _vp, _vp, _u64, _vp]),
     ("dbgk_map_batch_stats", _i, [_vp, C.POINTER(MapStats)]),
+    ("dbgk_map_reads_device", _i, [_vp, _vp, _vp, _u64, _u64, _u64, _vp]),
     ("dbgk_clean_create", _i, [_i, C.POINTER(_vp)]),
     ("dbgk_clean_destroy", _i, [_vp]),
     ("dbgk_clean_set_adapters", _i, [_vp, _vp, _vp, _u64, C.c_int32]),
@@ -405,6 +414,13 @@ SYMBOLS = [
     ("dbgk_clean_compact_results", _i, [_vp, _vp, _vp, _vp]),
     ("dbgk_clean_compact_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
     ("dbgk_push_cleaned", _i, [_vp, _vp]),
+    ("dbgk_pair_create", _i, [_i, C.POINTER(_vp)]),
+    ("dbgk_pair_destroy", _i, [_vp]),
+    ("dbgk_pair_split_from", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(PairInfo)]),
+    ("dbgk_pair_split_device", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(PairInfo)]),
+    ("dbgk_pair_results", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    ("dbgk_pair_device", _i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("dbgk_push_pairs", _i, [_vp, _vp, _i]),
     ("dbgk_link_create", _i, [C.POINTER(LinkParams), _i, C.POINTER(_vp)]),
     ("dbgk_link_destroy", _i, [_vp]),
     ("dbgk_link_set_contigs", _i, [_vp, _vp, _u64]),
@@ -671,6 +687,11 @@ class Graph:
     def push_cleaned(self, cleaner):
         """the cleaner's compact bases (Cleaner.compact) pushed where they lie on the device (dbgk_push_cleaned)"""
         _chk(lib().dbgk_push_cleaned(self._h, cleaner._h), "dbgk_push_cleaned")
+
+    def push_pairs(self, pairer, which):
+        """one output of the pair split (Pairer.split*; which = PAIR_PAIRED / PAIR_SINGLE) pushed where it lies on the device
+        (dbgk_push_pairs)"""
+        _chk(lib().dbgk_push_pairs(self._h, pairer._h, which), "dbgk_push_pairs")
 
     def finalize(self):
         st = Stats()
@@ -1332,6 +1353,13 @@ class Mapper:
              "dbgk_map_reads")
         return hits[:n]
 
+    def map_device(self, d_bases, d_offsets, n_reads, n_bases, max_len):
+        """map() for a batch on the device, offsets included (pointers; Pairer.device, Corrector / Cleaner.compact_device); max_len
+        is at least the longest read (PairInfo.max_len) -> MAP_HIT_DTYPE[n, 2]"""
+        hits = np.zeros((max(n_reads, 1), 2), dtype=MAP_HIT_DTYPE)
+        _chk(lib().dbgk_map_reads_device(self._h, d_bases, d_offsets, n_reads, n_bases, max_len, hits.ctypes.data), "dbgk_map_reads_device")
+        return hits[:n_reads]
+
     def map_sequences(self, reads):
         return self.map(*concat_sequences(reads))
 
@@ -1339,6 +1367,79 @@ class Mapper:
         s = MapStats()
         _chk(lib().dbgk_map_batch_stats(self._h, C.byref(s)), "dbgk_map_batch_stats")
         return {f: getattr(s, f) for f, _ in MapStats._fields_}
+
+
+class Pairer:
+    """The pair split on the GPU (PAIR section of include/dbgk.h): two batches of n reads, mate 1 and mate 2 of pair i at index i,
+    become the PAIRED batch (both mates of every pair with two reads left) and the SINGLE batch (the mate that is left of every
+    other pair).  split / split_device return the counters; results(which) and device(which) give either output."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        _chk(lib().dbgk_pair_create(device, C.byref(self._h)), "dbgk_pair_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_pair_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def _info(info):
+        return {f: getattr(info, f) for f, _ in PairInfo._fields_}
+
+    def split(self, b1, o1, b2, o2, q1=None, q2=None):
+        """two batches held on the host (bases uint8, offsets uint64[n + 1] from 0; qualities for both or for neither)"""
+        if (q1 is None) != (q2 is None):
+            raise ValueError("qualities for both batches or for neither")
+        planes = []
+        for b, o, q in ((b1, o1, q1), (b2, o2, q2)):
+            b = np.ascontiguousarray(b, dtype=np.uint8)
+            o = np.ascontiguousarray(o, dtype=np.uint64)
+            q = None if q is None else np.ascontiguousarray(q, dtype=np.uint8)
+            if len(o) < 1 or int(o[-1]) > b.size or (q is not None and q.size != b.size):
+                raise ValueError("the last offset inside the bases, and as many qualities as bases")
+            planes.append((b, o, q))
+        (b1, o1, q1), (b2, o2, q2) = planes
+        if len(o1) != len(o2):
+            raise ValueError("both batches hold one read per pair")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        # (a quality plane of no bytes is still a quality plane: the library tells the two apart by the pointer)
+        none = np.zeros(16, dtype=np.uint8)
+        qp = lambda q: None if q is None else (q.ctypes.data if q.size else none.ctypes.data)
+        info = PairInfo()
+        _chk(lib().dbgk_pair_split_from(self._h, ptr(b1), qp(q1), o1.ctypes.data, ptr(b2), qp(q2), o2.ctypes.data, len(o1) - 1, C.byref(info)),
+             "dbgk_pair_split_from")
+        return self._info(info)
+
+    def split_device(self, d_b1, d_o1, d_b2, d_o2, n, d_q1=None, d_q2=None):
+        """two batches on the device, offsets included (pointers; the planes 16-byte aligned) -- what compact_device of two
+        Corrector / Cleaner handles returns"""
+        info = PairInfo()
+        _chk(lib().dbgk_pair_split_device(self._h, d_b1, d_q1, d_o1, d_b2, d_q2, d_o2, n, C.byref(info)), "dbgk_pair_split_device")
+        return self._info(info)
+
+    def device(self, which):
+        """-> (device pointer of the bases, of the qualities or None, of the n + 1 offsets, reads, bases) of one output"""
+        b, q, o, n, nb = _vp(), _vp(), _vp(), _u64(), _u64()
+        _chk(lib().dbgk_pair_device(self._h, which, C.byref(b), C.byref(q), C.byref(o), C.byref(n), C.byref(nb)), "dbgk_pair_device")
+        return b.value, q.value, o.value, int(n.value), int(nb.value)
+
+    def results(self, which):
+        """-> (bases uint8, qualities uint8 or None, offsets uint64[n + 1], source ids uint32[n]: 2 * pair + mate) of one output"""
+        _, q, _, n, nb = self.device(which)
+        bases = np.empty(max(nb, 1), dtype=np.uint8)
+        quals = np.empty(max(nb, 1), dtype=np.uint8) if q else None
+        offsets = np.empty(n + 1, dtype=np.uint64)
+        ids = np.empty(max(n, 1), dtype=np.uint32)
+        _chk(lib().dbgk_pair_results(self._h, which, bases.ctypes.data, quals.ctypes.data if q else None, offsets.ctypes.data, ids.ctypes.data),
+             "dbgk_pair_results")
+        return bases[:nb], (quals[:nb] if q else None), offsets, ids[:n]
 
 
 class Cleaner:

@@ -20,6 +20,7 @@ struct dbgk_map {
 	mapk::Hit *d_hits = nullptr;
 	uint32_t *d_long = nullptr;
 	mapk::MapCounters *d_ctr = nullptr;
+	unsigned long long *d_chk = nullptr; // dbgk_map_reads_device: what k_map_check_batch found
 	uint64_t cap_bytes = 0, cap_reads = 0;
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	dbgk_map_stats last{};
@@ -113,6 +114,7 @@ extern "C" int dbgk_map_destroy(dbgk_map *m)
 	map_free_contigs(m);
 	(void)hipFree(m->d_accept);
 	(void)hipFree(m->d_ctr);
+	(void)hipFree(m->d_chk);
 	for (auto &e : m->ev)
 		if (e) (void)hipEventDestroy(e);
 	if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -195,28 +197,14 @@ static int map_ensure_accept(dbgk_map *m, uint64_t max_len)
 	return DBGK_OK;
 }
 
-extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_reads, dbgk_map_hit *out)
+// batch buffers for n_reads reads and, for a batch that is uploaded, n_bytes bytes of them
+static int map_ensure_batch(dbgk_map *m, uint64_t n_bytes, uint64_t n_reads)
 {
-	if (!m || !offsets || (n_reads && !out)) return DBGK_ERR_ARG;
-	if (offsets[0] != 0 || n_reads >= (1ull << 31)) return DBGK_ERR_ARG;
-	uint64_t max_len = 0;
-	for (uint64_t i = 0; i < n_reads; ++i) {
-		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
-		max_len = std::max<uint64_t>(max_len, offsets[i + 1] - offsets[i]);
-	}
-	if (max_len >= (1ull << 31) || (n_reads && offsets[n_reads] && !bases)) return DBGK_ERR_ARG;
-	if (!m->index) return DBGK_ERR_STATE;
-	m->last = dbgk_map_stats{};
-	m->last.reads = n_reads;
-	if (!n_reads) return DBGK_OK;
-	HIPCHK(hipSetDevice(m->device));
-	int rc = map_ensure_accept(m, max_len);
-	if (rc) return rc;
-	const uint64_t nb = offsets[n_reads];
-	if (nb + 16 > m->cap_bytes || n_reads > m->cap_reads) {
+	if (n_bytes + 16 > m->cap_bytes || n_reads > m->cap_reads) {
+		const uint64_t bytes = std::max<uint64_t>(n_bytes + 16, 1 << 20), reads = std::max<uint64_t>(n_reads, 1 << 14);
 		map_free_batch(m);
-		m->cap_bytes = std::max<uint64_t>(nb + 16, 1 << 20);
-		m->cap_reads = std::max<uint64_t>(n_reads, 1 << 14);
+		m->cap_bytes = bytes;
+		m->cap_reads = reads;
 		if (hipMalloc(&m->d_seq, m->cap_bytes) != hipSuccess || hipMalloc(&m->d_off, (m->cap_reads + 1) * 8) != hipSuccess ||
 		    hipMalloc(&m->d_hits, m->cap_reads * 2 * sizeof(mapk::Hit)) != hipSuccess ||
 		    hipMalloc(&m->d_long, m->cap_reads * 4) != hipSuccess) {
@@ -224,8 +212,13 @@ extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *of
 			return DBGK_ERR_NOMEM;
 		}
 	}
-	if (nb) HIPCHK(hipMemcpyAsync(m->d_seq, bases, nb, hipMemcpyHostToDevice, m->stream));
-	HIPCHK(hipMemcpyAsync(m->d_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	return DBGK_OK;
+}
+
+// The n_reads > 0 reads of d_seq / d_off (on the device, or on their way there on the mapper's stream) -> out.  The accept table
+// covers the longest read and the batch buffers hold n_reads reads.
+static int map_run(dbgk_map *m, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, dbgk_map_hit *out)
+{
 	HIPCHK(hipMemsetAsync(m->d_ctr, 0, sizeof(mapk::MapCounters), m->stream));
 	const mapk::MapParams P{m->p.k, m->p.seed_kmers, m->p.min_read_len, m->p.second_alignment, m->chunk0, (uint32_t)m->accept.size()};
 	const mapk::MapIndex X{m->index->tref(), m->index->h_ctr->polyA_links, m->d_ctg, m->d_ctg_off, (uint32_t)m->n_contigs};
@@ -233,7 +226,7 @@ extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *of
 	const uint64_t groups = (n_reads + mapk::kMapWaves - 1) / mapk::kMapWaves;
 	const unsigned grid = (unsigned)std::min<uint64_t>(groups, (uint64_t)m->n_cu * 32);
 	HIPCHK(hipEventRecord(m->ev[0], m->stream));
-	hipLaunchKernelGGL(mapk::k_map_reads<false>, dim3(grid), dim3(mapk::kMapWaves * 64), 0, m->stream, m->d_seq, m->d_off, nr, P, X,
+	hipLaunchKernelGGL(mapk::k_map_reads<false>, dim3(grid), dim3(mapk::kMapWaves * 64), 0, m->stream, d_seq, d_off, nr, P, X,
 	                   (const int32_t *)m->d_accept, m->d_hits, m->d_long, m->d_ctr);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(m->ev[1], m->stream));
@@ -243,7 +236,7 @@ extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *of
 	if (hc.n_long) { // reads beyond the LDS slice: the same code out of global memory
 		const unsigned grid_long = (unsigned)std::min<uint64_t>((hc.n_long + mapk::kMapWaves - 1) / mapk::kMapWaves, (uint64_t)m->n_cu * 32);
 		HIPCHK(hipEventRecord(m->ev[2], m->stream));
-		hipLaunchKernelGGL(mapk::k_map_reads<true>, dim3(grid_long), dim3(mapk::kMapWaves * 64), 0, m->stream, m->d_seq, m->d_off, nr, P, X,
+		hipLaunchKernelGGL(mapk::k_map_reads<true>, dim3(grid_long), dim3(mapk::kMapWaves * 64), 0, m->stream, d_seq, d_off, nr, P, X,
 		                   (const int32_t *)m->d_accept, m->d_hits, m->d_long, m->d_ctr);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(m->ev[3], m->stream));
@@ -263,6 +256,59 @@ extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *of
 	m->last.skipped = hc.skipped;
 	m->last.windows_probed = hc.windows;
 	return DBGK_OK;
+}
+
+extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_reads, dbgk_map_hit *out)
+{
+	if (!m || !offsets || (n_reads && !out)) return DBGK_ERR_ARG;
+	if (offsets[0] != 0 || n_reads >= (1ull << 31)) return DBGK_ERR_ARG;
+	uint64_t max_len = 0;
+	for (uint64_t i = 0; i < n_reads; ++i) {
+		if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
+		max_len = std::max<uint64_t>(max_len, offsets[i + 1] - offsets[i]);
+	}
+	if (max_len >= (1ull << 31) || (n_reads && offsets[n_reads] && !bases)) return DBGK_ERR_ARG;
+	if (!m->index) return DBGK_ERR_STATE;
+	m->last = dbgk_map_stats{};
+	m->last.reads = n_reads;
+	if (!n_reads) return DBGK_OK;
+	HIPCHK(hipSetDevice(m->device));
+	int rc = map_ensure_accept(m, max_len);
+	if (rc) return rc;
+	// stage the batch
+	const uint64_t nb = offsets[n_reads];
+	rc = map_ensure_batch(m, nb, n_reads);
+	if (rc) return rc;
+	if (nb) HIPCHK(hipMemcpyAsync(m->d_seq, bases, nb, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipMemcpyAsync(m->d_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	return map_run(m, m->d_seq, m->d_off, n_reads, out);
+}
+
+extern "C" int dbgk_map_reads_device(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len,
+                                     dbgk_map_hit *out)
+{
+	if (!m || (n_reads && (!out || !d_offsets)) || n_reads >= (1ull << 31) || max_len >= (1ull << 31)) return DBGK_ERR_ARG;
+	if (((uintptr_t)d_bases & 15u) || ((uintptr_t)d_offsets & 7u) || (n_bases && !d_bases)) return DBGK_ERR_ARG;
+	if (!m->index) return DBGK_ERR_STATE;
+	m->last = dbgk_map_stats{};
+	m->last.reads = n_reads;
+	if (!n_reads) return DBGK_OK;
+	HIPCHK(hipSetDevice(m->device));
+	// what dbgk_map_reads learns from its host loop over the offsets, learned on the device, before any read is mapped
+	if (!m->d_chk && hipMalloc(&m->d_chk, 3 * sizeof(unsigned long long)) != hipSuccess) return DBGK_ERR_NOMEM;
+	unsigned long long chk[3] = {0, 0, 0};
+	HIPCHK(hipMemsetAsync(m->d_chk, 0, sizeof chk, m->stream));
+	hipLaunchKernelGGL(mapk::k_map_check_batch, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)m->n_cu * 16)), dim3(256), 0,
+	                   m->stream, d_offsets, (uint32_t)n_reads, m->d_chk);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(chk, m->d_chk, sizeof chk, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	if (chk[1] || chk[0] > max_len || chk[2] > n_bases) return DBGK_ERR_ARG;
+	int rc = map_ensure_accept(m, max_len);
+	if (rc) return rc;
+	rc = map_ensure_batch(m, 0, n_reads);
+	if (rc) return rc;
+	return map_run(m, (const uint8_t *)d_bases, d_offsets, n_reads, out);
 }
 
 extern "C" int dbgk_map_batch_stats(dbgk_map *m, dbgk_map_stats *out)

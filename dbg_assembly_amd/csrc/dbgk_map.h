@@ -278,5 +278,28 @@ __global__ __launch_bounds__(kMapWaves * 64) void k_map_reads(const uint8_t *__r
 	}
 }
 
+// What the host loop of dbgk_map_reads finds out about offsets it holds, for offsets that lie on the device
+// (dbgk_map_reads_device): chk[0] = the longest read, chk[1] = the number of reads whose offsets decrease, chk[2] = off[n_reads].
+// A decreasing pair counts as a length of 2^64 - something, so chk[0] alone would refuse it too; chk[1] says why.
+__global__ __launch_bounds__(256) void k_map_check_batch(const uint64_t *__restrict__ off, uint32_t n_reads, unsigned long long *__restrict__ chk)
+{
+	unsigned long long longest = 0, bad = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * 256) {
+		const uint64_t a = off[i], b = off[i + 1];
+		if (b < a) bad++;
+		else longest = b - a > longest ? b - a : longest;
+		if (i + 1 == n_reads) chk[2] = b;
+	}
+	for (int d = 32; d > 0; d >>= 1) {
+		const unsigned long long o = __shfl_down(longest, d, 64);
+		longest = o > longest ? o : longest;
+		bad += __shfl_down(bad, d, 64);
+	}
+	if ((threadIdx.x & 63u) == 0u) {
+		if (longest) atomicMax(&chk[0], longest);
+		if (bad) atomicAdd(&chk[1], bad);
+	}
+}
+
 } // namespace mapk
 } // namespace dbgk

@@ -727,6 +727,15 @@ int dbgk_map_set_ramp(dbgk_map *m, uint32_t first_chunk);
  * second_alignment.  Input order is kept.                                                                                 */
 int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *offsets, uint64_t n_reads, dbgk_map_hit *out);
 int dbgk_map_batch_stats(dbgk_map *m, dbgk_map_stats *out);
+/* dbgk_map_reads for a batch in device memory of the mapper's GPU, offsets included -- a PAIR output (dbgk_pair_device), or a
+ * compact batch of the corrector or the cleaner: read 2i and 2i + 1 of a PAIRED output are pair i.  d_bases (16-byte aligned)
+ * holds n_bases bytes and must be readable for 16 bytes behind them, as the PAIR and compact planes are for 64; d_offsets are
+ * n_reads + 1 offsets into it, non-decreasing, the last one <= n_bases.  max_len >= the longest read sizes the identity table
+ * (dbgk_pair_info.max_len; any upper bound will do).  The offsets are checked on the device before a read is mapped: a read
+ * longer than max_len, offsets that decrease or an end behind n_bases give DBGK_ERR_ARG and no hits.  Work of the caller's own on
+ * the batch has to be synchronised; the call returns when the hits are in `out`.                                           */
+int dbgk_map_reads_device(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len,
+                          dbgk_map_hit *out);
 
 /* ---- CLEAN: clean_adapter / clean_lowqual of the clean_illumina module on the GPU (additions to ABI 7) -------------------------
  * clean_adapter aligns every read against every contaminant sequence with an ungapped local dynamic programme (match +1,
@@ -831,6 +840,56 @@ int dbgk_clean_compact_device(dbgk_clean *c, const char **d_bases, const char **
  * into several handles: each push makes h's stream wait for the event of the push before it, so the latest event lies behind
  * every reader.  Handles on different devices: DBGK_ERR_ARG; no compact batch, or h finalized: DBGK_ERR_STATE.                */
 int dbgk_push_cleaned(dbgk_handle *h, dbgk_clean *c);
+
+/* ---- PAIR: read pairs through the device pipeline (additions to ABI 7) -----------------------------------------------------------
+ * The compact batches of the corrector and the cleaner keep an emptied read at its place with length 0, so that mate 1 and mate 2 of
+ * pair i stay at index i of their two batches.  The PAIR stage splits two such batches of n reads each the way
+ * merge_two_corr_files does (correct_error/correct.cpp:851-922; clean_illumina/filter_unpaired_reads.pl states the same rule):
+ *   PAIRED  for every i with both mates not empty: mate 1, then mate 2, in index order;
+ *   SINGLE  for every other i: mate 1 if it is not empty, then mate 2 if it is not empty, in index order.
+ * Both outputs have the layout of dbgk_corr_compact / dbgk_clean_compact -- each plane from a 16-byte boundary in whole 16-byte
+ * vectors, the pad of the last one 0, 64 readable bytes behind the end, n_reads + 1 64-bit offsets -- so dbgk_push_reads_device and
+ * dbgk_map_reads_device read them where they lie.  Per output read there is a source id 2 i + mate (mate 0 or 1), by which a
+ * caller attaches headers.  Both inputs have a quality plane or neither has; the outputs then have one or none.            */
+typedef struct dbgk_pair dbgk_pair;
+#define DBGK_PAIR_PAIRED 0
+#define DBGK_PAIR_SINGLE 1
+typedef struct dbgk_pair_info {
+	uint64_t n_pairs_in;        /* n                                                                                    */
+	uint64_t pair_reads;        /* the four numbers of <file>.pair.single.stat: reads (2 per kept pair) and bases of    */
+	uint64_t pair_bases;        /* PAIRED, reads and bases of SINGLE                                                    */
+	uint64_t single_reads;
+	uint64_t single_bases;
+	uint64_t max_len;           /* the longest read of both outputs (0: both are empty): dbgk_map_reads_device's max_len */
+	double ms_rank;             /* device time of classify + scans + scatter + offset scans, and of both gathers        */
+	double ms_gather;
+} dbgk_pair_info;
+/* DBGK_ERR_HIP without a usable gfx950 device: there is no host fall-back                                                  */
+int dbgk_pair_create(int device, dbgk_pair **out);
+int dbgk_pair_destroy(dbgk_pair *p);
+/* two batches on the host, uploaded by the call: read i of mate file m = bases<m>[offsets<m>[i], offsets<m>[i + 1]) (offsets<m>[0]
+ * == 0, non-decreasing, each read < 2^31 bytes, n < 2^31); quals1 and quals2 are both null or both set and share the offsets of
+ * their bases.  n == 0 and inputs or outputs without a read are valid.  Returns when both outputs are complete.            */
+int dbgk_pair_split_from(dbgk_pair *p, const char *bases1, const char *quals1, const uint64_t *offsets1, const char *bases2,
+                         const char *quals2, const uint64_t *offsets2, uint64_t n, dbgk_pair_info *out);
+/* the same for batches in device memory of p's GPU, offsets included -- what dbgk_corr_compact_device / dbgk_clean_compact_device
+ * of two handles return (those calls return synchronised; work of the caller's own on the inputs has to be synchronised too).
+ * The planes must be 16-byte aligned (else DBGK_ERR_ARG), are never written, and are read only inside the whole dwords of
+ * [offsets[0] & ~3, offsets[n]); offsets[0] need not be 0.  The stage's own output planes as input: DBGK_ERR_ARG.  Offsets that
+ * decrease or a read of 2^31 bytes and more are found on the device: DBGK_ERR_ARG, no output.                                */
+int dbgk_pair_split_device(dbgk_pair *p, const char *d_bases1, const char *d_quals1, const uint64_t *d_offsets1, const char *d_bases2,
+                           const char *d_quals2, const uint64_t *d_offsets2, uint64_t n, dbgk_pair_info *out);
+/* host copy of one output (which: DBGK_PAIR_PAIRED / DBGK_PAIR_SINGLE): offsets[n_reads] bytes of each plane (without the pad),
+ * n_reads + 1 offsets, n_reads source ids.  Any pointer may be null; quals of an output without a quality plane: DBGK_ERR_ARG.
+ * Before a successful split: DBGK_ERR_STATE (also for the two calls below).                                                */
+int dbgk_pair_results(dbgk_pair *p, int which, char *bases, char *quals, uint64_t *offsets, uint32_t *src_ids);
+/* one output where it lies (*d_quals null without a quality plane); valid until the next split or dbgk_pair_destroy        */
+int dbgk_pair_device(dbgk_pair *p, int which, const char **d_bases, const char **d_quals, const uint64_t **d_offsets, uint64_t *n_reads,
+                     uint64_t *n_bases);
+/* dbgk_push_reads_device of one output into h (any engine that call serves), ordered by events as dbgk_push_corrected is: p may
+ * start its next split at once, and one output may be pushed into several handles.  Handles on different devices: DBGK_ERR_ARG;
+ * no split yet, or h finalized: DBGK_ERR_STATE.                                                                           */
+int dbgk_push_pairs(dbgk_handle *h, dbgk_pair *p, int which);
 
 /* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
  * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
