@@ -151,6 +151,15 @@ class PairInfo(C.Structure):
                [("ms_rank", C.c_double), ("ms_gather", C.c_double)]
 
 
+PARSE_TEXT_TILE = 4096  # DBGK_PARSE_TEXT_TILE
+PARSE_REC_DTYPE = np.dtype([(f, "<u4") for f in ("head_pos", "head_len", "seq_pos", "seq_len", "qual_pos", "qual_len")])  # dbgk_parse_rec
+
+
+class ParseInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_records", "n_lines", "ignored_lines", "consumed", "n_bases", "max_len", "mismatched")] + \
+               [(f, C.c_double) for f in ("ms_lines", "ms_states", "ms_scan", "ms_gather")]
+
+
 class LinkParams(C.Structure):
     _fields_ = [("mate_pair", C.c_int32), ("pair_num_cut", C.c_int32), ("insert_size", C.c_int32)]
 
@@ -421,6 +430,13 @@ SYMBOLS = [
     ("dbgk_pair_results", _i, [_vp, _i, _vp, _vp, _vp, _vp]),
     ("dbgk_pair_device", _i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
     ("dbgk_push_pairs", _i, [_vp, _vp, _i]),
+    ("dbgk_parse_create", _i, [C.c_int32, C.c_int32, _i, C.POINTER(_vp)]),
+    ("dbgk_parse_destroy", _i, [_vp]),
+    ("dbgk_parse_chunk", _i, [_vp, _vp, _u64, C.c_int32, C.POINTER(ParseInfo)]),
+    ("dbgk_parse_chunk_device", _i, [_vp, _vp, _u64, C.c_int32, C.POINTER(ParseInfo)]),
+    ("dbgk_parse_results", _i, [_vp, _vp, _vp, _vp, _vp]),
+    ("dbgk_parse_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("dbgk_push_parsed", _i, [_vp, _vp]),
     ("dbgk_link_create", _i, [C.POINTER(LinkParams), _i, C.POINTER(_vp)]),
     ("dbgk_link_destroy", _i, [_vp]),
     ("dbgk_link_set_contigs", _i, [_vp, _vp, _u64]),
@@ -692,6 +708,10 @@ class Graph:
         """one output of the pair split (Pairer.split*; which = PAIR_PAIRED / PAIR_SINGLE) pushed where it lies on the device
         (dbgk_push_pairs)"""
         _chk(lib().dbgk_push_pairs(self._h, pairer._h, which), "dbgk_push_pairs")
+
+    def push_parsed(self, parser):
+        """the batch of the last chunk of a Parser pushed where it lies on the device (dbgk_push_parsed)"""
+        _chk(lib().dbgk_push_parsed(self._h, parser._h), "dbgk_push_parsed")
 
     def finalize(self):
         st = Stats()
@@ -1440,6 +1460,76 @@ class Pairer:
         _chk(lib().dbgk_pair_results(self._h, which, bases.ctypes.data, quals.ctypes.data if q else None, offsets.ctypes.data, ids.ctypes.data),
              "dbgk_pair_results")
         return bases[:nb], (quals[:nb] if q else None), offsets, ids[:n]
+
+
+class Parser:
+    """FASTQ (fmt 1) / FASTA (fmt 2) text parsed on the GPU (PARSE section of include/dbgk.h): a chunk of the file's bytes becomes the
+    compact batch -- bases, qualities with with_quals, n + 1 offsets -- that the other stages read in place.  chunk / chunk_device
+    return the counters and `consumed`; results() and device() give the batch; stream() feeds a file chunk by chunk."""
+
+    def __init__(self, fmt, with_quals=False, device=0):
+        self._h = C.c_void_p()
+        _chk(lib().dbgk_parse_create(fmt, 1 if with_quals else 0, device, C.byref(self._h)), "dbgk_parse_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_parse_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def _info(info):
+        return {f: getattr(info, f) for f, _ in ParseInfo._fields_}
+
+    def chunk(self, text, last=True):
+        """one chunk of text held on the host (bytes, or a uint8 array); last: the input ends with it"""
+        a = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        info = ParseInfo()
+        _chk(lib().dbgk_parse_chunk(self._h, a.ctypes.data if a.size else None, a.size, 1 if last else 0, C.byref(info)), "dbgk_parse_chunk")
+        return self._info(info)
+
+    def chunk_device(self, d_text, n_bytes, last=True):
+        """one chunk on the device (pointer, 16-byte aligned, readable up to n_bytes rounded up to 16), read in place"""
+        info = ParseInfo()
+        _chk(lib().dbgk_parse_chunk_device(self._h, d_text, n_bytes, 1 if last else 0, C.byref(info)), "dbgk_parse_chunk_device")
+        return self._info(info)
+
+    def stream(self, fileobj, chunk_bytes):
+        """the text of fileobj (opened in binary mode) in chunks of chunk_bytes, each with what the chunk before it left unconsumed
+        in front -> yields the info of every chunk; between two of them the batch of the chunk is results() / device()"""
+        if chunk_bytes < 1:
+            raise ValueError("chunk_bytes >= 1")
+        carry, block = b"", fileobj.read(chunk_bytes)
+        while True:
+            ahead = fileobj.read(chunk_bytes) if block else b""
+            text = carry + block
+            info = self.chunk(text, last=not ahead)
+            yield info
+            if not ahead:
+                return
+            carry, block = text[info["consumed"]:], ahead
+
+    def device(self):
+        """-> (device pointer of the bases, of the qualities or None, of the n + 1 offsets, reads, bases)"""
+        b, q, o, n, nb = _vp(), _vp(), _vp(), _u64(), _u64()
+        _chk(lib().dbgk_parse_device(self._h, C.byref(b), C.byref(q), C.byref(o), C.byref(n), C.byref(nb)), "dbgk_parse_device")
+        return b.value, q.value, o.value, int(n.value), int(nb.value)
+
+    def results(self):
+        """-> (bases uint8, qualities uint8 or None, offsets uint64[n + 1], records PARSE_REC_DTYPE[n])"""
+        _, q, _, n, nb = self.device()
+        bases = np.empty(max(nb, 1), dtype=np.uint8)
+        quals = np.empty(max(nb, 1), dtype=np.uint8) if q else None
+        offsets = np.empty(n + 1, dtype=np.uint64)
+        recs = np.empty(max(n, 1), dtype=PARSE_REC_DTYPE)
+        _chk(lib().dbgk_parse_results(self._h, bases.ctypes.data, quals.ctypes.data if q else None, offsets.ctypes.data, recs.ctypes.data),
+             "dbgk_parse_results")
+        return bases[:nb], (quals[:nb] if q else None), offsets, recs[:n]
 
 
 class Cleaner:

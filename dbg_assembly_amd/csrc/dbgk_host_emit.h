@@ -1,6 +1,7 @@
 // Output stage of CORRECT and CLEAN, host side (kernels in dbgk_emit.h): the compact batch of a handle on the device, its
 // read-back, and its hand-over to a graph handle.  dbgk_corr and dbgk_clean each hold one EmitStage; what describes their INPUT
-// batch (have_batch, batch_n, the cleaner's kind, shift and planes) stays with them.
+// batch (have_batch, batch_n, the cleaner's kind, shift and planes) stays with them.  The parser (dbgk_host_parse.h) holds one too:
+// its source is the text, where the quality line of a read lies elsewhere than its sequence line (split_src).
 
 // dbgk_sort.hip
 extern "C" int dbgk_internal_scan_lengths(void *tmp, size_t *tmp_bytes, const uint32_t *d_len, uint64_t *d_offsets, uint64_t n_items,
@@ -10,11 +11,13 @@ struct EmitStage {
 	uint8_t *bases = nullptr, *quals = nullptr; // 16-byte vectors, the pad of the last one 0; one capacity.  quals: from the first batch with qualities on
 	uint64_t *off = nullptr;      // n + 1 compact offsets
 	uint64_t *src = nullptr;      // where each read's result starts in the source planes
+	uint64_t *qsrc = nullptr;     // split_src: ... in the quality plane's source, where that is another place (the parser's text)
 	uint32_t *len = nullptr;
 	void *tmp = nullptr;          // the scan's temporary storage
 	unsigned long long *ctr = nullptr; // n_counters counters of the producer's rule
 	int n_counters = 0;
 	bool lds_one_plane = false;   // a batch without qualities takes k_emit_gather_lds: the corrector's stage (dbgk_emit.h says why)
+	bool split_src = false;       // each plane is gathered on its own, the quality plane from qsrc: the parser's stage (set after emit_create)
 	uint64_t cap_bytes = 0, cap_reads = 0, tmp_bytes = 0;
 	uint64_t n = 0, total = 0;
 	bool has_qual = false;        // the compact batch has a quality plane
@@ -40,7 +43,7 @@ static int emit_create(EmitStage &s, int n_counters, bool lds_one_plane)
 static void emit_destroy(EmitStage &s)
 {
 	if (s.lent) (void)hipEventSynchronize(s.read); // a graph handle may still be reading the compact batch
-	(void)hipFree(s.bases); (void)hipFree(s.quals); (void)hipFree(s.off); (void)hipFree(s.src); (void)hipFree(s.len);
+	(void)hipFree(s.bases); (void)hipFree(s.quals); (void)hipFree(s.off); (void)hipFree(s.src); (void)hipFree(s.qsrc); (void)hipFree(s.len);
 	(void)hipFree(s.tmp); (void)hipFree(s.ctr);
 	for (hipEvent_t e : {s.ev[0], s.ev[1], s.ev[2], s.ev[3], s.done, s.read})
 		if (e) (void)hipEventDestroy(e);
@@ -68,7 +71,8 @@ static void emit_launch_gather(EmitStage &s, hipStream_t stream, unsigned grid, 
 
 // The n reads of the planes seq / qual (qual null: no quality plane; subst: the quality of a base 'N' becomes the byte of shift_word)
 // -> the compact batch.  launch_len(grid, len, src, ctr) launches the producer's k_emit_out_len on `stream`.  ctr: the stage's
-// n_counters counters.  What the gather needs of seq / qual: dbgk_emit.h, "Memory the gather reads".
+// n_counters counters.  What the gather needs of seq / qual: dbgk_emit.h, "Memory the gather reads".  A split_src stage: qual is
+// null or seq, and launch_len also fills s.qsrc (allocated here, beside s.src) when qual is set.
 template <class LaunchLen>
 static int emit_run(EmitStage &s, hipStream_t stream, int n_cu, uint64_t n, const uint8_t *seq, const uint8_t *qual, bool subst, uint32_t shift_word,
                     LaunchLen launch_len, unsigned long long *ctr, double *ms_scan, double *ms_gather)
@@ -79,12 +83,12 @@ static int emit_run(EmitStage &s, hipStream_t stream, int n_cu, uint64_t n, cons
 	int rc = emit_reclaim(s, stream, grow_reads);
 	if (rc) return rc;
 	if (grow_reads) {
-		(void)hipFree(s.off); (void)hipFree(s.len); (void)hipFree(s.src);
-		s.off = nullptr; s.len = nullptr; s.src = nullptr;
+		(void)hipFree(s.off); (void)hipFree(s.len); (void)hipFree(s.src); (void)hipFree(s.qsrc);
+		s.off = nullptr; s.len = nullptr; s.src = nullptr; s.qsrc = nullptr;
 		s.cap_reads = 0;
 		const uint64_t cap = std::max<uint64_t>(n, 1 << 14);
 		if (hipMalloc(&s.off, (cap + 1) * 8) != hipSuccess || hipMalloc(&s.len, (cap + 1) * 4) != hipSuccess ||
-		    hipMalloc(&s.src, cap * 8) != hipSuccess)
+		    hipMalloc(&s.src, cap * 8) != hipSuccess || (s.split_src && hipMalloc(&s.qsrc, cap * 8) != hipSuccess))
 			return DBGK_ERR_NOMEM;
 		s.cap_reads = cap;
 	}
@@ -132,7 +136,13 @@ static int emit_run(EmitStage &s, hipStream_t stream, int n_cu, uint64_t n, cons
 		const uint64_t tiles = (total + emitk::kEmitTile - 1) / emitk::kEmitTile;
 		const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)n_cu * 64);
 		HIPCHK(hipEventRecord(s.ev[2], stream)); // directly in front of the kernel: the copies, the host round trip and an allocation lie before it
-		if (!with_qual && s.lds_one_plane)
+		if (s.split_src) { // one launch per plane, both from `seq`, under the one set of offsets
+			hipLaunchKernelGGL((emitk::k_emit_gather<false, false>), dim3(grid), dim3(emitk::kEmitBlock), 0, stream, seq, (const uint8_t *)nullptr, s.src,
+			                   s.off, (uint32_t)n, total, 0u, reinterpret_cast<uint4 *>(s.bases), (uint4 *)nullptr);
+			if (with_qual)
+				hipLaunchKernelGGL((emitk::k_emit_gather<false, false>), dim3(grid), dim3(emitk::kEmitBlock), 0, stream, seq, (const uint8_t *)nullptr,
+				                   s.qsrc, s.off, (uint32_t)n, total, 0u, reinterpret_cast<uint4 *>(s.quals), (uint4 *)nullptr);
+		} else if (!with_qual && s.lds_one_plane)
 			hipLaunchKernelGGL(emitk::k_emit_gather_lds, dim3(grid), dim3(emitk::kEmitBlock), 0, stream, seq, s.src, s.off, (uint32_t)n, total,
 			                   reinterpret_cast<uint4 *>(s.bases));
 		else if (!with_qual) emit_launch_gather<false, false>(s, stream, grid, seq, qual, shift_word);

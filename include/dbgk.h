@@ -891,6 +891,65 @@ int dbgk_pair_device(dbgk_pair *p, int which, const char **d_bases, const char *
  * no split yet, or h finalized: DBGK_ERR_STATE.                                                                           */
 int dbgk_push_pairs(dbgk_handle *h, dbgk_pair *p, int which);
 
+/* ---- PARSE: from a FASTQ / FASTA file's bytes to the device batch (additions to ABI 7) ---------------------------------------------
+ * The stage in front of the first stage: the caller uploads the text of the file as it is (a gz file inflated first), the handle
+ * finds the records on the device and leaves the batch in the layout of dbgk_corr_compact / dbgk_clean_compact -- each plane from a
+ * 16-byte boundary in whole 16-byte vectors, the pad of the last one 0, 64 readable bytes behind the end, n + 1 64-bit offsets -- so
+ * dbgk_clean_*_device, dbgk_corr_reads_device, dbgk_pair_split_device, dbgk_push_reads_device and dbgk_map_reads_device read it where it
+ * lies.  The record rule is the one of both host readers (DBG_contig/DBGgraph.cpp:244-272, clean_illumina/clean_adapter.cpp:376-387):
+ *   - a line ends at '\n'; a '\r' in front of it belongs to the line; the last line of the input may lack its '\n';
+ *   - state 0 looks for a header: a line that is not empty and begins with the marker ('@' for format 1, '>' for format 2) opens a
+ *     record, any other line is ignored; the next line is the sequence; FASTQ then passes a separator and a quality line whatever
+ *     they begin with; single-line FASTA only, as in the reference;
+ *   - a record exists once its header has been seen: lines the input lacks at its end are empty;
+ *   - with a quality plane (FASTQ only) a record whose sequence and quality lines differ in length is emptied in both planes and
+ *     counted, as bin/clean_lowqual does; without one the quality line is not looked at.
+ * A chunk is parsed on its own, from state 0.  With last == 0 only records whose lines all end with a newline inside the chunk are
+ * delivered, and `consumed` is the first byte not used up -- the header of the first incomplete record, or, if the chunk ends in
+ * state 0, the byte behind its last newline; the caller presents the bytes from there on again at the front of its next chunk.
+ * consumed == 0 with no record is a valid answer: the chunk is smaller than one record.  With last != 0 the final line needs no
+ * newline, an incomplete record is delivered with its missing lines empty, and consumed == n_bytes.  The counters of the chunks of a
+ * stream add up to those of the whole text.                                                                                */
+typedef struct dbgk_parse dbgk_parse;
+#define DBGK_PARSE_TEXT_TILE 4096   /* bytes of text per workgroup round of the line kernels                              */
+typedef struct dbgk_parse_rec {     /* the lines of one record, relative to the chunk; a missing line: n_bytes, 0; FASTA: no */
+	uint32_t head_pos, head_len, seq_pos, seq_len, qual_pos, qual_len; /* quality line (0, 0).  As the text has them, also   */
+} dbgk_parse_rec;                   /* for a record that was emptied                                                      */
+typedef struct dbgk_parse_info {
+	uint64_t n_records;         /* records delivered                                                                    */
+	uint64_t n_lines;           /* lines in front of `consumed`                                                         */
+	uint64_t ignored_lines;     /* ... of which met in state 0 without being a header                                   */
+	uint64_t consumed;
+	uint64_t n_bases;           /* bytes of each plane                                                                  */
+	uint64_t max_len;           /* the longest read delivered: dbgk_map_reads_device's max_len                          */
+	uint64_t mismatched;        /* records emptied because sequence and quality differ in length                        */
+	double ms_lines;            /* device time: newline count + scan + line table; map scan + flags + rank;             */
+	double ms_states;           /* records + offsets; the gathers                                                       */
+	double ms_scan;
+	double ms_gather;
+} dbgk_parse_info;
+/* format 1 FASTQ, 2 FASTA; with_quals: the batch has a quality plane (format 1 only, else DBGK_ERR_ARG).  DBGK_ERR_HIP without a
+ * usable gfx950 device: there is no host fall-back                                                                         */
+int dbgk_parse_create(int32_t format, int32_t with_quals, int device, dbgk_parse **out);
+int dbgk_parse_destroy(dbgk_parse *p);
+/* one chunk of text on the host, uploaded by the call.  n_bytes < 2^31 (else DBGK_ERR_ARG); n_bytes == 0 is valid.  Returns when
+ * the batch is complete.                                                                                                   */
+int dbgk_parse_chunk(dbgk_parse *p, const char *text, uint64_t n_bytes, int32_t last, dbgk_parse_info *out);
+/* the same for text in device memory of p's GPU, read in place and never written: d_text 16-byte aligned (else DBGK_ERR_ARG) and
+ * readable up to n_bytes rounded up to 16; no byte at or behind n_bytes influences a result.  The handle's own planes as input:
+ * DBGK_ERR_ARG.  Work of the caller's own on the text has to be synchronised.                                              */
+int dbgk_parse_chunk_device(dbgk_parse *p, const char *d_text, uint64_t n_bytes, int32_t last, dbgk_parse_info *out);
+/* host copy of the batch: n_bases bytes of each plane (without the pad), n_records + 1 offsets -- the host copy that
+ * dbgk_clean_lowqual_device and dbgk_corr_reads_device ask for --, n_records records.  Any pointer may be null; quals of a batch
+ * without a quality plane: DBGK_ERR_ARG.  Before a successful chunk: DBGK_ERR_STATE (also for the two calls below).        */
+int dbgk_parse_results(dbgk_parse *p, char *bases, char *quals, uint64_t *offsets, dbgk_parse_rec *recs);
+/* the batch where it lies (*d_quals null without a quality plane); valid until the next chunk or dbgk_parse_destroy        */
+int dbgk_parse_device(dbgk_parse *p, const char **d_bases, const char **d_quals, const uint64_t **d_offsets, uint64_t *n_reads,
+                      uint64_t *n_bases);
+/* dbgk_push_reads_device of the batch into h, ordered by events as dbgk_push_corrected is: p may start its next chunk at once.
+ * Handles on different devices: DBGK_ERR_ARG; no batch, or h finalized: DBGK_ERR_STATE.                                    */
+int dbgk_push_parsed(dbgk_handle *h, dbgk_parse *p);
+
 /* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
  * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
  * links between contigs and walks the unambiguous ones into scaffolds.  Contig c (0-based, in the order of the contig file) is node
