@@ -160,6 +160,18 @@ class ParseInfo(C.Structure):
                [(f, C.c_double) for f in ("ms_lines", "ms_states", "ms_scan", "ms_gather")]
 
 
+GZ_PIECE = 65280   # DBGK_GZ_PIECE
+GZ_MAX_LEVEL = 2   # DBGK_GZ_MAX_LEVEL
+
+
+class GzInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_members", "out_bytes", "stored_members", "n_literals", "n_matches", "match_bytes")]
+
+
+class GzTiming(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("ms_members", "ms_match", "ms_crc_hist", "ms_codes", "ms_encode", "ms_compact")]
+
+
 class LinkParams(C.Structure):
     _fields_ = [("mate_pair", C.c_int32), ("pair_num_cut", C.c_int32), ("insert_size", C.c_int32)]
 
@@ -437,6 +449,13 @@ SYMBOLS = [
     ("dbgk_parse_results", _i, [_vp, _vp, _vp, _vp, _vp]),
     ("dbgk_parse_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
     ("dbgk_push_parsed", _i, [_vp, _vp]),
+    ("dbgk_gz_create", _i, [_i, C.POINTER(_vp)]),
+    ("dbgk_gz_destroy", _i, [_vp]),
+    ("dbgk_gz_deflate", _i, [_vp, _vp, _u64, _i, C.POINTER(GzInfo)]),
+    ("dbgk_gz_deflate_device", _i, [_vp, _vp, _u64, _i, C.POINTER(GzInfo)]),
+    ("dbgk_gz_results", _i, [_vp, _vp, _u64]),
+    ("dbgk_gz_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("dbgk_gz_timing_get", _i, [_vp, C.POINTER(GzTiming)]),
     ("dbgk_link_create", _i, [C.POINTER(LinkParams), _i, C.POINTER(_vp)]),
     ("dbgk_link_destroy", _i, [_vp]),
     ("dbgk_link_set_contigs", _i, [_vp, _vp, _u64]),
@@ -1530,6 +1549,79 @@ class Parser:
         _chk(lib().dbgk_parse_results(self._h, bases.ctypes.data, quals.ctypes.data if q else None, offsets.ctypes.data, recs.ctypes.data),
              "dbgk_parse_results")
         return bases[:nb], (quals[:nb] if q else None), offsets, recs[:n]
+
+
+class Deflater:
+    """bytes deflated on the GPU into BGZF-framed gzip members (GZ section of include/dbgk.h): level 0 stored, 1 one dynamic-Huffman
+    block of literals per member, 2 one over LZ77 tokens.  deflate / deflate_device return the members of the call as bytes; `info` holds the counters of
+    the last call; stream() compresses a file window by window."""
+
+    def __init__(self, level=GZ_MAX_LEVEL):
+        self._h = C.c_void_p()
+        self.info = None
+        _chk(lib().dbgk_gz_create(level, C.byref(self._h)), "dbgk_gz_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_gz_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _done(self, info):
+        self.info = {f: getattr(info, f) for f, _ in GzInfo._fields_}
+        return self.results()
+
+    def deflate(self, data, last=True):
+        """text held on the host (bytes, or a uint8 array) -> its members, with the end marker behind them if last"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        info = GzInfo()
+        _chk(lib().dbgk_gz_deflate(self._h, a.ctypes.data if a.size else None, a.size, 1 if last else 0, C.byref(info)), "dbgk_gz_deflate")
+        return self._done(info)
+
+    def deflate_device(self, d_text, n, last=True):
+        """text on the device (pointer, 16-byte aligned, readable up to n rounded up to 16), read in place"""
+        info = GzInfo()
+        _chk(lib().dbgk_gz_deflate_device(self._h, d_text, n, 1 if last else 0, C.byref(info)), "dbgk_gz_deflate_device")
+        return self._done(info)
+
+    def device(self):
+        """-> (device pointer of the members of the last call or None, their bytes)"""
+        p, n = _vp(), _u64()
+        _chk(lib().dbgk_gz_device(self._h, C.byref(p), C.byref(n)), "dbgk_gz_device")
+        return p.value, int(n.value)
+
+    def results(self):
+        """-> the members of the last call as bytes"""
+        _, n = self.device()
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        _chk(lib().dbgk_gz_results(self._h, out.ctypes.data, n), "dbgk_gz_results")
+        return out[:n].tobytes()
+
+    def timing(self):
+        t = GzTiming()
+        _chk(lib().dbgk_gz_timing_get(self._h, C.byref(t)), "dbgk_gz_timing_get")
+        return {f: getattr(t, f) for f, _ in GzTiming._fields_}
+
+    def stream(self, src, dst, chunk_bytes):
+        """src (opened in binary mode) read in windows of chunk_bytes, the members of every window written to dst, the end marker
+        once behind the last -> the summed counters"""
+        if chunk_bytes < 1:
+            raise ValueError("chunk_bytes >= 1")
+        total = {f: 0 for f, _ in GzInfo._fields_}
+        block = src.read(chunk_bytes)
+        while True:
+            ahead = src.read(chunk_bytes) if block else b""
+            dst.write(self.deflate(block, last=not ahead))
+            for f in total:
+                total[f] += self.info[f]
+            if not ahead:
+                return total
+            block = ahead
 
 
 class Cleaner:

@@ -118,6 +118,7 @@ int main(int argc, char *argv[])
 			batch.write(cleanfile1);
 			batch.clear();
 		}
+		cleanfile1.close();
 	}
 	dbgk_clean_destroy(cleaner);
 

@@ -2,6 +2,8 @@
 // reader, gzip line input and output, and strings laid back to back for the device.
 #pragma once
 #include <zlib.h>
+#include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -92,19 +94,91 @@ struct LineReader {
 	}
 };
 
-// what ogzstream writes
+// what ogzstream writes.  With DBGK_GZ=device in the environment the same text leaves as BGZF-framed gzip members deflated on the
+// GPU (dbgk.h, GZ section): it gathers in a host buffer of kWindow bytes, a full buffer is one dbgk_gz_deflate call whose members
+// are written as they come back, and close() writes the rest and the end marker.  zlib's readers inflate both forms to the same
+// bytes.  Without a usable GPU that form fails with the library's error: there is no fall-back to zlib.  A file that cannot be
+// opened is reported and nothing is deflated for it, as the zlib form drops its writes.  A failed device call or a short write ends
+// the program with status 1 from write() or close(); the programs call close() themselves, and the destructor of a writer that is
+// still open only closes the file and says that its output is incomplete -- it deflates nothing and does not exit.
 struct GzWriter {
+	static constexpr size_t kWindow = (size_t)1028 * DBGK_GZ_PIECE; // whole pieces, 64 MiB
 	gzFile f = nullptr;
-	explicit GzWriter(const string &path)
+	FILE *raw = nullptr; // DBGK_GZ=device
+	dbgk_gz_t z = nullptr;
+	string name, pending;
+	vector<char> members;
+	explicit GzWriter(const string &path) : name(path)
 	{
+		const char *form = getenv("DBGK_GZ");
+		if (form && strcmp(form, "device") == 0) {
+			raw = fopen(path.c_str(), "wb");
+			if (!raw) {
+				cerr << "fail to open output file " << path << endl;
+				return;
+			}
+			const int rc = dbgk_gz_create(DBGK_GZ_MAX_LEVEL, &z);
+			if (rc) die("dbgk_gz_create", rc);
+			return;
+		}
 		f = gzopen(path.c_str(), "wb");
 		if (!f) cerr << "fail to open output file " << path << endl;
 	}
-	~GzWriter() { if (f) gzclose(f); }
-	void write(const string &s)
+	GzWriter(const GzWriter &) = delete;
+	GzWriter &operator=(const GzWriter &) = delete;
+	~GzWriter()
 	{
-		if (f && !s.empty()) gzwrite(f, s.data(), (unsigned)s.size());
+		if (f) gzclose(f);
+		if (z) {
+			cerr << "output file " << name << " was not closed: it is incomplete" << endl;
+			dbgk_gz_destroy(z);
+		}
+		if (raw) fclose(raw);
 	}
+	void write_failed()
+	{
+		cerr << "fail to write output file " << name << endl;
+		exit(1);
+	}
+	void deflate_pending(bool last)
+	{
+		dbgk_gz_info info;
+		int rc = dbgk_gz_deflate(z, pending.data(), pending.size(), last ? 1 : 0, &info);
+		if (rc) die("dbgk_gz_deflate", rc);
+		members.resize(info.out_bytes);
+		rc = dbgk_gz_results(z, members.data(), members.size());
+		if (rc) die("dbgk_gz_results", rc);
+		if (!members.empty() && fwrite(members.data(), 1, members.size(), raw) != members.size()) write_failed();
+		pending.clear();
+	}
+	void close()
+	{
+		if (f) gzclose(f);
+		f = nullptr;
+		if (z) {
+			deflate_pending(true);
+			dbgk_gz_destroy(z);
+			z = nullptr;
+		}
+		FILE *file = raw;
+		raw = nullptr;
+		if (file && fclose(file) != 0) write_failed();
+	}
+	void write(const char *p, size_t n)
+	{
+		if (z) {
+			while (n) {
+				const size_t take = min(n, kWindow - pending.size());
+				pending.append(p, take);
+				p += take;
+				n -= take;
+				if (pending.size() == kWindow) deflate_pending(false);
+			}
+			return;
+		}
+		for (size_t at = 0; f && at < n; at += 1u << 30) gzwrite(f, p + at, (unsigned)min<size_t>(n - at, 1u << 30));
+	}
+	void write(const string &s) { write(s.data(), s.size()); }
 };
 
 // the strings of v back to back, string i at bases[offsets[i] .. offsets[i + 1])

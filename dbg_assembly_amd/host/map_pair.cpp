@@ -106,6 +106,9 @@ static void parse_two_paired_reads_file(const Contigs &ctg, const string &input_
 		if (batch.full()) flush();
 	}
 	flush();
+	MapCtgDiff.close();
+	MapCtgSame.close();
+	MapCtgGap.close();
 
 	MapCtgStat << "\ttotal_read_pair_num: " << total_read_pair_num << endl;
 	MapCtgStat << "\tmap_ctg_diff_num: " << map_ctg_diff_num << "  " << (double)map_ctg_diff_num / total_read_pair_num * 100 << "%" << endl;

@@ -101,6 +101,9 @@ static void parse_one_reads_file(const Contigs &ctg, const string &reads_file)
 		if (batch.full()) flush();
 	}
 	flush();
+	MapCtgDiff.close();
+	MapCtgDiffSeq.close();
+	MapCtgSame.close();
 
 	MapCtgStat << "\ttotal_read_num: " << total_read_num << endl;
 	MapCtgStat << "\tmap_ctg_diff_num: " << map_ctg_diff_num << "  " << (double)map_ctg_diff_num / total_read_num * 100 << "%" << endl;

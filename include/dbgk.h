@@ -950,6 +950,59 @@ int dbgk_parse_device(dbgk_parse *p, const char **d_bases, const char **d_quals,
  * Handles on different devices: DBGK_ERR_ARG; no batch, or h finalized: DBGK_ERR_STATE.                                    */
 int dbgk_push_parsed(dbgk_handle *h, dbgk_parse *p);
 
+/* ---- GZ: deflate on the GPU, the output as BGZF-framed gzip members (additions to ABI 7) -------------------------------------------
+ * The text of a call is cut into pieces of at most 65 280 bytes, every piece but the last exactly that long, and every piece becomes
+ * one gzip member of its own: the 18-byte header 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, the subfield 42 43 02 00 and BSIZE
+ * (u16, the member's size - 1); ONE deflate block with BFINAL set; CRC-32 and ISIZE of the piece.  Concatenated members are a
+ * valid gzip file (zlib's gzread, Python's gzip and bgzip read them), and BSIZE makes the file self-delimiting.  With last != 0 the
+ * 28-byte BGZF end marker follows the members; empty input gives the marker alone, or nothing with last == 0.  Calls are stateless:
+ * no history, code or checksum carries over, and a short last member per call is fine.  Levels, fixed at creation:
+ *   0  stored blocks;
+ *   1  one dynamic-Huffman block of literals only;
+ *   2  dynamic Huffman over LZ77 tokens (the default of the Python binding and the bin/ programs): matches of length 3..258 at
+ *      distance 1..32 768 that never reach into another member or past the piece's end, chosen by a deterministic rule.
+ * At levels 1 and 2 a member whose dynamic block would not be smaller than its stored block is written stored.  Fixed-Huffman blocks
+ * are not used.  The same input gives the same bytes on every run.
+ * The members are independent, which is what lets them be built (and later inflated) in parallel and costs the size DESIGN.md
+ * states.  The construction rules of the codes are DESIGN.md's; CRC-32 is computed on the device.                              */
+typedef struct dbgk_gz dbgk_gz;
+typedef dbgk_gz *dbgk_gz_t;
+#define DBGK_GZ_PIECE 65280         /* bytes of text per member                                                             */
+#define DBGK_GZ_MAX_LEVEL 2
+typedef struct dbgk_gz_info {
+	uint64_t n_members;         /* members with text: ceil(n_bytes / 65280); the end marker is not counted              */
+	uint64_t out_bytes;         /* all bytes of the call's output, the marker included                                  */
+	uint64_t stored_members;    /* members written with a stored block                                                  */
+	uint64_t n_literals;        /* literal tokens of the dynamic blocks (a stored member has no tokens)                 */
+	uint64_t n_matches;         /* match tokens of the dynamic blocks and the bytes they cover (0 at levels 0 and 1)    */
+	uint64_t match_bytes;
+} dbgk_gz_info;
+typedef struct dbgk_gz_timing {     /* device time of the last call.  A member is built by ONE launch from the piece in LDS, */
+	double ms_members;          /* timed by events; its phases are that time divided by the shares of the shader-clock   */
+	double ms_match;            /* cycles that lane 0 of every workgroup counted between them: the matcher (level 2;     */
+	double ms_crc_hist;         /* else 0); staging,      CRC-32 and the histogram, which are one pass over the piece;   */
+	double ms_codes;            /* ranking, code lengths, codes and the block header; bit count, scan, zeroing and       */
+	double ms_encode;           /* encoding.  ms_match + ms_crc_hist + ms_codes + ms_encode == ms_members.               */
+	double ms_compact;          /* the scan of the sizes and the gather, by events                                       */
+} dbgk_gz_timing;
+/* on the current device.  A level outside 0..DBGK_GZ_MAX_LEVEL: DBGK_ERR_ARG, before any device work.  DBGK_ERR_HIP without a
+ * usable gfx950 device: there is no host fall-back                                                                         */
+int dbgk_gz_create(int level, dbgk_gz_t *out);
+int dbgk_gz_destroy(dbgk_gz_t z);
+/* text on the host, uploaded by the call.  n_bytes < 2^31 (else DBGK_ERR_ARG); n_bytes == 0 is valid.  info may be null.  Returns
+ * when the output is complete.                                                                                             */
+int dbgk_gz_deflate(dbgk_gz_t z, const void *text, uint64_t n_bytes, int last, dbgk_gz_info *info);
+/* the same for text in device memory of z's GPU, read in place and never written: d_text 16-byte aligned (else DBGK_ERR_ARG) and
+ * readable up to n_bytes rounded up to 16; no byte at or behind n_bytes influences a result.  The handle's own output as input:
+ * DBGK_ERR_ARG.  Work of the caller's own on the text has to be synchronised.                                              */
+int dbgk_gz_deflate_device(dbgk_gz_t z, const void *d_text, uint64_t n_bytes, int last, dbgk_gz_info *info);
+/* host copy of the output of the last call: out_bytes bytes; a capacity below that: DBGK_ERR_ARG.  Before a successful call:
+ * DBGK_ERR_STATE (also for dbgk_gz_device).                                                                                */
+int dbgk_gz_results(dbgk_gz_t z, void *out, uint64_t capacity);
+/* the output where it lies (null if it is empty); valid until the next call or dbgk_gz_destroy                             */
+int dbgk_gz_device(dbgk_gz_t z, const void **d_out, uint64_t *n_out);
+int dbgk_gz_timing_get(dbgk_gz_t z, dbgk_gz_timing *t);
+
 /* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
  * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
  * links between contigs and walks the unambiguous ones into scaffolds.  Contig c (0-based, in the order of the contig file) is node
