@@ -172,6 +172,21 @@ class GzTiming(C.Structure):
     _fields_ = [(f, C.c_double) for f in ("ms_members", "ms_match", "ms_crc_hist", "ms_codes", "ms_encode", "ms_compact")]
 
 
+INF_ROUND = 4000   # DBGK_INF_ROUND
+INF_REASONS = ("OK", "BLOCK_TYPE", "STORED_LEN", "STORED_PAST", "TOO_MANY_SYMS", "CL_OVER", "CL_INCOMPLETE", "CODE_OVER", "CODE_INCOMPLETE",
+               "REPEAT_FIRST", "REPEAT_PAST", "NO_EOB", "BAD_LENGTH", "BAD_DISTANCE", "DISTANCE_FAR", "TRUNCATED", "GARBAGE", "OUT_MORE", "OUT_LESS",
+               "CRC", "FRAME")   # DBGK_INF_*: a member's verdict is the index
+
+
+class InfInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_members", "n_markers", "consumed", "out_bytes", "n_stored", "n_fixed", "n_dynamic", "n_literals", "n_matches",
+                                          "n_bad", "first_bad")] + [("first_bad_reason", C.c_uint32)]
+
+
+class InfTiming(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("ms_decode", "ms_resolve", "ms_scan")]
+
+
 class LinkParams(C.Structure):
     _fields_ = [("mate_pair", C.c_int32), ("pair_num_cut", C.c_int32), ("insert_size", C.c_int32)]
 
@@ -456,6 +471,14 @@ SYMBOLS = [
     ("dbgk_gz_results", _i, [_vp, _vp, _u64]),
     ("dbgk_gz_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("dbgk_gz_timing_get", _i, [_vp, C.POINTER(GzTiming)]),
+    ("dbgk_inf_create", _i, [_u64, C.POINTER(_vp)]),
+    ("dbgk_inf_destroy", _i, [_vp]),
+    ("dbgk_inf_inflate", _i, [_vp, _vp, _u64, _i, C.POINTER(InfInfo)]),
+    ("dbgk_inf_inflate_device", _i, [_vp, _vp, _u64, C.POINTER(_u64), _u64, C.POINTER(InfInfo)]),
+    ("dbgk_inf_results", _i, [_vp, _vp, _u64]),
+    ("dbgk_inf_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("dbgk_inf_member_status", _i, [_vp, _vp, _u64]),
+    ("dbgk_inf_timing_get", _i, [_vp, C.POINTER(InfTiming)]),
     ("dbgk_link_create", _i, [C.POINTER(LinkParams), _i, C.POINTER(_vp)]),
     ("dbgk_link_destroy", _i, [_vp]),
     ("dbgk_link_set_contigs", _i, [_vp, _vp, _u64]),
@@ -1622,6 +1645,108 @@ class Deflater:
             if not ahead:
                 return total
             block = ahead
+
+
+class Inflater:
+    """BGZF-framed gzip members inflated on the GPU (INFLATE section of include/dbgk.h).  inflate / inflate_device return the bytes
+    of the members of the call and its counters; a member that is refused leaves zeros, `info["n_bad"]` counts them and member_status()
+    says why; device() is the text where it lies, for Parser.chunk_device; stream() inflates a file window by window."""
+
+    def __init__(self, max_out_bytes=0):
+        self._h = C.c_void_p()
+        self.info = None
+        _chk(lib().dbgk_inf_create(max_out_bytes, C.byref(self._h)), "dbgk_inf_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_inf_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _done(self, info):
+        self.info = {f: getattr(info, f) for f, _ in InfInfo._fields_}
+        return self.results(), self.info
+
+    def inflate(self, data, last=True):
+        """members held on the host (bytes, or a uint8 array) -> (their bytes, info); with last=False a member cut short at the end
+        is left unconsumed: info["consumed"]"""
+        a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        info = InfInfo()
+        _chk(lib().dbgk_inf_inflate(self._h, a.ctypes.data if a.size else None, a.size, 1 if last else 0, C.byref(info)), "dbgk_inf_inflate")
+        return self._done(info)
+
+    def inflate_device(self, d_gz, offsets, n_bytes=None):
+        """members on the device: d_gz a pointer (16-byte aligned) or a uint8 torch tensor; offsets: where each member starts and,
+        last, where the last one ends.  n_bytes: the buffer's size (a tensor's own by default, else the last offset)"""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if off.size < 1:
+            raise ValueError("n_members + 1 offsets")
+        if hasattr(d_gz, "data_ptr"):
+            n_bytes = d_gz.numel() if n_bytes is None else n_bytes
+            d_gz = d_gz.data_ptr()
+        n_bytes = int(off[-1]) if n_bytes is None else n_bytes
+        info = InfInfo()
+        _chk(lib().dbgk_inf_inflate_device(self._h, d_gz, n_bytes, off.ctypes.data_as(C.POINTER(_u64)), off.size - 1, C.byref(info)), "dbgk_inf_inflate_device")
+        return self._done(info)
+
+    def device_ptr(self):
+        """-> (device pointer of the text of the last call or None, its bytes)"""
+        p, n = _vp(), _u64()
+        _chk(lib().dbgk_inf_device(self._h, C.byref(p), C.byref(n)), "dbgk_inf_device")
+        return p.value, int(n.value)
+
+    def device(self):
+        """-> the text of the last call as a uint8 torch tensor that views the handle's memory (valid until the next call): 16-byte
+        aligned and readable up to its size rounded up to 16, so Parser.chunk_device(t.data_ptr(), t.numel()) reads it in place"""
+        import torch
+        p, n = self.device_ptr()
+        if not n:
+            return torch.empty(0, dtype=torch.uint8, device="cuda")
+
+        class _View:
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (p, False), "version": 2}
+        t = torch.as_tensor(_View(), device="cuda")
+        t._dbgk_owner = self
+        return t
+
+    def results(self):
+        """-> the text of the last call as bytes"""
+        _, n = self.device_ptr()
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        _chk(lib().dbgk_inf_results(self._h, out.ctypes.data, n), "dbgk_inf_results")
+        return out[:n].tobytes()
+
+    def member_status(self):
+        """-> one verdict per member of the last call (uint8; names in INF_REASONS)"""
+        n = self.info["n_members"] if self.info else 0
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        _chk(lib().dbgk_inf_member_status(self._h, out.ctypes.data, n), "dbgk_inf_member_status")
+        return out[:n]
+
+    def timing(self):
+        t = InfTiming()
+        _chk(lib().dbgk_inf_timing_get(self._h, C.byref(t)), "dbgk_inf_timing_get")
+        return {f: getattr(t, f) for f, _ in InfTiming._fields_}
+
+    def stream(self, fileobj, window):
+        """the members of fileobj (opened in binary mode) in windows of `window` bytes, each with what the window before it left
+        unconsumed in front -> yields (bytes, info) per window; a tail that is no whole member at the end of the file is an error"""
+        if window < 1:
+            raise ValueError("window >= 1")
+        carry, block = b"", fileobj.read(window)
+        while True:
+            ahead = fileobj.read(window) if block else b""
+            data = carry + block
+            text, info = self.inflate(data, last=not ahead)
+            yield text, info
+            if not ahead:
+                return
+            carry, block = data[info["consumed"]:], ahead
 
 
 class Cleaner:

@@ -33,6 +33,7 @@
 #include "dbgk_pair.h"
 #include "dbgk_parse.h"
 #include "dbgk_gz.h"
+#include "dbgk_inflate.h"
 #include "dbgk_link.h"
 #include "dbgk_fill.h"
 #include "dbgk_super.h"
@@ -479,6 +480,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_pair.h"
 #include "dbgk_host_parse.h"
 #include "dbgk_host_gz.h"
+#include "dbgk_host_inflate.h"
 #include "dbgk_host_link.h"
 #include "dbgk_host_fill.h"
 #include "dbgk_host_super.h"

@@ -54,31 +54,116 @@ static void die(const char *what, int rc)
 }
 
 // getline over a plain or gzip file (what igzstream + getline read); a caller with a message of its own for a failed open
-// passes report = false and asks ok()
+// passes report = false and asks ok().  With DBGK_GUNZIP=device in the environment a file that begins with the 16 fixed header bytes
+// of a BGZF member (dbgk.h, GZ and INFLATE sections) is inflated on the GPU: it is read raw in windows of kWindow bytes, a window and
+// what the one before it left unconsumed is one dbgk_inf_inflate call that delivers at most kText bytes, and getline is served from
+// the inflated bytes.  Any other file -- plain text, an ordinary gzip file -- and any other value of the variable go through zlib as
+// ever.  Without a usable GPU the device form fails with the library's error: there is no fall-back to zlib.  A member that the
+// device refuses ends the program with status 1.  The device form exists where the program is built with DBGK_READER_DEVICE, as
+// host/Makefile builds every bin/ program; a test driver of the host readers that does not link libdbgk.so gets the zlib reader alone.
 struct LineReader {
+	static constexpr size_t kWindow = (size_t)16 << 20, kText = (size_t)64 << 20; // host buffers near the writer's 64 MiB
 	gzFile f = nullptr;
-	vector<char> buf = vector<char>(1 << 20);
-	size_t pos = 0, len = 0;
-	bool eof = false;
-	explicit LineReader(const string &path, bool report = true)
+	FILE *raw = nullptr; // DBGK_GUNZIP=device
+	dbgk_inf_t z = nullptr;
+	string name;
+	vector<char> buf = vector<char>(1 << 20), in;
+	size_t pos = 0, len = 0, in_len = 0;
+	uint64_t members_done = 0;
+	bool eof = false, raw_eof = false;
+	explicit LineReader(const string &path, bool report = true) : name(path)
 	{
+#ifdef DBGK_READER_DEVICE
+		const char *form = getenv("DBGK_GUNZIP");
+		if (form && strcmp(form, "device") == 0 && open_device()) return;
+#endif
 		f = gzopen(path.c_str(), "rb");
 		if (f) gzbuffer(f, 1 << 20);
 		else if (report) cerr << "fail to open input file " << path << endl;
 	}
-	~LineReader() { if (f) gzclose(f); }
-	bool ok() const { return f != nullptr; }
+	LineReader(const LineReader &) = delete;
+	LineReader &operator=(const LineReader &) = delete;
+	~LineReader()
+	{
+		if (f) gzclose(f);
+#ifdef DBGK_READER_DEVICE
+		if (z) dbgk_inf_destroy(z);
+#endif
+		if (raw) fclose(raw);
+	}
+	bool ok() const { return f != nullptr || raw != nullptr; }
+#ifdef DBGK_READER_DEVICE
+	// the file is this framing by its first 18 bytes: it stays open raw and a handle exists
+	bool open_device()
+	{
+		static const unsigned char head[16] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0};
+		raw = fopen(name.c_str(), "rb");
+		if (!raw) return false;
+		in.resize(kWindow + (1 << 16));
+		in_len = fread(in.data(), 1, 18, raw);
+		if (in_len != 18 || memcmp(in.data(), head, 16) != 0) {
+			fclose(raw);
+			raw = nullptr;
+			in.clear();
+			in.shrink_to_fit();
+			in_len = 0;
+			return false;
+		}
+		const int rc = dbgk_inf_create(kText, &z);
+		if (rc) die("dbgk_inf_create", rc);
+		return true;
+	}
+	// the next window's text into buf; false at the end of the file
+	bool refill_device()
+	{
+		for (;;) {
+			if (!raw_eof && in_len < kWindow) {
+				const size_t room = kWindow - in_len, n = fread(in.data() + in_len, 1, room, raw);
+				in_len += n;
+				if (n < room) raw_eof = true;
+			}
+			if (in_len == 0) return false;
+			dbgk_inf_info info;
+			int rc = dbgk_inf_inflate(z, in.data(), in_len, raw_eof ? 1 : 0, &info);
+			if (rc) {
+				cerr << "fail to inflate input file " << name << ": " << dbgk_last_error() << endl;
+				die("dbgk_inf_inflate", rc);
+			}
+			if (info.n_bad) {
+				const string what = "inflate of input file " + name + ": member " + to_string(members_done + info.first_bad) + " refused, reason " +
+				                    to_string(info.first_bad_reason) + " (DBGK_INF_* of dbgk.h): dbgk_inf_inflate";
+				die(what.c_str(), DBGK_ERR_ARG);
+			}
+			if (info.n_members == 0) die("dbgk_inf_inflate (a window without a whole member)", DBGK_ERR_STATE);
+			buf.resize(max<size_t>(info.out_bytes, 1));
+			rc = dbgk_inf_results(z, buf.data(), buf.size());
+			if (rc) die("dbgk_inf_results", rc);
+			members_done += info.n_members;
+			memmove(in.data(), in.data() + info.consumed, in_len - info.consumed);
+			in_len -= info.consumed;
+			pos = 0;
+			len = info.out_bytes;
+			if (len) return true; // (else: end markers only)
+		}
+	}
+#else
+	bool refill_device() { return false; }
+#endif
 	bool getline(string &s)
 	{
 		s.clear();
 		bool any = false;
 		for (;;) {
 			if (pos == len) {
-				if (eof || !f) return any;
-				const int n = gzread(f, buf.data(), (unsigned)buf.size());
-				if (n <= 0) { eof = true; return any; }
-				pos = 0;
-				len = (size_t)n;
+				if (eof || !ok()) return any;
+				if (raw) {
+					if (!refill_device()) { eof = true; return any; }
+				} else {
+					const int n = gzread(f, buf.data(), (unsigned)buf.size());
+					if (n <= 0) { eof = true; return any; }
+					pos = 0;
+					len = (size_t)n;
+				}
 			}
 			any = true;
 			const char *b = buf.data() + pos;

@@ -892,7 +892,7 @@ int dbgk_pair_device(dbgk_pair *p, int which, const char **d_bases, const char *
 int dbgk_push_pairs(dbgk_handle *h, dbgk_pair *p, int which);
 
 /* ---- PARSE: from a FASTQ / FASTA file's bytes to the device batch (additions to ABI 7) ---------------------------------------------
- * The stage in front of the first stage: the caller uploads the text of the file as it is (a gz file inflated first), the handle
+ * The stage in front of the first stage: the caller uploads the text of the file as it is (a gz file through dbgk_inf_inflate first), the handle
  * finds the records on the device and leaves the batch in the layout of dbgk_corr_compact / dbgk_clean_compact -- each plane from a
  * 16-byte boundary in whole 16-byte vectors, the pad of the last one 0, 64 readable bytes behind the end, n + 1 64-bit offsets -- so
  * dbgk_clean_*_device, dbgk_corr_reads_device, dbgk_pair_split_device, dbgk_push_reads_device and dbgk_map_reads_device read it where it
@@ -963,7 +963,7 @@ int dbgk_push_parsed(dbgk_handle *h, dbgk_parse *p);
  *      distance 1..32 768 that never reach into another member or past the piece's end, chosen by a deterministic rule.
  * At levels 1 and 2 a member whose dynamic block would not be smaller than its stored block is written stored.  Fixed-Huffman blocks
  * are not used.  The same input gives the same bytes on every run.
- * The members are independent, which is what lets them be built (and later inflated) in parallel and costs the size DESIGN.md
+ * The members are independent, which is what lets them be built (and inflated: the INFLATE section) in parallel and costs the size DESIGN.md
  * states.  The construction rules of the codes are DESIGN.md's; CRC-32 is computed on the device.                              */
 typedef struct dbgk_gz dbgk_gz;
 typedef dbgk_gz *dbgk_gz_t;
@@ -1002,6 +1002,89 @@ int dbgk_gz_results(dbgk_gz_t z, void *out, uint64_t capacity);
 /* the output where it lies (null if it is empty); valid until the next call or dbgk_gz_destroy                             */
 int dbgk_gz_device(dbgk_gz_t z, const void **d_out, uint64_t *n_out);
 int dbgk_gz_timing_get(dbgk_gz_t z, dbgk_gz_timing *t);
+
+/* ---- INFLATE: inflate on the GPU, BGZF-framed gzip members decoded in parallel (additions to ABI 7) --------------------------------
+ * The reader that the GZ section's members were made independent for.  Input: gzip members in exactly that section's framing -- the
+ * 16 fixed header bytes, BSIZE, a deflate stream, CRC-32 and ISIZE <= 65 280 -- back to back; htslib's bgzip writes the same 16
+ * bytes, so its files are accepted too.  The stream inside a member may be anything RFC 1951 allows: stored, fixed and dynamic
+ * blocks, any number of them, empty stored blocks of a flush, codes of up to 15 bits, a distance code of one symbol or none,
+ * matches that overlap themselves, distances of up to 32 768.  Output: the members' bytes back to back, on the device.
+ * Every member gets a verdict: 0, or the first reason below for which it was refused.  What zlib accepts is accepted, what it refuses
+ * is refused.  A refused member's range of the output is zero bytes and no other member is disturbed; a call that ran returns
+ * DBGK_OK whatever the verdicts, n_bad counts them.  The same input gives the same bytes, verdicts and counters on every run.
+ * Temporary device memory is the token area: 4 000 members x 65 280 tokens x 4 bytes = 1 044 480 000 bytes at the most, whatever the
+ * size of the call; members are processed in rounds of 4 000.  (28 bytes of table and verdict per member come on top.)
+ * Calls are stateless apart from buffers.  There is no host fall-back inside the library.                                        */
+typedef struct dbgk_inf dbgk_inf;
+typedef dbgk_inf *dbgk_inf_t;
+#define DBGK_INF_ROUND 4000             /* members per round of the token area                                                */
+#define DBGK_INF_OK 0
+#define DBGK_INF_BLOCK_TYPE 1           /* block type 3                                                                       */
+#define DBGK_INF_STORED_LEN 2           /* a stored block's LEN is not the complement of its NLEN                             */
+#define DBGK_INF_STORED_PAST 3          /* a stored block's LEN runs past the member                                          */
+#define DBGK_INF_TOO_MANY_SYMS 4        /* HLIT above 286 or HDIST above 30                                                   */
+#define DBGK_INF_CL_OVER 5              /* the code of the code lengths is over-subscribed                                    */
+#define DBGK_INF_CL_INCOMPLETE 6        /* ... or incomplete                                                                  */
+#define DBGK_INF_CODE_OVER 7            /* the literal/length or the distance code is over-subscribed                         */
+#define DBGK_INF_CODE_INCOMPLETE 8      /* ... or incomplete and not a single code of one bit                                 */
+#define DBGK_INF_REPEAT_FIRST 9         /* repeat code 16 as the first length                                                 */
+#define DBGK_INF_REPEAT_PAST 10         /* a repeat that runs past HLIT + HDIST                                               */
+#define DBGK_INF_NO_EOB 11              /* no code for symbol 256                                                             */
+#define DBGK_INF_BAD_LENGTH 12          /* length symbol 286 or 287, or bits that are no literal/length code                  */
+#define DBGK_INF_BAD_DISTANCE 13        /* distance symbol 30 or 31, or bits that are no distance code                        */
+#define DBGK_INF_DISTANCE_FAR 14        /* a distance that reaches in front of the member's first byte                        */
+#define DBGK_INF_TRUNCATED 15           /* the stream ends in mid-symbol at the trailer                                       */
+#define DBGK_INF_GARBAGE 16             /* the final block ends before the trailer                                            */
+#define DBGK_INF_OUT_MORE 17            /* more output than ISIZE                                                             */
+#define DBGK_INF_OUT_LESS 18            /* less output than ISIZE                                                             */
+#define DBGK_INF_CRC 19                 /* the CRC-32 of the output is not the trailer's                                      */
+#define DBGK_INF_FRAME 20               /* dbgk_inf_inflate_device: no member of this framing where the table says one is     */
+typedef struct dbgk_inf_info {
+	uint64_t n_members;         /* members inflated by the call (end markers and other ISIZE-0 members included)        */
+	uint64_t n_markers;         /* ... of which the 28-byte end marker, byte for byte                                   */
+	uint64_t consumed;          /* bytes of input used up: whole members only                                           */
+	uint64_t out_bytes;
+	uint64_t n_stored, n_fixed, n_dynamic;   /* blocks of the members whose streams decoded: verdict 0 or DBGK_INF_CRC    */
+	uint64_t n_literals, n_matches;          /* their tokens; a byte of a stored block is a literal                     */
+	uint64_t n_bad;             /* members with a verdict other than 0                                                  */
+	uint64_t first_bad;         /* index of the first, and its reason                                                   */
+	uint32_t first_bad_reason;
+} dbgk_inf_info;
+typedef struct dbgk_inf_timing {    /* device time of the last call, by events                                             */
+	double ms_decode;           /* k_inf_decode, all rounds                                                             */
+	double ms_resolve;          /* k_inf_resolve, all rounds                                                            */
+	double ms_scan;             /* the frame check and the scan of ISIZE                                                */
+} dbgk_inf_timing;
+/* on the current device.  max_out_bytes: the most a call delivers; 0: the default, 2^31 - 65536, so that a result always fits one
+ * chunk of the parser; above that: DBGK_ERR_ARG.  DBGK_ERR_HIP without a usable gfx950 device: there is no host fall-back      */
+int dbgk_inf_create(uint64_t max_out_bytes, dbgk_inf_t *out);
+int dbgk_inf_destroy(dbgk_inf_t z);
+/* members on the host.  The host follows BSIZE from member to member (two bytes each), takes whole members from the front while the
+ * sum of ISIZE stays within max_out_bytes, uploads them and inflates them.  info->consumed is the first byte not used up: with
+ * last == 0 a member that is cut short at the end is not consumed, and the caller presents the bytes from there on again at the front
+ * of its next call; with last != 0 a cut-short tail is DBGK_ERR_ARG.  Bytes that are not this framing -- plain gzip, plain text,
+ * other extra subfields, ISIZE above 65 280 -- give DBGK_ERR_ARG before any device work, and dbgk_last_error() says which: that is
+ * how a caller learns that the file is zlib's to read.  n_bytes < 2^31 (else DBGK_ERR_ARG); n_bytes == 0 is valid.  info may be
+ * null.  Returns when the output is complete.                                                                               */
+int dbgk_inf_inflate(dbgk_inf_t z, const void *gz, uint64_t n_bytes, int last, dbgk_inf_info *info);
+/* the same for members in device memory of z's GPU, read in place and never written: d_gz 16-byte aligned (else DBGK_ERR_ARG);
+ * member_offsets, on the host, says where each of the n_members members starts and, in its last entry, where the last one ends:
+ * n_members + 1 offsets that do not decrease, the last one at most n_bytes (else DBGK_ERR_ARG).  No byte outside the members' ranges
+ * is read.  A range that does not hold a member of the framing gets the verdict DBGK_INF_FRAME and no output.  A sum of ISIZE
+ * above max_out_bytes, or the handle's own output as input: DBGK_ERR_ARG.  consumed is the last offset.  The members must be
+ * complete in d_gz before the call: the handle works on a stream of its own that waits for no work of the caller's, so work of the
+ * caller's own that writes them has to be synchronised first.                                                                */
+int dbgk_inf_inflate_device(dbgk_inf_t z, const void *d_gz, uint64_t n_bytes, const uint64_t *member_offsets, uint64_t n_members,
+                            dbgk_inf_info *info);
+/* host copy of the output of the last call: out_bytes bytes; a capacity below that: DBGK_ERR_ARG.  Before a successful call:
+ * DBGK_ERR_STATE (also for dbgk_inf_device and dbgk_inf_member_status).                                                      */
+int dbgk_inf_results(dbgk_inf_t z, void *out, uint64_t capacity);
+/* the output where it lies (null if it is empty): 16-byte aligned and readable up to n_bytes rounded up to 16, which is what
+ * dbgk_parse_chunk_device and dbgk_gz_deflate_device ask for; valid until the next call or dbgk_inf_destroy                  */
+int dbgk_inf_device(dbgk_inf_t z, const void **d_text, uint64_t *n_bytes);
+/* one verdict per member of the last call; a capacity below n_members: DBGK_ERR_ARG                                          */
+int dbgk_inf_member_status(dbgk_inf_t z, uint8_t *reason, uint64_t capacity);
+int dbgk_inf_timing_get(dbgk_inf_t z, dbgk_inf_timing *t);
 
 /* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
  * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
