@@ -160,6 +160,14 @@ class ParseInfo(C.Structure):
                [(f, C.c_double) for f in ("ms_lines", "ms_states", "ms_scan", "ms_gather")]
 
 
+FMT_TILE = 4096  # DBGK_FMT_TILE
+
+
+class FmtInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_records", "out_bytes", "head_bytes", "suffix_bytes", "seq_bytes")] + \
+               [("ms_scan", C.c_double), ("ms_gather", C.c_double)]
+
+
 GZ_PIECE = 65280   # DBGK_GZ_PIECE
 GZ_MAX_LEVEL = 2   # DBGK_GZ_MAX_LEVEL
 
@@ -464,6 +472,14 @@ SYMBOLS = [
     ("dbgk_parse_results", _i, [_vp, _vp, _vp, _vp, _vp]),
     ("dbgk_parse_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
     ("dbgk_push_parsed", _i, [_vp, _vp]),
+    ("dbgk_fmt_create", _i, [C.c_int32, C.c_int32, _i, C.POINTER(_vp)]),
+    ("dbgk_fmt_destroy", _i, [_vp]),
+    ("dbgk_fmt_records_device", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, C.POINTER(FmtInfo)]),
+    ("dbgk_fmt_records", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, C.POINTER(FmtInfo)]),
+    ("dbgk_fmt_results", _i, [_vp, _vp, _u64]),
+    ("dbgk_fmt_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("dbgk_parse_recs_device", _i, [_vp, C.POINTER(_vp)]),
+    ("dbgk_parse_text_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("dbgk_gz_create", _i, [_i, C.POINTER(_vp)]),
     ("dbgk_gz_destroy", _i, [_vp]),
     ("dbgk_gz_deflate", _i, [_vp, _vp, _u64, _i, C.POINTER(GzInfo)]),
@@ -1572,6 +1588,105 @@ class Parser:
         _chk(lib().dbgk_parse_results(self._h, bases.ctypes.data, quals.ctypes.data if q else None, offsets.ctypes.data, recs.ctypes.data),
              "dbgk_parse_results")
         return bases[:nb], (quals[:nb] if q else None), offsets, recs[:n]
+
+
+class Formatter:
+    """A compact batch written as FASTQ (fmt 1) / FASTA (fmt 2) text on the GPU (FORMAT section of include/dbgk.h): the headers from the
+    text the parser parsed, the reads from the planes of a compact batch, an optional suffix per header from the host.  marker: 0,
+    or the byte that replaces the first byte of every header.  format / format_device return the info as a dict (also kept in
+    `info`); results() and device() give the text."""
+
+    def __init__(self, fmt, marker=0, device=0):
+        self._h = C.c_void_p()
+        self.info = None
+        if isinstance(marker, (bytes, str)):
+            marker = ord(marker)
+        _chk(lib().dbgk_fmt_create(fmt, marker, device, C.byref(self._h)), "dbgk_fmt_create")
+
+    def close(self):
+        if self._h:
+            lib().dbgk_fmt_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @staticmethod
+    def _suffix_plane(suffixes, n):
+        """None, a list of n bytes objects, or (uint8 bytes, uint64 offsets[n + 1]) -> the two arrays, or (None, None)"""
+        if suffixes is None:
+            return None, None
+        if isinstance(suffixes, tuple):
+            data, off = suffixes
+            return np.ascontiguousarray(data, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.uint64)
+        if len(suffixes) != n:
+            raise ValueError("one suffix per record")
+        off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum([len(x) for x in suffixes], out=off[1:])
+        return np.frombuffer(b"".join(suffixes), dtype=np.uint8), off
+
+    def _done(self, info):
+        self.info = {f: getattr(info, f) for f, _ in FmtInfo._fields_}
+        return self.info
+
+    def format(self, text, recs, bases, quals, offsets, suffixes=None):
+        """everything held on the host: the text (bytes, or a uint8 array), PARSE_REC_DTYPE[n], the planes (quals None for FASTA)
+        and uint64 offsets[n + 1]; suffixes as _suffix_plane takes them"""
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        recs = np.ascontiguousarray(recs, dtype=PARSE_REC_DTYPE)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(recs)
+        if len(offsets) != n + 1:
+            raise ValueError("n + 1 offsets")
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        quals = None if quals is None else np.ascontiguousarray(quals, dtype=np.uint8)
+        pad = np.zeros(1, dtype=np.uint8)  # (a plane of no bytes still says whether there is one)
+        sd, so = self._suffix_plane(suffixes, n)
+        info = FmtInfo()
+        _chk(lib().dbgk_fmt_records(self._h, t.ctypes.data if t.size else None, t.size, recs.ctypes.data if n else None,
+                                    (bases if bases.size else pad).ctypes.data, None if quals is None else (quals if quals.size else pad).ctypes.data,
+                                    offsets.ctypes.data, n, sd.ctypes.data if sd is not None and sd.size else None,
+                                    so.ctypes.data if so is not None else None, C.byref(info)), "dbgk_fmt_records")
+        return self._done(info)
+
+    def format_device(self, source, planes, suffixes=None):
+        """source: a Parser after a chunk (its text and records where they lie), (parser, d_text, n_text) -- a Parser and the chunk
+        its last chunk_device parsed -- or the pointers (d_text, n_text, d_recs) themselves; planes: (d_bases, d_quals or None, d_offsets, n) as the device() of a Parser, Cleaner, Corrector or
+        Pairer gives them (further entries are ignored); suffixes as _suffix_plane takes them"""
+        if isinstance(source, Parser):   # the chunk of its last call, where chunk() uploaded it or chunk_device() read it
+            d_text, nt = _vp(), _u64()
+            _chk(lib().dbgk_parse_text_device(source._h, C.byref(d_text), C.byref(nt)), "dbgk_parse_text_device")
+            source = (source, d_text.value, int(nt.value))
+        if isinstance(source[0], Parser):
+            parser, d_text, nt = source
+            d_recs = _vp()
+            _chk(lib().dbgk_parse_recs_device(parser._h, C.byref(d_recs)), "dbgk_parse_recs_device")
+            d_recs = d_recs.value
+        else:
+            d_text, nt, d_recs = source
+        d_bases, d_quals, d_off, n = planes[:4]
+        sd, so = self._suffix_plane(suffixes, n)
+        info = FmtInfo()
+        _chk(lib().dbgk_fmt_records_device(self._h, d_text, nt, d_recs, d_bases, d_quals, d_off, n,
+                                           sd.ctypes.data if sd is not None and sd.size else None, so.ctypes.data if so is not None else None,
+                                           C.byref(info)), "dbgk_fmt_records_device")
+        return self._done(info)
+
+    def device(self):
+        """-> (device pointer of the text of the last call, its bytes)"""
+        p, n = _vp(), _u64()
+        _chk(lib().dbgk_fmt_device(self._h, C.byref(p), C.byref(n)), "dbgk_fmt_device")
+        return p.value, int(n.value)
+
+    def results(self):
+        """-> the text of the last call as bytes"""
+        _, n = self.device()
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        _chk(lib().dbgk_fmt_results(self._h, out.ctypes.data, n), "dbgk_fmt_results")
+        return out[:n].tobytes()
 
 
 class Deflater:

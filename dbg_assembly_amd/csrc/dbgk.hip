@@ -32,6 +32,7 @@
 #include "dbgk_emit.h"
 #include "dbgk_pair.h"
 #include "dbgk_parse.h"
+#include "dbgk_format.h"
 #include "dbgk_gz.h"
 #include "dbgk_inflate.h"
 #include "dbgk_link.h"
@@ -479,6 +480,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_clean.h"
 #include "dbgk_host_pair.h"
 #include "dbgk_host_parse.h"
+#include "dbgk_host_format.h"
 #include "dbgk_host_gz.h"
 #include "dbgk_host_inflate.h"
 #include "dbgk_host_link.h"

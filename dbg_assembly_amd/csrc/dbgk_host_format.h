@@ -1,0 +1,281 @@
+// FORMAT stage, host side (include/dbgk.h, FORMAT section; kernels in dbgk_format.h): the output text of one batch on the device,
+// its read-back and its device view.  The launches of a call follow each other on one stream; the host reads the counters and the
+// total in between, which size the text.
+
+struct dbgk_fmt {
+	int device = 0;
+	int n_cu = 256;
+	int format = 1;
+	uint32_t marker = 0;
+	hipStream_t stream = nullptr;
+	uint8_t *out = nullptr; // 16-byte vectors, the pad of the last one 0, 64 readable bytes behind
+	uint64_t cap_out = 0, n_out = 0;
+	bool have = false;
+	uint32_t *len = nullptr; // n + 1 output lengths and their exclusive scan
+	uint64_t *coff = nullptr;
+	uint64_t cap_recs = 0;
+	void *tmp = nullptr; // the scan's temporary storage
+	size_t tmp_bytes = 0;
+	unsigned long long *ctr = nullptr;
+	uint8_t *suf = nullptr; // the uploaded suffix plane
+	uint64_t *soff = nullptr;
+	uint64_t cap_suf = 0, cap_soff = 0;
+	// dbgk_fmt_records: the uploaded batch
+	uint8_t *in_text = nullptr, *in_b = nullptr, *in_q = nullptr;
+	uint64_t *in_off = nullptr;
+	dbgk_parse_rec *in_rec = nullptr;
+	uint64_t in_cap_text = 0, in_cap_b = 0, in_cap_q = 0, in_cap_recs = 0;
+	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // length + scan: [0] .. [1]; gather: [2] .. [3]
+};
+
+extern "C" int dbgk_fmt_create(int32_t format, int32_t marker, int device, dbgk_fmt **out)
+{
+	if (!out) return DBGK_ERR_ARG;
+	*out = nullptr;
+	if (device < 0 || (format != 1 && format != 2) || marker < 0 || marker > 255) return DBGK_ERR_ARG;
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
+		g_last_error = "no usable HIP device";
+		return DBGK_ERR_HIP;
+	}
+	dbgk_fmt *f = new (std::nothrow) dbgk_fmt;
+	if (!f) return DBGK_ERR_NOMEM;
+	f->device = device;
+	f->format = format;
+	f->marker = (uint32_t)marker;
+	int rc = DBGK_OK;
+	hipDeviceProp_t prop;
+	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
+		rc = DBGK_ERR_HIP;
+	}
+	if (!rc) f->n_cu = prop.multiProcessorCount;
+	if (!rc && hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
+	for (int i = 0; !rc && i < 4; ++i)
+		if (hipEventCreate(&f->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	if (!rc && hipMalloc(&f->ctr, fmtk::FC_COUNT * sizeof(unsigned long long)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (rc) {
+		dbgk_fmt_destroy(f);
+		return rc;
+	}
+	*out = f;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_fmt_destroy(dbgk_fmt *f)
+{
+	if (!f) return DBGK_ERR_ARG;
+	(void)hipSetDevice(f->device);
+	if (f->stream) (void)hipStreamSynchronize(f->stream);
+	(void)hipFree(f->out); (void)hipFree(f->len); (void)hipFree(f->coff); (void)hipFree(f->tmp); (void)hipFree(f->ctr); (void)hipFree(f->suf);
+	(void)hipFree(f->soff); (void)hipFree(f->in_text); (void)hipFree(f->in_b); (void)hipFree(f->in_q); (void)hipFree(f->in_off); (void)hipFree(f->in_rec);
+	for (hipEvent_t e : f->ev)
+		if (e) (void)hipEventDestroy(e);
+	if (f->stream) (void)hipStreamDestroy(f->stream);
+	delete f;
+	return DBGK_OK;
+}
+
+// a device buffer of at least `want` bytes (the stream is idle: nothing queued reads the old one)
+template <class T>
+static int fmt_ensure(T *&buf, uint64_t &cap, uint64_t want, uint64_t least)
+{
+	if (want <= cap && buf) return DBGK_OK;
+	(void)hipFree(buf);
+	buf = nullptr;
+	cap = 0;
+	const uint64_t bytes = std::max<uint64_t>(want, least);
+	if (hipMalloc(&buf, bytes) != hipSuccess) return DBGK_ERR_NOMEM;
+	cap = bytes;
+	return DBGK_OK;
+}
+
+// n records that lie on the device (the stream is ordered behind whatever wrote them); the suffix plane on the host, checked here
+static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk_parse_rec *recs, const uint8_t *bases, const uint8_t *quals,
+                   const uint64_t *off, uint64_t n, const char *suffix, const uint64_t *suffix_offsets, dbgk_fmt_info *out)
+{
+	f->have = false;
+	const bool fastq = f->format == 1;
+	uint64_t n_suf = 0;
+	if (suffix_offsets && n) {
+		if (suffix_offsets[0] != 0) return DBGK_ERR_ARG;
+		for (uint64_t i = 0; i < n; ++i)
+			if (suffix_offsets[i + 1] < suffix_offsets[i]) return DBGK_ERR_ARG;
+		n_suf = suffix_offsets[n];
+		if (n_suf >= (1ull << 32) || (n_suf && !suffix)) return DBGK_ERR_ARG;
+	}
+	const bool with_suf = n_suf != 0; // (a plane of empty suffixes is no plane)
+	HIPCHK(hipStreamSynchronize(f->stream));
+	uint64_t cap_len = f->cap_recs * 4, cap_coff = f->cap_recs * 8;
+	if (n + 1 > f->cap_recs || !f->len || !f->coff) {
+		const uint64_t cap = std::max<uint64_t>(n + 1, 1 << 14);
+		f->cap_recs = 0;
+		cap_len = cap_coff = 0;
+		if (fmt_ensure(f->len, cap_len, cap * 4, 0) || fmt_ensure(f->coff, cap_coff, cap * 8, 0)) return DBGK_ERR_NOMEM;
+		f->cap_recs = cap;
+	}
+	if (with_suf) {
+		if (fmt_ensure(f->suf, f->cap_suf, n_suf + 16, 1 << 16) || fmt_ensure(f->soff, f->cap_soff, (n + 1) * 8, 1 << 17)) return DBGK_ERR_NOMEM;
+		HIPCHK(hipMemcpyAsync(f->suf, suffix, n_suf, hipMemcpyHostToDevice, f->stream));
+		HIPCHK(hipMemcpyAsync(f->soff, suffix_offsets, (n + 1) * 8, hipMemcpyHostToDevice, f->stream));
+	}
+	size_t need = 0;
+	if (n && dbgk_internal_scan_lengths(nullptr, &need, f->len, f->coff, n + 1, f->stream)) return DBGK_ERR_HIP;
+	if (need > f->tmp_bytes) {
+		(void)hipFree(f->tmp);
+		f->tmp = nullptr;
+		f->tmp_bytes = 0;
+		if (hipMalloc(&f->tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
+		f->tmp_bytes = need;
+	}
+	const fmtk::FmtIn in{text, recs, bases, quals, off, with_suf ? f->suf : nullptr, with_suf ? f->soff : nullptr};
+	unsigned long long ctr[fmtk::FC_COUNT] = {0};
+	uint64_t total = 0;
+	HIPCHK(hipEventRecord(f->ev[0], f->stream));
+	if (n) {
+		HIPCHK(hipMemsetAsync(f->ctr, 0, sizeof ctr, f->stream));
+		const unsigned grid = (unsigned)std::min<uint64_t>((n + emitk::kEmitBlock) / emitk::kEmitBlock, (uint64_t)f->n_cu * 16);
+		hipLaunchKernelGGL(fmtk::k_fmt_len, dim3(grid), dim3(emitk::kEmitBlock), 0, f->stream, in, (uint32_t)n, (uint32_t)n_text, (uint32_t)fastq, f->len,
+		                   f->ctr);
+		HIPCHK(hipGetLastError());
+		size_t bytes = f->tmp_bytes;
+		if (dbgk_internal_scan_lengths(f->tmp, &bytes, f->len, f->coff, n + 1, f->stream)) return DBGK_ERR_HIP;
+	}
+	HIPCHK(hipEventRecord(f->ev[1], f->stream));
+	if (n) {
+		HIPCHK(hipMemcpyAsync(&total, f->coff + n, 8, hipMemcpyDeviceToHost, f->stream));
+		HIPCHK(hipMemcpyAsync(ctr, f->ctr, sizeof ctr, hipMemcpyDeviceToHost, f->stream));
+	}
+	HIPCHK(hipStreamSynchronize(f->stream)); // the total sizes the text; the caller's suffix plane is free from here on
+	if (ctr[fmtk::FC_BAD]) return DBGK_ERR_ARG; // a header that leaves the text, offsets that decrease, a record of 2^32 bytes
+	// whole vectors, and room behind the end for the 16-byte reads of the kernels that take the text as their input
+	if (fmt_ensure(f->out, f->cap_out, ((total + 15) & ~15ull) + 64, 1 << 20)) return DBGK_ERR_NOMEM;
+	if (total) {
+		const uint64_t tiles = (total + emitk::kEmitTile - 1) / emitk::kEmitTile;
+		const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)f->n_cu * 64);
+		HIPCHK(hipEventRecord(f->ev[2], f->stream));
+		if (fastq)
+			hipLaunchKernelGGL(fmtk::k_fmt_gather<true>, dim3(grid), dim3(emitk::kEmitBlock), 0, f->stream, in, (const uint64_t *)f->coff, (uint32_t)n, total,
+			                   f->marker, reinterpret_cast<uint4 *>(f->out));
+		else
+			hipLaunchKernelGGL(fmtk::k_fmt_gather<false>, dim3(grid), dim3(emitk::kEmitBlock), 0, f->stream, in, (const uint64_t *)f->coff, (uint32_t)n, total,
+			                   f->marker, reinterpret_cast<uint4 *>(f->out));
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(f->ev[3], f->stream));
+		HIPCHK(hipStreamSynchronize(f->stream));
+	}
+	dbgk_fmt_info I{};
+	float ms = 0;
+	HIPCHK(hipEventElapsedTime(&ms, f->ev[0], f->ev[1]));
+	I.ms_scan = ms;
+	if (total) {
+		HIPCHK(hipEventElapsedTime(&ms, f->ev[2], f->ev[3]));
+		I.ms_gather = ms;
+	}
+	I.n_records = n;
+	I.out_bytes = total;
+	I.head_bytes = ctr[fmtk::FC_HEAD], I.suffix_bytes = ctr[fmtk::FC_SUFFIX], I.seq_bytes = ctr[fmtk::FC_SEQ];
+	f->n_out = total;
+	f->have = true;
+	*out = I;
+	return DBGK_OK;
+}
+
+// the arguments both calls share
+static bool fmt_args_ok(const dbgk_fmt *f, const void *text, uint64_t n_text, const void *recs, const void *bases, const void *quals,
+                        const void *offsets, uint64_t n, const dbgk_fmt_info *out)
+{
+	if (!f || !out || n >= (1ull << 31) || n_text >= (1ull << 31) || (n_text && !text)) return false;
+	if ((f->format == 1) != (quals != nullptr)) return false; // FASTQ has a quality plane, FASTA has none
+	if (n && (!recs || !offsets || !bases)) return false;
+	return true;
+}
+
+extern "C" int dbgk_fmt_records_device(dbgk_fmt *f, const char *d_text, uint64_t n_text, const dbgk_parse_rec *d_recs, const char *d_bases,
+                                       const char *d_quals, const uint64_t *d_offsets, uint64_t n, const char *suffix,
+                                       const uint64_t *suffix_offsets, dbgk_fmt_info *out)
+{
+	if (!fmt_args_ok(f, d_text, n_text, d_recs, d_bases, d_quals, d_offsets, n, out)) return DBGK_ERR_ARG;
+	if (((uintptr_t)d_text & 15u) || ((uintptr_t)d_bases & 15u) || ((uintptr_t)d_quals & 15u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_recs & 3u))
+		return DBGK_ERR_ARG;
+	for (const char *p : {d_text, d_bases, d_quals}) { // the text the call is about to write
+		const uint8_t *u = (const uint8_t *)p;
+		if (u && f->out && u >= f->out && u < f->out + f->cap_out) return DBGK_ERR_ARG;
+	}
+	HIPCHK(hipSetDevice(f->device));
+	return fmt_run(f, (const uint8_t *)d_text, n_text, d_recs, (const uint8_t *)d_bases, (const uint8_t *)d_quals, d_offsets, n, suffix, suffix_offsets,
+	               out);
+}
+
+extern "C" int dbgk_fmt_records(dbgk_fmt *f, const char *text, uint64_t n_text, const dbgk_parse_rec *recs, const char *bases, const char *quals,
+                                const uint64_t *offsets, uint64_t n, const char *suffix, const uint64_t *suffix_offsets, dbgk_fmt_info *out)
+{
+	if (!fmt_args_ok(f, text, n_text, recs, bases, quals, offsets, n, out)) return DBGK_ERR_ARG;
+	f->have = false;
+	uint64_t nb = 0;
+	if (n) {
+		for (uint64_t i = 0; i < n; ++i) // (the planes are uploaded up to offsets[n])
+			if (offsets[i + 1] < offsets[i]) return DBGK_ERR_ARG;
+		nb = offsets[n];
+	}
+	HIPCHK(hipSetDevice(f->device));
+	HIPCHK(hipStreamSynchronize(f->stream));
+	uint64_t cap_off = f->in_cap_recs * 8, cap_rec = f->in_cap_recs * sizeof(dbgk_parse_rec);
+	if (n + 1 > f->in_cap_recs || !f->in_off || !f->in_rec) {
+		const uint64_t cap = std::max<uint64_t>(n + 1, 1 << 14);
+		f->in_cap_recs = 0;
+		cap_off = cap_rec = 0;
+		if (fmt_ensure(f->in_off, cap_off, cap * 8, 0) || fmt_ensure(f->in_rec, cap_rec, cap * sizeof(dbgk_parse_rec), 0)) return DBGK_ERR_NOMEM;
+		f->in_cap_recs = cap;
+	}
+	if (fmt_ensure(f->in_text, f->in_cap_text, n_text + 16, 1 << 20) || fmt_ensure(f->in_b, f->in_cap_b, nb + 16, 1 << 20) ||
+	    (quals && fmt_ensure(f->in_q, f->in_cap_q, nb + 16, 1 << 20)))
+		return DBGK_ERR_NOMEM;
+	if (n_text) HIPCHK(hipMemcpyAsync(f->in_text, text, n_text, hipMemcpyHostToDevice, f->stream));
+	if (nb) HIPCHK(hipMemcpyAsync(f->in_b, bases, nb, hipMemcpyHostToDevice, f->stream));
+	if (nb && quals) HIPCHK(hipMemcpyAsync(f->in_q, quals, nb, hipMemcpyHostToDevice, f->stream));
+	if (n) {
+		HIPCHK(hipMemcpyAsync(f->in_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, f->stream));
+		HIPCHK(hipMemcpyAsync(f->in_rec, recs, n * sizeof(dbgk_parse_rec), hipMemcpyHostToDevice, f->stream));
+	}
+	HIPCHK(hipStreamSynchronize(f->stream)); // the caller's buffers are free on return
+	return fmt_run(f, f->in_text, n_text, f->in_rec, f->in_b, quals ? f->in_q : nullptr, f->in_off, n, suffix, suffix_offsets, out);
+}
+
+extern "C" int dbgk_fmt_results(dbgk_fmt *f, void *out, uint64_t capacity)
+{
+	if (!f) return DBGK_ERR_ARG;
+	if (!f->have) return DBGK_ERR_STATE;
+	if (capacity < f->n_out || (f->n_out && !out)) return DBGK_ERR_ARG;
+	HIPCHK(hipSetDevice(f->device));
+	if (f->n_out) HIPCHK(hipMemcpyAsync(out, f->out, f->n_out, hipMemcpyDeviceToHost, f->stream));
+	HIPCHK(hipStreamSynchronize(f->stream));
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_fmt_device(dbgk_fmt *f, const void **d_out, uint64_t *n_out)
+{
+	if (!f || !d_out || !n_out) return DBGK_ERR_ARG;
+	if (!f->have) return DBGK_ERR_STATE;
+	*d_out = f->out;
+	*n_out = f->n_out;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_parse_recs_device(dbgk_parse *p, const dbgk_parse_rec **d_recs)
+{
+	if (!p || !d_recs) return DBGK_ERR_ARG;
+	if (!p->out.have) return DBGK_ERR_STATE;
+	*d_recs = p->rec;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_parse_text_device(dbgk_parse *p, const char **d_text, uint64_t *n_bytes)
+{
+	if (!p || !d_text || !n_bytes) return DBGK_ERR_ARG;
+	if (!p->out.have) return DBGK_ERR_STATE;
+	*d_text = (const char *)p->last_text;
+	*n_bytes = p->last_n;
+	return DBGK_OK;
+}

@@ -12,6 +12,8 @@ struct dbgk_parse {
 	EmitStage out; // split_src; its counters are parsek::Counter, its scan storage serves every scan of the stage
 	uint8_t *text = nullptr; // dbgk_parse_chunk: the uploaded chunk
 	uint64_t cap_text = 0;
+	const uint8_t *last_text = nullptr; // the text of the last chunk where it lies (dbgk_parse_text_device)
+	uint64_t last_n = 0;
 	uint32_t *tile_cnt = nullptr; // per tile of the text: newlines, and their exclusive scan
 	uint64_t *tile_off = nullptr;
 	uint64_t cap_tiles = 0;
@@ -129,6 +131,8 @@ static int parse_run(dbgk_parse *p, const uint8_t *text, uint64_t n_bytes, bool 
 {
 	EmitStage &s = p->out;
 	s.have = false;
+	p->last_text = text;
+	p->last_n = n_bytes;
 	const bool fastq = p->format == 1;
 	const uint32_t nb = (uint32_t)n_bytes;
 	dbgk_parse_info I{};

@@ -76,6 +76,19 @@ static void read_fasta(const string &file_name, vector<string> &seqs, vector<str
 	}
 }
 
+// what the program appends to a record's header (clean_adapter.cpp:189-220): the hit, if there is one, and the mark of a read that
+// is shorter than -r after the cut.  Both routes call it.
+static void adapter_suffix(const dbgk_adapter_hit &h, const vector<string> &ids, bool is_short, string &out)
+{
+	if (h.adapter >= 0) {
+		out += "   Aligned to adapter " + ids[h.adapter] + ", ";
+		out += " reads_pos: " + to_string(h.read_start) + "-" + to_string(h.read_end) + ", ";
+		out += "adapter_pos: " + to_string(h.adapter_start) + "-" + to_string(h.adapter_end) + ", ";
+		out += "  score: " + to_string(h.score);
+	}
+	if (is_short) out += "   RemoveShort";
+}
+
 static string default_adapter_file(const char *name)
 {
 	const char *dir = getenv("DBGK_ADAPTER_DIR");
@@ -137,7 +150,29 @@ int main(int argc, char *argv[])
 
 	uint64_t total_raw_reads = 0, total_raw_bases = 0, total_clean_reads = 0, total_clean_bases = 0;
 	uint64_t total_adapter_trimmed_reads = 0, total_adapter_trimmed_bases = 0, total_Nmasked_short_reads = 0, total_Nmasked_short_bases = 0;
-	{
+	if (text_on_device()) {
+		GzWriter cleanfile1(out_reads1_file);
+		DeviceTextTotals T;
+		vector<dbgk_adapter_hit> hits;
+		clean_text_on_device(in_reads1_file, cleanfile1, cleaner, Minimum_trimmed_read_len, true, T,
+		                     [&](const char *d_bases, const char *d_quals, const uint64_t *offsets, const uint64_t *lens, uint64_t n, string &suffix,
+		                         vector<uint64_t> &suffix_offsets) {
+			hits.resize(n + 1);
+			const int rc = dbgk_clean_adapter_device(cleaner, d_bases, d_quals, offsets, n, hits.data());
+			if (rc) die("dbgk_clean_adapter_device", rc);
+			for (uint64_t i = 0; i < n; i++) {
+				const dbgk_adapter_hit &h = hits[i];
+				const uint64_t kept = h.adapter >= 0 ? min<uint64_t>(lens[i], (uint64_t)(h.read_start - 1)) : lens[i];
+				adapter_suffix(h, AdapterVecId, kept < (uint64_t)Minimum_trimmed_read_len, suffix);
+				suffix_offsets.push_back(suffix.size());
+			}
+		});
+		cleanfile1.close();
+		total_raw_reads = T.raw_reads, total_raw_bases = T.raw_bases;
+		total_adapter_trimmed_reads = T.trimmed_reads, total_adapter_trimmed_bases = T.trimmed_bases;
+		total_Nmasked_short_reads = T.short_reads, total_Nmasked_short_bases = T.short_bases;
+		total_clean_reads = T.clean_reads, total_clean_bases = T.clean_bases;
+	} else {
 		LineReader infile1(in_reads1_file);
 		GzWriter cleanfile1(out_reads1_file);
 		RecordBatch batch;
@@ -157,19 +192,16 @@ int main(int argc, char *argv[])
 					const int trimmed_read_len = h.read_start - 1;
 					read = read.substr(0, trimmed_read_len);
 					batch.quals[i] = batch.quals[i].substr(0, trimmed_read_len);
-					batch.heads[i] += "   Aligned to adapter " + AdapterVecId[h.adapter] + ", ";
-					batch.heads[i] += " reads_pos: " + to_string(h.read_start) + "-" + to_string(h.read_end) + ", ";
-					batch.heads[i] += "adapter_pos: " + to_string(h.adapter_start) + "-" + to_string(h.adapter_end) + ", ";
-					batch.heads[i] += "  score: " + to_string(h.score);
 					total_adapter_trimmed_reads++;
 					total_adapter_trimmed_bases += read_len - h.read_start + 1;
 				}
-				if (read.size() < (size_t)Minimum_trimmed_read_len) {
+				const bool is_short = read.size() < (size_t)Minimum_trimmed_read_len;
+				adapter_suffix(h, AdapterVecId, is_short, batch.heads[i]);
+				if (is_short) {
 					total_Nmasked_short_reads++;
 					total_Nmasked_short_bases += read.size();
 					read = "";
 					batch.quals[i] = "";
-					batch.heads[i] += "   RemoveShort";
 				} else {
 					total_clean_reads++;
 					total_clean_bases += read.size();

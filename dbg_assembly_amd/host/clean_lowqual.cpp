@@ -31,6 +31,20 @@ static void usage()
 	exit(0);
 }
 
+// what the program appends to a record's header (clean_lowqual.cpp:79-183): seq_len is the read's length after a record whose two
+// strings differ in length was emptied, is_short says that what is left of it is shorter than -r.  Both routes call it.
+static void lowqual_suffix(const dbgk_lowqual_block &b, int seq_len, bool is_short, string &out)
+{
+	char number[64];
+	// boost::lexical_cast<std::string>(double) writes 17 significant digits
+	snprintf(number, sizeof number, "%.17g", b.error_sum / seq_len * 100);
+	out += "    RQ: ";
+	out += number;
+	out += "%";
+	if (b.trimmed) out += "  TrimLowQual";
+	if (is_short) out += "  FilterShort";
+}
+
 int main(int argc, char *argv[])
 {
 	int c;
@@ -61,14 +75,35 @@ int main(int argc, char *argv[])
 
 	uint64_t total_raw_reads = 0, total_raw_bases = 0, total_filtered_lowqual_reads = 0, total_filtered_lowqual_bases = 0;
 	uint64_t total_filtered_short_reads = 0, total_filtered_short_bases = 0, total_clean_reads = 0, total_clean_bases = 0;
-	{
+	if (text_on_device()) {
+		GzWriter cleanfile1(out_reads1_file);
+		DeviceTextTotals T;
+		vector<dbgk_lowqual_block> blocks;
+		clean_text_on_device(in_reads1_file, cleanfile1, cleaner, Min_read_len, false, T,
+		                     [&](const char *d_bases, const char *d_quals, const uint64_t *offsets, const uint64_t *lens, uint64_t n, string &suffix,
+		                         vector<uint64_t> &suffix_offsets) {
+			blocks.resize(n + 1);
+			const int rc = dbgk_clean_lowqual_device(cleaner, d_bases, d_quals, offsets, n, Error_rate_cutoff, Quality_shift, blocks.data());
+			if (rc) die("dbgk_clean_lowqual_device", rc);
+			for (uint64_t i = 0; i < n; i++) {
+				const dbgk_lowqual_block &b = blocks[i];
+				const uint64_t kept = b.trimmed ? (b.start >= 1 ? (uint64_t)b.length : 0) : lens[i];
+				lowqual_suffix(b, (int)lens[i], kept < (uint64_t)Min_read_len, suffix);
+				suffix_offsets.push_back(suffix.size());
+			}
+		});
+		cleanfile1.close();
+		total_raw_reads = T.raw_reads, total_raw_bases = T.raw_bases;
+		total_filtered_lowqual_reads = T.trimmed_reads, total_filtered_lowqual_bases = T.trimmed_bases;
+		total_filtered_short_reads = T.short_reads, total_filtered_short_bases = T.short_bases;
+		total_clean_reads = T.clean_reads, total_clean_bases = T.clean_bases;
+	} else {
 		LineReader infile1(in_reads1_file);
 		GzWriter cleanfile1(out_reads1_file);
 		RecordBatch batch;
 		vector<dbgk_lowqual_block> blocks;
 		string bases, quals;
 		vector<uint64_t> offsets;
-		char number[64];
 		for (bool more = true; more;) {
 			more = batch.fill(infile1, total_raw_reads, total_raw_bases);
 			cerr << "reading num " << batch.size() << endl;
@@ -88,11 +123,7 @@ int main(int argc, char *argv[])
 				const int seq_len = (int)read.size();
 				for (int j = 0; j < seq_len; j++)
 					if (read[j] == 'N') qual[j] = (char)Quality_shift;
-				// boost::lexical_cast<std::string>(double) writes 17 significant digits
-				snprintf(number, sizeof number, "%.17g", b.error_sum / seq_len * 100);
-				batch.heads[i] += string("    RQ: ") + number + "%";
 				if (b.trimmed) {
-					batch.heads[i] += "  TrimLowQual";
 					if (b.start >= 1) {
 						read = read.substr(b.start - 1, b.length);
 						qual = qual.substr(b.start - 1, b.length);
@@ -103,10 +134,11 @@ int main(int argc, char *argv[])
 					total_filtered_lowqual_reads++;
 					total_filtered_lowqual_bases += seq_len - b.length;
 				}
-				if (read.size() < (size_t)Min_read_len) {
+				const bool is_short = read.size() < (size_t)Min_read_len;
+				lowqual_suffix(b, seq_len, is_short, batch.heads[i]);
+				if (is_short) {
 					total_filtered_short_reads++;
 					total_filtered_short_bases += read.size();
-					batch.heads[i] += "  FilterShort";
 					read = "";
 					qual = "";
 				}

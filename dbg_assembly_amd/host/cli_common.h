@@ -264,6 +264,36 @@ struct GzWriter {
 		for (size_t at = 0; f && at < n; at += 1u << 30) gzwrite(f, p + at, (unsigned)min<size_t>(n - at, 1u << 30));
 	}
 	void write(const string &s) { write(s.data(), s.size()); }
+	// The text of a formatter's last call (FORMAT section of dbgk.h), behind everything written so far.  With DBGK_GZ=device what
+	// the writer still holds on the host is deflated first (a short member in mid-file is valid), then the text where it lies, in
+	// slices of whole pieces below 2^31 bytes; the end marker stays close()'s.  Otherwise the text comes back to the host for zlib.
+	void write_device(dbgk_fmt *text)
+	{
+		const void *d_text = nullptr;
+		uint64_t n = 0;
+		int rc = dbgk_fmt_device(text, &d_text, &n);
+		if (rc) die("dbgk_fmt_device", rc);
+		if (!n) return;
+		if (!z) {
+			vector<char> host(n);
+			rc = dbgk_fmt_results(text, host.data(), host.size());
+			if (rc) die("dbgk_fmt_results", rc);
+			write(host.data(), host.size());
+			return;
+		}
+		if (!pending.empty()) deflate_pending(false);
+		const uint64_t slice = (uint64_t)32768 * DBGK_GZ_PIECE; // 16-byte aligned offsets: a piece is 16 * 4080 bytes
+		static_assert((uint64_t)32768 * DBGK_GZ_PIECE < (1ull << 31) && DBGK_GZ_PIECE % 16 == 0, "a slice is one call on aligned text");
+		for (uint64_t at = 0; at < n; at += slice) {
+			dbgk_gz_info info;
+			rc = dbgk_gz_deflate_device(z, (const char *)d_text + at, min<uint64_t>(slice, n - at), 0, &info);
+			if (rc) die("dbgk_gz_deflate_device", rc);
+			members.resize(info.out_bytes);
+			rc = dbgk_gz_results(z, members.data(), members.size());
+			if (rc) die("dbgk_gz_results", rc);
+			if (!members.empty() && fwrite(members.data(), 1, members.size(), raw) != members.size()) write_failed();
+		}
+	}
 };
 
 // the strings of v back to back, string i at bases[offsets[i] .. offsets[i + 1])

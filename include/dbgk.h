@@ -1086,6 +1086,64 @@ int dbgk_inf_device(dbgk_inf_t z, const void **d_text, uint64_t *n_bytes);
 int dbgk_inf_member_status(dbgk_inf_t z, uint8_t *reason, uint64_t capacity);
 int dbgk_inf_timing_get(dbgk_inf_t z, dbgk_inf_timing *t);
 
+/* ---- FORMAT: from the device batch to the bytes of a FASTQ / FASTA output file (additions to ABI 7) ------------------------------------
+ * The stage behind the last stage, PARSE read backwards.  Inputs, all of one batch of n records:
+ *   - the source text of n_text bytes, the chunk the parser parsed, and record i's dbgk_parse_rec, of which only head_pos and head_len
+ *     are used: the header line lies in the text as it stands;
+ *   - a compact batch in the layout of dbgk_clean_compact / dbgk_corr_compact / dbgk_parse_device / dbgk_pair_device: a bases plane, a
+ *     quality plane (format 1 only), n + 1 64-bit offsets;
+ *   - an optional suffix plane ON THE HOST, uploaded by the call: bytes and n + 1 offsets that start at 0 and do not decrease, below
+ *     2^32, or null for all empty.  It is what a program appends to the header, composed by the caller.
+ * Output, record after record in input order, with H the header's bytes (a '\r' included), S the suffix, B / Q the record's bytes
+ * of the two planes and L their length:
+ *   format 1 (FASTQ)  H S "\n" B "\n+\n" Q "\n"        head_len + suf_len + 2 L + 5 bytes
+ *   format 2 (FASTA)  H S "\n" B "\n"                  head_len + suf_len + L + 2 bytes
+ * If marker != 0 and head_len > 0 the first byte of H is replaced by marker (correct_error_reads turns '@' into '>').  An emptied
+ * record (L == 0) is written with its empty lines; no record is dropped.  The text starts on a 16-byte boundary, is written in whole
+ * 16-byte vectors with the pad of the last one 0, and 64 readable bytes follow it, so dbgk_gz_deflate_device and
+ * dbgk_parse_chunk_device read it where it lies.  n < 2^31, n_text < 2^31, every record below 2^32 bytes of output; plane offsets and
+ * out_bytes are 64-bit.                                                                                                      */
+typedef struct dbgk_fmt dbgk_fmt;
+#define DBGK_FMT_TILE 4096          /* bytes of output per workgroup round of the gather                                  */
+typedef struct dbgk_fmt_info {
+	uint64_t n_records;         /* n                                                                                    */
+	uint64_t out_bytes;         /* bytes of the text (without the pad)                                                  */
+	uint64_t head_bytes;        /* ... of which header, suffix and sequence bytes (FASTQ: the quality bytes are as many  */
+	uint64_t suffix_bytes;      /* again); the rest are the separators                                                  */
+	uint64_t seq_bytes;
+	double ms_scan;             /* device time: lengths + scan; the gather                                              */
+	double ms_gather;
+} dbgk_fmt_info;
+/* format 1 FASTQ, 2 FASTA; marker 0..255.  Anything else: DBGK_ERR_ARG.  DBGK_ERR_HIP without a usable gfx950 device: there is no
+ * host fall-back                                                                                                          */
+int dbgk_fmt_create(int32_t format, int32_t marker, int device, dbgk_fmt **out);
+int dbgk_fmt_destroy(dbgk_fmt *f);
+/* text, records, planes and offsets in device memory of f's GPU, read in place and never written; the suffix plane on the host.
+ * d_text, d_bases and d_quals 16-byte aligned; d_text readable up to n_text rounded up to 16.  No source byte is read outside the
+ * aligned dwords that hold a byte of a header or of a record's bytes: never at or behind n_text rounded up to 16, never behind
+ * d_offsets[n] rounded up to 4; d_offsets[0] need not be 0.  DBGK_ERR_ARG with no output for: format 1 without a quality plane,
+ * format 2 with one, a misaligned pointer, the stage's own output as an input, suffix offsets that do not start at 0 or decrease
+ * -- and, found on the device, a header that leaves the text (head_pos + head_len > n_text), plane offsets that decrease, a record
+ * of 2^32 bytes and more.  n == 0 is valid.  Work of the caller's own on the inputs has to be synchronised.  Returns when the text
+ * is complete.                                                                                                            */
+int dbgk_fmt_records_device(dbgk_fmt *f, const char *d_text, uint64_t n_text, const dbgk_parse_rec *d_recs, const char *d_bases,
+                            const char *d_quals, const uint64_t *d_offsets, uint64_t n, const char *suffix, const uint64_t *suffix_offsets,
+                            dbgk_fmt_info *out);
+/* the same with everything on the host, uploaded by the call: offsets[n] bytes of each plane                               */
+int dbgk_fmt_records(dbgk_fmt *f, const char *text, uint64_t n_text, const dbgk_parse_rec *recs, const char *bases, const char *quals,
+                     const uint64_t *offsets, uint64_t n, const char *suffix, const uint64_t *suffix_offsets, dbgk_fmt_info *out);
+/* host copy of the text of the last call: out_bytes bytes; a capacity below that: DBGK_ERR_ARG.  Before a successful call:
+ * DBGK_ERR_STATE (also for dbgk_fmt_device).                                                                               */
+int dbgk_fmt_results(dbgk_fmt *f, void *out, uint64_t capacity);
+/* the text where it lies; valid until the next call or dbgk_fmt_destroy                                                    */
+int dbgk_fmt_device(dbgk_fmt *f, const void **d_out, uint64_t *n_out);
+/* the records of the parser's last chunk where they lie (n_records of them; the array dbgk_parse_results copies): what
+ * dbgk_fmt_records_device takes beside the text that chunk was.  Before a successful chunk: DBGK_ERR_STATE.                  */
+int dbgk_parse_recs_device(dbgk_parse *p, const dbgk_parse_rec **d_recs);
+/* ... and the text of that chunk where it lies: the copy dbgk_parse_chunk uploaded (16-byte aligned, readable up to n_bytes
+ * rounded up to 16, valid until the next chunk), or the caller's own buffer of dbgk_parse_chunk_device                     */
+int dbgk_parse_text_device(dbgk_parse *p, const char **d_text, uint64_t *n_bytes);
+
 /* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
  * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
  * links between contigs and walks the unambiguous ones into scaffolds.  Contig c (0-based, in the order of the contig file) is node
