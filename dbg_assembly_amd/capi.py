@@ -1240,21 +1240,14 @@ def plan_partition(table_slots, expected_kmers, shard_count=0, shard_index=0):
     return info
 
 
-class Corrector:
-    """correct_error_reads on the GPU (CORRECT section of include/dbgk.h).  Defaults are the reference's: -m and -x are
-    17 whatever k is.  Build the table with load_file (a 1-bit .cz file: raw blocks, then the loader's mirror) or
-    from_kfreq (a finalized KFREQ Graph + cutoff), then correct(bases, offsets)."""
-
-    BLOCK_BYTES = 1 << 20  # one compressed block of the .cz file: 8 Mi k-mers
-
-    def __init__(self, k=17, m=17, c=2, x=17, n=5000000, r=75, device=0):
-        self.k = k
-        self._h = C.c_void_p()
-        _chk(lib().dbgk_corr_create(C.byref(CorrParams(k, m, c, x, n, r)), device, C.byref(self._h)), "dbgk_corr_create")
+class _Handle:
+    """What the stage classes share: the handle `_h` of the C library, destroyed once by the C function `_destroy` names, and the
+    context manager that closes it."""
+    _destroy = None
 
     def close(self):
         if self._h:
-            lib().dbgk_corr_destroy(self._h)
+            getattr(lib(), self._destroy)(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -1262,6 +1255,19 @@ class Corrector:
 
     def __exit__(self, *a):
         self.close()
+
+
+class Corrector(_Handle):
+    """correct_error_reads on the GPU (CORRECT section of include/dbgk.h).  Defaults are the reference's: -m and -x are
+    17 whatever k is.  Build the table with load_file (a 1-bit .cz file: raw blocks, then the loader's mirror) or
+    from_kfreq (a finalized KFREQ Graph + cutoff), then correct(bases, offsets)."""
+    _destroy = "dbgk_corr_destroy"
+    BLOCK_BYTES = 1 << 20  # one compressed block of the .cz file: 8 Mi k-mers
+
+    def __init__(self, k=17, m=17, c=2, x=17, n=5000000, r=75, device=0):
+        self.k = k
+        self._h = C.c_void_p()
+        _chk(lib().dbgk_corr_create(C.byref(CorrParams(k, m, c, x, n, r)), device, C.byref(self._h)), "dbgk_corr_create")
 
     def load_bits(self, first_byte, raw):
         raw = np.ascontiguousarray(np.frombuffer(bytes(raw), dtype=np.uint8) if not isinstance(raw, np.ndarray) else raw, dtype=np.uint8)
@@ -1391,26 +1397,16 @@ def concat_sequences(seqs):
     return np.frombuffer(b"".join(seqs), dtype=np.uint8), offsets
 
 
-class Mapper:
+class Mapper(_Handle):
     """map_reads / map_pair on the GPU (MAP section of include/dbgk.h).  Defaults are the reference's.  set_contigs builds the
     seed index and keeps the contig text on the device; map(bases, offsets) returns two hits per read (the second one only
     with second_alignment, the map_reads mode)."""
+    _destroy = "dbgk_map_destroy"
 
     def __init__(self, k=31, s=5, r=250, identity=0.97, second_alignment=False, device=0):
         self._h = C.c_void_p()
         _chk(lib().dbgk_map_create(C.byref(MapParams(k, s, r, 1 if second_alignment else 0, identity)), device, C.byref(self._h)),
              "dbgk_map_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_map_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def set_contigs(self, contigs):
         """a list of sequences (bytes / str); empty ones keep their index"""
@@ -1447,25 +1443,15 @@ class Mapper:
         return {f: getattr(s, f) for f, _ in MapStats._fields_}
 
 
-class Pairer:
+class Pairer(_Handle):
     """The pair split on the GPU (PAIR section of include/dbgk.h): two batches of n reads, mate 1 and mate 2 of pair i at index i,
     become the PAIRED batch (both mates of every pair with two reads left) and the SINGLE batch (the mate that is left of every
     other pair).  split / split_device return the counters; results(which) and device(which) give either output."""
+    _destroy = "dbgk_pair_destroy"
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         _chk(lib().dbgk_pair_create(device, C.byref(self._h)), "dbgk_pair_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_pair_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     @staticmethod
     def _info(info):
@@ -1520,25 +1506,15 @@ class Pairer:
         return bases[:nb], (quals[:nb] if q else None), offsets, ids[:n]
 
 
-class Parser:
+class Parser(_Handle):
     """FASTQ (fmt 1) / FASTA (fmt 2) text parsed on the GPU (PARSE section of include/dbgk.h): a chunk of the file's bytes becomes the
     compact batch -- bases, qualities with with_quals, n + 1 offsets -- that the other stages read in place.  chunk / chunk_device
     return the counters and `consumed`; results() and device() give the batch; stream() feeds a file chunk by chunk."""
+    _destroy = "dbgk_parse_destroy"
 
     def __init__(self, fmt, with_quals=False, device=0):
         self._h = C.c_void_p()
         _chk(lib().dbgk_parse_create(fmt, 1 if with_quals else 0, device, C.byref(self._h)), "dbgk_parse_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_parse_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     @staticmethod
     def _info(info):
@@ -1590,11 +1566,12 @@ class Parser:
         return bases[:nb], (quals[:nb] if q else None), offsets, recs[:n]
 
 
-class Formatter:
+class Formatter(_Handle):
     """A compact batch written as FASTQ (fmt 1) / FASTA (fmt 2) text on the GPU (FORMAT section of include/dbgk.h): the headers from the
     text the parser parsed, the reads from the planes of a compact batch, an optional suffix per header from the host.  marker: 0,
     or the byte that replaces the first byte of every header.  format / format_device return the info as a dict (also kept in
     `info`); results() and device() give the text."""
+    _destroy = "dbgk_fmt_destroy"
 
     def __init__(self, fmt, marker=0, device=0):
         self._h = C.c_void_p()
@@ -1602,17 +1579,6 @@ class Formatter:
         if isinstance(marker, (bytes, str)):
             marker = ord(marker)
         _chk(lib().dbgk_fmt_create(fmt, marker, device, C.byref(self._h)), "dbgk_fmt_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_fmt_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     @staticmethod
     def _suffix_plane(suffixes, n):
@@ -1689,26 +1655,16 @@ class Formatter:
         return out[:n].tobytes()
 
 
-class Deflater:
+class Deflater(_Handle):
     """bytes deflated on the GPU into BGZF-framed gzip members (GZ section of include/dbgk.h): level 0 stored, 1 one dynamic-Huffman
     block of literals per member, 2 one over LZ77 tokens.  deflate / deflate_device return the members of the call as bytes; `info` holds the counters of
     the last call; stream() compresses a file window by window."""
+    _destroy = "dbgk_gz_destroy"
 
     def __init__(self, level=GZ_MAX_LEVEL):
         self._h = C.c_void_p()
         self.info = None
         _chk(lib().dbgk_gz_create(level, C.byref(self._h)), "dbgk_gz_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_gz_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def _done(self, info):
         self.info = {f: getattr(info, f) for f, _ in GzInfo._fields_}
@@ -1762,26 +1718,16 @@ class Deflater:
             block = ahead
 
 
-class Inflater:
+class Inflater(_Handle):
     """BGZF-framed gzip members inflated on the GPU (INFLATE section of include/dbgk.h).  inflate / inflate_device return the bytes
     of the members of the call and its counters; a member that is refused leaves zeros, `info["n_bad"]` counts them and member_status()
     says why; device() is the text where it lies, for Parser.chunk_device; stream() inflates a file window by window."""
+    _destroy = "dbgk_inf_destroy"
 
     def __init__(self, max_out_bytes=0):
         self._h = C.c_void_p()
         self.info = None
         _chk(lib().dbgk_inf_create(max_out_bytes, C.byref(self._h)), "dbgk_inf_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_inf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def _done(self, info):
         self.info = {f: getattr(info, f) for f, _ in InfInfo._fields_}
@@ -1864,24 +1810,14 @@ class Inflater:
             carry, block = data[info["consumed"]:], ahead
 
 
-class Cleaner:
+class Cleaner(_Handle):
     """clean_adapter / clean_lowqual on the GPU (CLEAN section of include/dbgk.h).  The device returns one hit / one block per
     read; trim_adapter and trim_lowqual cut the records the way the two programs do."""
+    _destroy = "dbgk_clean_destroy"
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
         _chk(lib().dbgk_clean_create(device, C.byref(self._h)), "dbgk_clean_create")
-
-    def close(self):
-        if self._h:
-            lib().dbgk_clean_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def set_adapters(self, adapters, score_cutoff=12):
         """contaminant sequences (bytes / str) in the order they are tried"""
@@ -2016,11 +1952,12 @@ class Cleaner:
         return out, blocks
 
 
-class _LinkTable:
+class _LinkTable(_Handle):
     """What Scaffolder, GapFiller and SuperLinker share: the handle, the contigs, the link table and the emit of the C calls that start with
     `_prefix` ("dbgk_link" / "dbgk_fill"); `_item_dtype` is the dtype of the items emit() takes."""
     _prefix = None
     _item_dtype = None
+    _destroy = property(lambda self: self._prefix + "_destroy")
 
     def _call(self, name, *args, ok=(0,)):
         """lib().<_prefix>_<name>(handle, *args) -> its return code, checked under the C function's name unless it is in `ok`"""
@@ -2029,17 +1966,6 @@ class _LinkTable:
         if rc not in ok:
             _chk(rc, what)
         return rc
-
-    def close(self):
-        if self._h:
-            getattr(lib(), self._prefix + "_destroy")(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def set_contigs(self, lengths):
         lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
@@ -2364,12 +2290,13 @@ class SuperLinker(_LinkTable):
         return {f: getattr(s, f) for f, _ in SuperTiming._fields_}
 
 
-class ContigBuilder:
+class ContigBuilder(_Handle):
     """The contig read-out on the GPU (CONTIG section of include/dbgk.h).  set_table(array, nul_flag, del_flag, klink) takes the
     host-layout table after simplification: NODE_DTYPE array[size], the two flag arrays of size // 8 + 1 bytes (bit 128 >> (i % 8)
     of byte i // 8), the 2-byte link records (bit 8 = linear).  read_out() -> bases, depths, offsets, records, summary: contigs in
     the order the reference's scan finds them.  wide=True: k up to 63 on a table of NODE32_DTYPE nodes (128-bit keys; parity
     unpinned above k = 32), everything else the same."""
+    _destroy = "dbgk_contig_destroy"
 
     def __init__(self, k, kmer_freq_cutoff=2, contig_len_cutoff=125, device=0, wide=False):
         self.wide = bool(wide)
@@ -2377,17 +2304,6 @@ class ContigBuilder:
         self._keep = None
         create = "dbgk_wide_contig_create" if self.wide else "dbgk_contig_create"
         _chk(getattr(lib(), create)(C.byref(ContigParams(k, kmer_freq_cutoff, contig_len_cutoff, 0)), device, C.byref(self._h)), create)
-
-    def close(self):
-        if self._h:
-            lib().dbgk_contig_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def set_table(self, array, nul_flag, del_flag, klink):
         array = np.ascontiguousarray(array, dtype=NODE32_DTYPE if self.wide else NODE_DTYPE)

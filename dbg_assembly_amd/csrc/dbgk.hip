@@ -473,6 +473,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_misc.h"
 #include "dbgk_comm.h"
 #include "dbgk_host_wide_links.h"
+#include "dbgk_host_stage.h"
 #include "dbgk_host_emit.h"
 #include "dbgk_host_correct.h"
 #include "dbgk_host_spectrum.h"

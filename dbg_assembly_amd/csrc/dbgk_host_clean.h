@@ -1,26 +1,23 @@
 // CLEAN: host side of clean_adapter / clean_lowqual on the GPU (include/dbgk.h, CLEAN section; kernels in dbgk_clean.h)
 
-struct dbgk_clean {
-	int device = 0;
-	int n_cu = 256;
-	hipStream_t stream = nullptr;
+struct dbgk_clean : StageDev {
 	// the adapter set: codes back to back (padded to whole dwords), offsets[n + 1]
-	uint8_t *d_ad = nullptr;
-	uint32_t *d_ad_off = nullptr;
+	DevBuf<uint8_t> d_ad;
+	DevBuf<uint32_t> d_ad_off;
 	uint64_t n_adapters = 0, adapter_bytes = 0;
 	int32_t score_cutoff = 0;
 	bool adapters_set = false;
 	// Qual2Err of clean_lowqual.cpp:220-222 for the shift it was last built for
-	double *d_table = nullptr;
+	DevBuf<double> d_table;
 	int32_t table_shift = -1;
 	// batch buffers, grown on demand
-	uint8_t *d_seq = nullptr, *d_qual = nullptr;
-	uint64_t *d_off = nullptr;
-	void *d_out = nullptr; // cleank::AdapterHit or cleank::LowqualBlock per read (both 24 bytes)
-	uint32_t *d_long = nullptr;
-	cleank::CleanCounters *d_ctr = nullptr;
+	DevBuf<uint8_t> d_seq, d_qual;
+	DevBuf<uint64_t> d_off;
+	DevBuf<uint8_t> d_out; // cleank::AdapterHit or cleank::LowqualBlock per read (both 24 bytes)
+	DevBuf<uint32_t> d_long;
+	DevBuf<cleank::CleanCounters> d_ctr;
 	uint64_t cap_bytes = 0, cap_qual = 0, cap_reads = 0;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	StageEvents<4> ev;
 	dbgk_clean_stats last{};
 	// output stage (dbgk_host_emit.h): the batch whose offsets and records d_off / d_out hold, and its compact form
 	bool have_batch = false;      // the last batch call succeeded: batch_n reads of b_seq / b_qual are resident
@@ -35,40 +32,17 @@ static_assert(sizeof(dbgk_adapter_hit) == 24 && sizeof(cleank::AdapterHit) == 24
 static_assert(sizeof(dbgk_lowqual_block) == 24 && sizeof(cleank::LowqualBlock) == 24, "dbgk_lowqual_block layout");
 static_assert(offsetof(dbgk_lowqual_block, start) == 8 && offsetof(dbgk_lowqual_block, trimmed) == 16, "dbgk_lowqual_block layout");
 
-static void clean_free_batch(dbgk_clean *c)
-{
-	(void)hipFree(c->d_seq); (void)hipFree(c->d_qual); (void)hipFree(c->d_off); (void)hipFree(c->d_out); (void)hipFree(c->d_long);
-	c->d_seq = c->d_qual = nullptr; c->d_off = nullptr; c->d_out = nullptr; c->d_long = nullptr;
-	c->cap_bytes = c->cap_qual = c->cap_reads = 0;
-}
-
 extern "C" int dbgk_clean_create(int device, dbgk_clean **out)
 {
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
 	if (device < 0) return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_clean *c = new (std::nothrow) dbgk_clean;
 	if (!c) return DBGK_ERR_NOMEM;
-	c->device = device;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) c->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 4; ++i)
-		if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	int rc = stage_open(*c, device);
+	if (!rc) rc = c->ev.create();
 	if (!rc) rc = emit_create(c->emit, emitk::CleanRule<DBGK_CLEAN_KIND_LOWQUAL>::kCounters, false); // (both kinds count the same seven)
-	if (!rc && (hipMalloc(&c->d_ctr, sizeof(cleank::CleanCounters)) != hipSuccess || hipMalloc(&c->d_table, 256 * sizeof(double)) != hipSuccess))
-		rc = DBGK_ERR_NOMEM;
+	if (!rc && (c->d_ctr.reserve(sizeof(cleank::CleanCounters)) || c->d_table.reserve(256 * sizeof(double)))) rc = DBGK_ERR_NOMEM;
 	if (rc) {
 		dbgk_clean_destroy(c);
 		return rc;
@@ -80,14 +54,8 @@ extern "C" int dbgk_clean_create(int device, dbgk_clean **out)
 extern "C" int dbgk_clean_destroy(dbgk_clean *c)
 {
 	if (!c) return DBGK_ERR_ARG;
-	(void)hipSetDevice(c->device);
-	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	stage_drain(c->device, c->stream);
 	emit_destroy(c->emit);
-	clean_free_batch(c);
-	(void)hipFree(c->d_ad); (void)hipFree(c->d_ad_off); (void)hipFree(c->d_table); (void)hipFree(c->d_ctr);
-	for (hipEvent_t e : c->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return DBGK_OK;
 }
@@ -108,10 +76,9 @@ extern "C" int dbgk_clean_set_adapters(dbgk_clean *c, const char *bases, const u
 	std::vector<uint32_t> off32(n + 1);
 	for (uint64_t i = 0; i <= n; ++i) off32[i] = (uint32_t)offsets[i];
 	HIPCHK(hipSetDevice(c->device));
-	(void)hipFree(c->d_ad); (void)hipFree(c->d_ad_off);
-	c->d_ad = nullptr; c->d_ad_off = nullptr;
 	c->adapters_set = false;
-	if (hipMalloc(&c->d_ad, codes.size()) != hipSuccess || hipMalloc(&c->d_ad_off, off32.size() * 4) != hipSuccess) return DBGK_ERR_NOMEM;
+	c->d_ad.release(); c->d_ad_off.release();
+	if (c->d_ad.reserve(codes.size()) || c->d_ad_off.reserve(off32.size() * 4)) return DBGK_ERR_NOMEM;
 	HIPCHK(hipMemcpyAsync(c->d_ad, codes.data(), codes.size(), hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(c->d_ad_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -130,13 +97,10 @@ static int clean_ensure_batch(dbgk_clean *c, uint64_t n_bytes, uint64_t n_reads,
 		const uint64_t bytes = std::max<uint64_t>(std::max<uint64_t>(n_bytes + 16, c->cap_bytes), 1 << 20);
 		const uint64_t reads = std::max<uint64_t>(std::max<uint64_t>(n_reads, c->cap_reads), 1 << 14);
 		const bool qual = with_qual || c->cap_qual;
-		clean_free_batch(c);
-		if (hipMalloc(&c->d_seq, bytes) != hipSuccess || (qual && hipMalloc(&c->d_qual, bytes) != hipSuccess) ||
-		    hipMalloc(&c->d_off, (reads + 1) * 8) != hipSuccess || hipMalloc(&c->d_out, reads * 24) != hipSuccess ||
-		    hipMalloc(&c->d_long, reads * 4) != hipSuccess) {
-			clean_free_batch(c);
+		c->cap_bytes = c->cap_qual = c->cap_reads = 0;
+		if (c->d_seq.reserve(bytes) || (qual && c->d_qual.reserve(bytes)) || c->d_off.reserve((reads + 1) * 8) || c->d_out.reserve(reads * 24) ||
+		    c->d_long.reserve(reads * 4))
 			return DBGK_ERR_NOMEM;
-		}
 		c->cap_bytes = bytes;
 		c->cap_qual = qual ? bytes : 0;
 		c->cap_reads = reads;
@@ -149,7 +113,7 @@ static bool clean_device_plane_ok(const dbgk_clean *c, const char *p)
 {
 	if ((uintptr_t)p & 15u) return false;
 	const uint8_t *u = (const uint8_t *)p;
-	for (const uint8_t *own : {c->emit.bases, c->emit.quals})
+	for (const uint8_t *own : {c->emit.bases.p, c->emit.quals.p})
 		if (u && own && u >= own && u < own + c->emit.cap_bytes) return false;
 	return true;
 }
@@ -188,10 +152,10 @@ static int clean_adapter_run(dbgk_clean *c, const char *bases, bool on_device, c
 	rc = clean_ensure_batch(c, on_device ? 0 : nb, n_reads, false);
 	if (rc) return rc;
 	if (nb && !on_device) HIPCHK(hipMemcpyAsync(c->d_seq, bases, nb, hipMemcpyHostToDevice, c->stream));
-	const uint8_t *d_in = on_device ? (const uint8_t *)bases : c->d_seq;
+	const uint8_t *d_in = on_device ? (const uint8_t *)bases : c->d_seq.p;
 	HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemsetAsync(c->d_ctr, 0, sizeof(cleank::CleanCounters), c->stream));
-	cleank::AdapterHit *d_hits = static_cast<cleank::AdapterHit *>(c->d_out);
+	cleank::AdapterHit *d_hits = reinterpret_cast<cleank::AdapterHit *>(c->d_out.p);
 	const uint32_t nr = (uint32_t)n_reads, n_ad = (uint32_t)c->n_adapters;
 	const bool lds_form = c->adapter_bytes <= cleank::kCleanAdapterBytes;
 	auto grid_for = [&](uint64_t items) {
@@ -281,9 +245,9 @@ static int clean_lowqual_run(dbgk_clean *c, const char *bases, const char *quals
 		HIPCHK(hipMemcpyAsync(c->d_seq, bases, nb, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipMemcpyAsync(c->d_qual, quals, nb, hipMemcpyHostToDevice, c->stream));
 	}
-	const uint8_t *d_in = on_device ? (const uint8_t *)bases : c->d_seq, *d_in_q = on_device ? (const uint8_t *)quals : c->d_qual;
+	const uint8_t *d_in = on_device ? (const uint8_t *)bases : c->d_seq.p, *d_in_q = on_device ? (const uint8_t *)quals : c->d_qual.p;
 	HIPCHK(hipMemcpyAsync(c->d_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-	cleank::LowqualBlock *d_blocks = static_cast<cleank::LowqualBlock *>(c->d_out);
+	cleank::LowqualBlock *d_blocks = reinterpret_cast<cleank::LowqualBlock *>(c->d_out.p);
 	const unsigned grid = (unsigned)((n_reads + cleank::kLowqualThreads - 1) / cleank::kLowqualThreads);
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
 	hipLaunchKernelGGL(cleank::k_clean_lowqual, dim3(grid), dim3(cleank::kLowqualThreads), 0, c->stream, d_in, d_in_q, c->d_off,
@@ -386,8 +350,8 @@ extern "C" int dbgk_clean_compact_from(dbgk_clean *c, int32_t kind, const char *
 		HIPCHK(hipMemcpyAsync(c->d_out, recs, n_reads * 24, hipMemcpyHostToDevice, c->stream));
 		HIPCHK(hipStreamSynchronize(c->stream)); // the caller's buffers are free on return
 	}
-	clean_batch_is(c, kind, kind == DBGK_CLEAN_KIND_LOWQUAL ? quality_shift : 0, n_reads, n_reads ? c->d_seq : nullptr,
-	               n_reads && quals ? c->d_qual : nullptr);
+	clean_batch_is(c, kind, kind == DBGK_CLEAN_KIND_LOWQUAL ? quality_shift : 0, n_reads, n_reads ? c->d_seq.p : nullptr,
+	               n_reads && quals ? c->d_qual.p : nullptr);
 	return clean_compact_run(c, (uint32_t)min_len, out);
 }
 

@@ -8,26 +8,23 @@
 // merge -- is the same code.  The host walker works on 128-bit keys for both kinds; a 16-byte node's key has the high word 0, where
 // every rule of include/dbgk_wide.h is the reference's.
 
-struct dbgk_contig {
-	int device = 0;
-	int n_cu = 256;
-	hipStream_t stream = nullptr;
-	hipEvent_t ev[2] = {nullptr, nullptr};
+struct dbgk_contig : StageDev {
+	StageEvents<2> ev;
 	dbgk_contig_params p{};
 	// the table: borrowed host arrays and their device copies
 	uint64_t size = 0;
 	bool wide = false;                       // 32-byte nodes: h_array32 / d_array32 instead of h_array / d_array
 	const dbgk_node *h_array = nullptr;
 	const dbgk_node32 *h_array32 = nullptr;
-	dbgk_node32 *d_array32 = nullptr;
+	DevBuf<dbgk_node32> d_array32;
 	const uint8_t *h_nul = nullptr, *h_del = nullptr;
 	const uint16_t *h_klink = nullptr;
-	Node *d_array = nullptr;
-	uint8_t *d_nul = nullptr, *d_del = nullptr;
-	uint16_t *d_klink = nullptr;
+	DevBuf<Node> d_array;
+	DevBuf<uint8_t> d_nul, d_del;
+	DevBuf<uint16_t> d_klink;
 	bool table_set = false, done = false;
 	// the kernels' contigs, back to back on the device
-	uint8_t *d_bases = nullptr, *d_depths = nullptr;
+	DevBuf<uint8_t> d_bases, d_depths;
 	// all contigs in scan order
 	std::vector<uint64_t> offsets;
 	std::vector<dbgk_contig_record> records;
@@ -60,27 +57,12 @@ static int contig_create(const dbgk_contig_params *p, int device, int k_max, dbg
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
 	if (!p || device < 0 || p->k < 1 || p->k > k_max || p->kmer_freq_cutoff < 0 || p->reserved) return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_contig *c = new (std::nothrow) dbgk_contig;
 	if (!c) return DBGK_ERR_NOMEM;
-	c->device = device;
 	c->p = *p;
 	c->wide = k_max > 31;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) c->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 2; ++i)
-		if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	int rc = stage_open(*c, device);
+	if (!rc) rc = c->ev.create();
 	if (rc) {
 		dbgk_contig_destroy(c);
 		return rc;
@@ -95,24 +77,15 @@ extern "C" int dbgk_wide_contig_create(const dbgk_contig_params *p, int device, 
 
 static void contig_free_table(dbgk_contig *c)
 {
-	(void)hipFree(c->d_array); (void)hipFree(c->d_array32); (void)hipFree(c->d_nul); (void)hipFree(c->d_del); (void)hipFree(c->d_klink);
-	(void)hipFree(c->d_bases); (void)hipFree(c->d_depths);
-	c->d_array = nullptr;
-	c->d_array32 = nullptr;
-	c->d_nul = c->d_del = c->d_bases = c->d_depths = nullptr;
-	c->d_klink = nullptr;
+	c->d_array.release(); c->d_array32.release(); c->d_nul.release(); c->d_del.release(); c->d_klink.release();
+	c->d_bases.release(); c->d_depths.release();
 	c->table_set = c->done = false;
 }
 
 extern "C" int dbgk_contig_destroy(dbgk_contig *c)
 {
 	if (!c) return DBGK_ERR_ARG;
-	(void)hipSetDevice(c->device);
-	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	contig_free_table(c);
-	for (auto &e : c->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
+	stage_drain(c->device, c->stream);
 	delete c;
 	return DBGK_OK;
 }
@@ -130,14 +103,12 @@ static int contig_set_table(dbgk_contig *c, uint64_t size, const void *array, si
 	HIPCHK(hipSetDevice(c->device));
 	contig_free_table(c);
 	const uint64_t flag_bytes = size / 8 + 1;
-	void *d_nodes = nullptr;
-	if (hipMalloc(&d_nodes, size * node_bytes) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (c->wide) c->d_array32 = static_cast<dbgk_node32 *>(d_nodes);
-	else c->d_array = static_cast<Node *>(d_nodes);
-	if (hipMalloc(&c->d_nul, flag_bytes) != hipSuccess || hipMalloc(&c->d_del, flag_bytes) != hipSuccess || hipMalloc(&c->d_klink, size * 2) != hipSuccess) {
+	if ((c->wide ? c->d_array32.reserve(size * node_bytes) : c->d_array.reserve(size * node_bytes)) || c->d_nul.reserve(flag_bytes) ||
+	    c->d_del.reserve(flag_bytes) || c->d_klink.reserve(size * 2)) {
 		contig_free_table(c);
 		return DBGK_ERR_NOMEM;
 	}
+	void *d_nodes = c->wide ? (void *)c->d_array32.p : (void *)c->d_array.p;
 	const auto t0 = std::chrono::steady_clock::now();
 	HIPCHK(hipMemcpyAsync(d_nodes, array, size * node_bytes, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(c->d_nul, nul_flag, flag_bytes, hipMemcpyHostToDevice, c->stream));
@@ -308,8 +279,7 @@ extern "C" int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out)
 	if (!c) return DBGK_ERR_ARG;
 	if (!c->table_set) return DBGK_ERR_STATE;
 	HIPCHK(hipSetDevice(c->device));
-	(void)hipFree(c->d_bases); (void)hipFree(c->d_depths);
-	c->d_bases = c->d_depths = nullptr;
+	c->d_bases.release(); c->d_depths.release();
 	c->done = false;
 	c->offsets.assign(1, 0);
 	c->records.clear();
@@ -448,7 +418,7 @@ extern "C" int dbgk_contig_read_out(dbgk_contig *c, dbgk_contig_summary *out)
 		Record *d_rec = nullptr;
 		uint16_t *d_stage = nullptr;
 		if (!mem.get(d_off, n_kernel + 1) || !mem.get(d_rec, n_kernel) || !mem.get(d_stage, total)) return DBGK_ERR_NOMEM;
-		if (hipMalloc(&c->d_bases, total + 8) != hipSuccess || hipMalloc(&c->d_depths, total + 8) != hipSuccess) return DBGK_ERR_NOMEM;
+		if (c->d_bases.reserve(total + 8) || c->d_depths.reserve(total + 8)) return DBGK_ERR_NOMEM;
 		CTG_STEP(hipMemcpy(d_tc, tc.data(), n_tiles2 * 4, hipMemcpyHostToDevice));
 		CTG_STEP(hipMemcpy(d_tb, tb.data(), n_tiles2 * 8, hipMemcpyHostToDevice));
 		CTG_STEP(hipMemcpy(d_off + n_kernel, &total, 8, hipMemcpyHostToDevice));

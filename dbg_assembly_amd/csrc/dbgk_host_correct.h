@@ -1,22 +1,20 @@
 // CORRECT: host side of correct_error_reads on the GPU (include/dbgk.h, ABI 7; kernels in dbgk_correct.h)
 
-struct dbgk_corr {
+struct dbgk_corr : StageDev {
 	dbgk_corr_params p{};
 	corr::CorrParams cp{};
-	int device = 0;
-	int n_cu = 256;
-	hipStream_t stream = nullptr;
-	uint32_t *tab = nullptr;      // the loaded table, ceil(4^k / 32) words
+	DevBuf<uint32_t> tab;         // the loaded table, ceil(4^k / 32) words
 	uint64_t tab_words = 0;
 	bool sealed = false;
 	uint64_t hifreq = 0;
 	// batch buffers, grown on demand
-	uint8_t *d_seq = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-	uint64_t *d_off = nullptr;
-	dbgk_corr_rec *d_rec = nullptr;
-	uint32_t *d_work = nullptr, *d_ovf = nullptr, *d_cnt = nullptr;
-	uint64_t cap_bytes = 0, cap_reads = 0, cap_scratch = 0;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	DevBuf<uint8_t> d_seq, d_out, d_scratch;
+	DevBuf<uint64_t> d_off;
+	DevBuf<dbgk_corr_rec> d_rec;
+	DevBuf<uint32_t> d_work, d_ovf;
+	DevBuf<uint64_t> d_cnt;
+	uint64_t cap_bytes = 0, cap_reads = 0;
+	StageEvents<4> ev;
 	dbgk_corr_stats last{};
 	double ms_mut_scan = 0;       // device time of the last k_mut_scan
 	// output stage (dbgk_host_emit.h): the batch d_out / d_off / d_rec hold, and its compact form
@@ -31,14 +29,6 @@ static int corr_use(dbgk_corr *c)
 	return DBGK_OK;
 }
 
-static void corr_free_batch(dbgk_corr *c)
-{
-	(void)hipFree(c->d_seq); (void)hipFree(c->d_out); (void)hipFree(c->d_off); (void)hipFree(c->d_rec);
-	(void)hipFree(c->d_work); (void)hipFree(c->d_ovf);
-	c->d_seq = c->d_out = nullptr; c->d_off = nullptr; c->d_rec = nullptr; c->d_work = c->d_ovf = nullptr;
-	c->cap_bytes = c->cap_reads = 0;
-}
-
 extern "C" int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr **out)
 {
 	if (!p || !out) return DBGK_ERR_ARG;
@@ -46,27 +36,17 @@ extern "C" int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr
 	if (p->k < 1 || p->k > 19 || p->min_high_region < 1 || p->max_change < 0 || p->further_trim < 0 ||
 	    p->max_tree_nodes < 1 || p->max_tree_nodes >= (1 << 26) || p->min_trimmed_len < 0 || device < 0)
 		return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_corr *c = new (std::nothrow) dbgk_corr;
 	if (!c) return DBGK_ERR_NOMEM;
 	c->p = *p;
-	c->device = device;
 	c->cp = corr::CorrParams{p->k, p->min_high_region, p->max_change, p->further_trim, p->max_tree_nodes, p->min_trimmed_len,
 	                         1ull << (2 * p->k)};
 	c->tab_words = (c->cp.total + 31) / 32;
-	int rc = corr_use(c);
-	hipDeviceProp_t prop;
-	if (!rc && hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 4; ++i)
-		if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
+	int rc = stage_open(*c, device);
+	if (!rc) rc = c->ev.create();
 	if (!rc) rc = emit_create(c->emit, emitk::CorrRule::kCounters, true);
-	if (!rc && hipMalloc(&c->tab, c->tab_words * 4) != hipSuccess) rc = DBGK_ERR_NOMEM;
-	if (!rc && hipMalloc(&c->d_cnt, 4 * sizeof(uint64_t)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (!rc) rc = c->tab.reserve(c->tab_words * 4);
+	if (!rc) rc = c->d_cnt.reserve(4 * sizeof(uint64_t));
 	if (!rc && hipMemsetAsync(c->tab, 0, c->tab_words * 4, c->stream) != hipSuccess) rc = DBGK_ERR_HIP;
 	if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = DBGK_ERR_HIP;
 	if (rc) {
@@ -80,16 +60,8 @@ extern "C" int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr
 extern "C" int dbgk_corr_destroy(dbgk_corr *c)
 {
 	if (!c) return DBGK_ERR_ARG;
-	(void)hipSetDevice(c->device);
-	if (c->stream) (void)hipStreamSynchronize(c->stream);
+	stage_drain(c->device, c->stream);
 	emit_destroy(c->emit);
-	corr_free_batch(c);
-	(void)hipFree(c->d_scratch);
-	(void)hipFree(c->tab);
-	(void)hipFree(c->d_cnt);
-	for (auto &e : c->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
 	delete c;
 	return DBGK_OK;
 }
@@ -103,7 +75,7 @@ extern "C" int dbgk_corr_load_bits(dbgk_corr *c, uint64_t first_byte, uint64_t n
 	int rc = corr_use(c);
 	if (rc) return rc;
 	if (!n_bytes) return DBGK_OK;
-	HIPCHK(hipMemcpyAsync((uint8_t *)c->tab + first_byte, host_bits, n_bytes, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync((uint8_t *)c->tab.p + first_byte, host_bits, n_bytes, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return DBGK_OK;
 }
@@ -131,7 +103,7 @@ extern "C" int dbgk_corr_seal(dbgk_corr *c)
 	if (c->sealed) return DBGK_ERR_STATE;
 	int rc = corr_use(c);
 	if (rc) return rc;
-	unsigned long long *d_hif = (unsigned long long *)c->d_cnt;
+	unsigned long long *d_hif = (unsigned long long *)c->d_cnt.p;
 	HIPCHK(hipMemsetAsync(d_hif, 0, sizeof *d_hif, c->stream));
 	hipLaunchKernelGGL(corr::k_corr_seal, dim3(corr_table_grid(c)), dim3(256), 0, c->stream, c->tab, c->tab_words, c->cp.total,
 	                   c->p.k, d_hif);
@@ -147,7 +119,7 @@ extern "C" int dbgk_corr_from_kfreq(dbgk_corr *c, dbgk_handle *h, uint32_t cutof
 	int rc = corr_use(c);
 	if (rc) return rc;
 	HIPCHK(hipStreamSynchronize(h->stream)); // the counts are final on the handle's stream
-	unsigned long long *d_hif = (unsigned long long *)c->d_cnt;
+	unsigned long long *d_hif = (unsigned long long *)c->d_cnt.p;
 	HIPCHK(hipMemsetAsync(d_hif, 0, sizeof *d_hif, c->stream));
 	hipLaunchKernelGGL(corr::k_corr_from_counts, dim3(corr_table_grid(c)), dim3(256), 0, c->stream, c->tab, c->tab_words,
 	                   c->cp.total, c->p.k, (const uint8_t *)h->counts, cutoff, d_hif);
@@ -172,7 +144,7 @@ extern "C" int dbgk_corr_export_bits(dbgk_corr *c, uint64_t first_byte, uint64_t
 	int rc = corr_use(c);
 	if (rc) return rc;
 	if (!n_bytes) return DBGK_OK;
-	HIPCHK(hipMemcpyAsync(host_out, (const uint8_t *)c->tab + first_byte, n_bytes, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(host_out, (const uint8_t *)c->tab.p + first_byte, n_bytes, hipMemcpyDeviceToHost, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return DBGK_OK;
 }
@@ -198,16 +170,13 @@ static int corr_batch_begin(dbgk_corr *c, const uint64_t *offsets, uint64_t n)
 	if (rc) return rc;
 	const uint64_t nb = offsets[n];
 	if (nb + 16 > c->cap_bytes || n > c->cap_reads) {
-		corr_free_batch(c);
-		c->cap_bytes = std::max<uint64_t>(nb + 16, 1 << 20);
-		c->cap_reads = std::max<uint64_t>(n, 1 << 14);
-		if (hipMalloc(&c->d_seq, c->cap_bytes) != hipSuccess || hipMalloc(&c->d_out, c->cap_bytes) != hipSuccess ||
-		    hipMalloc(&c->d_off, (c->cap_reads + 1) * 8) != hipSuccess ||
-		    hipMalloc(&c->d_rec, c->cap_reads * sizeof(dbgk_corr_rec)) != hipSuccess ||
-		    hipMalloc(&c->d_work, c->cap_reads * 4) != hipSuccess || hipMalloc(&c->d_ovf, c->cap_reads * 4) != hipSuccess) {
-			corr_free_batch(c);
+		const uint64_t bytes = std::max<uint64_t>(nb + 16, 1 << 20), reads = std::max<uint64_t>(n, 1 << 14);
+		c->cap_bytes = c->cap_reads = 0;
+		if (c->d_seq.reserve(bytes) || c->d_out.reserve(bytes) || c->d_off.reserve((reads + 1) * 8) || c->d_rec.reserve(reads * sizeof(dbgk_corr_rec)) ||
+		    c->d_work.reserve(reads * 4) || c->d_ovf.reserve(reads * 4))
 			return DBGK_ERR_NOMEM;
-		}
+		c->cap_bytes = bytes;
+		c->cap_reads = reads;
 	}
 	return DBGK_OK;
 }
@@ -249,13 +218,7 @@ static int corr_batch_kernels(dbgk_corr *c, const uint8_t *d_in, const uint64_t 
 		const uint64_t slice = (2 * cap * sizeof(corr::TNode) + (ol / 64 + 1) * 8 + ol + 255) & ~255ull;
 		const uint64_t budget = 1ull << 30;
 		const uint64_t waves = std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)h_cnt[1], budget / slice, (uint64_t)c->n_cu * 8}));
-		if (waves * slice > c->cap_scratch) {
-			(void)hipFree(c->d_scratch);
-			c->d_scratch = nullptr;
-			c->cap_scratch = 0;
-			if (hipMalloc(&c->d_scratch, waves * slice) != hipSuccess) return DBGK_ERR_NOMEM;
-			c->cap_scratch = waves * slice;
-		}
+		if (c->d_scratch.reserve(waves * slice)) return DBGK_ERR_NOMEM;
 		HIPCHK(hipEventRecord(c->ev[2], c->stream));
 		hipLaunchKernelGGL(corr::k_corr_overflow, dim3((unsigned)waves), dim3(corr::kWave), 0, c->stream, d_in,
 		                   c->d_off, c->cp, c->tab, c->d_out, c->d_rec, c->d_ovf, h_cnt[1], c->d_scratch, slice, (uint32_t)ol, (uint32_t)cap);

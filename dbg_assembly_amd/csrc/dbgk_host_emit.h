@@ -3,50 +3,47 @@
 // batch (have_batch, batch_n, the cleaner's kind, shift and planes) stays with them.  The parser (dbgk_host_parse.h) holds one too:
 // its source is the text, where the quality line of a read lies elsewhere than its sequence line (split_src).
 
-// dbgk_sort.hip
-extern "C" int dbgk_internal_scan_lengths(void *tmp, size_t *tmp_bytes, const uint32_t *d_len, uint64_t *d_offsets, uint64_t n_items,
-                                          hipStream_t stream);
-
 struct EmitStage {
-	uint8_t *bases = nullptr, *quals = nullptr; // 16-byte vectors, the pad of the last one 0; one capacity.  quals: from the first batch with qualities on
-	uint64_t *off = nullptr;      // n + 1 compact offsets
-	uint64_t *src = nullptr;      // where each read's result starts in the source planes
-	uint64_t *qsrc = nullptr;     // split_src: ... in the quality plane's source, where that is another place (the parser's text)
-	uint32_t *len = nullptr;
-	void *tmp = nullptr;          // the scan's temporary storage
-	unsigned long long *ctr = nullptr; // n_counters counters of the producer's rule
+	DevBuf<uint8_t> bases, quals; // 16-byte vectors, the pad of the last one 0; one capacity.  quals: from the first batch with qualities on
+	DevBuf<uint64_t> off;         // n + 1 compact offsets
+	DevBuf<uint64_t> src;         // where each read's result starts in the source planes
+	DevBuf<uint64_t> qsrc;        // split_src: ... in the quality plane's source, where that is another place (the parser's text)
+	DevBuf<uint32_t> len;
+	ScanTmp tmp;                  // the scan's temporary storage
+	DevBuf<unsigned long long> ctr; // n_counters counters of the producer's rule
 	int n_counters = 0;
 	bool lds_one_plane = false;   // a batch without qualities takes k_emit_gather_lds: the corrector's stage (dbgk_emit.h says why)
 	bool split_src = false;       // each plane is gathered on its own, the quality plane from qsrc: the parser's stage (set after emit_create)
-	uint64_t cap_bytes = 0, cap_reads = 0, tmp_bytes = 0;
+	uint64_t cap_bytes = 0, cap_reads = 0;
 	uint64_t n = 0, total = 0;
 	bool has_qual = false;        // the compact batch has a quality plane
 	bool have = false;            // the last emit_run succeeded: n reads, total bytes per plane
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // length + scan: [0] .. [1]; gather: [2] .. [3]
+	StageEvents<4> ev;            // length + scan: [0] .. [1]; gather: [2] .. [3]
 	hipEvent_t done = nullptr;    // the compact batch is complete (recorded on the producer's stream)
 	hipEvent_t read = nullptr;    // a graph handle has read it (recorded on that handle's stream by emit_push)
 	bool lent = false;            // `read` is pending: waited for before the compact buffers are written, regrown or freed
+	~EmitStage()
+	{
+		for (hipEvent_t e : {done, read})
+			if (e) (void)hipEventDestroy(e);
+	}
 };
 
 static int emit_create(EmitStage &s, int n_counters, bool lds_one_plane)
 {
 	s.n_counters = n_counters;
 	s.lds_one_plane = lds_one_plane;
-	for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&s.ev[i]));
+	int rc = s.ev.create();
+	if (rc) return rc;
 	HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
 	HIPCHK(hipEventCreateWithFlags(&s.read, hipEventDisableTiming));
-	if (hipMalloc(&s.ctr, n_counters * sizeof(unsigned long long)) != hipSuccess) return DBGK_ERR_NOMEM;
-	return DBGK_OK;
+	return s.ctr.reserve(n_counters * sizeof(unsigned long long));
 }
 
-// (the producer's stream is idle)
+// before the handle is deleted (the producer's stream is idle): a graph handle may still be reading the compact batch
 static void emit_destroy(EmitStage &s)
 {
-	if (s.lent) (void)hipEventSynchronize(s.read); // a graph handle may still be reading the compact batch
-	(void)hipFree(s.bases); (void)hipFree(s.quals); (void)hipFree(s.off); (void)hipFree(s.src); (void)hipFree(s.qsrc); (void)hipFree(s.len);
-	(void)hipFree(s.tmp); (void)hipFree(s.ctr);
-	for (hipEvent_t e : {s.ev[0], s.ev[1], s.ev[2], s.ev[3], s.done, s.read})
-		if (e) (void)hipEventDestroy(e);
+	if (s.lent) (void)hipEventSynchronize(s.read);
 }
 
 // the compact buffers are about to be written (free_them: regrown or freed): a graph handle that was given them has to be done
@@ -66,7 +63,7 @@ template <bool QUAL, bool SUBST>
 static void emit_launch_gather(EmitStage &s, hipStream_t stream, unsigned grid, const uint8_t *seq, const uint8_t *qual, uint32_t shift_word)
 {
 	hipLaunchKernelGGL((emitk::k_emit_gather<QUAL, SUBST>), dim3(grid), dim3(emitk::kEmitBlock), 0, stream, seq, qual, s.src, s.off, (uint32_t)s.n,
-	                   s.total, shift_word, reinterpret_cast<uint4 *>(s.bases), reinterpret_cast<uint4 *>(s.quals));
+	                   s.total, shift_word, reinterpret_cast<uint4 *>(s.bases.p), reinterpret_cast<uint4 *>(s.quals.p));
 }
 
 // The n reads of the planes seq / qual (qual null: no quality plane; subst: the quality of a base 'N' becomes the byte of shift_word)
@@ -83,32 +80,19 @@ static int emit_run(EmitStage &s, hipStream_t stream, int n_cu, uint64_t n, cons
 	int rc = emit_reclaim(s, stream, grow_reads);
 	if (rc) return rc;
 	if (grow_reads) {
-		(void)hipFree(s.off); (void)hipFree(s.len); (void)hipFree(s.src); (void)hipFree(s.qsrc);
-		s.off = nullptr; s.len = nullptr; s.src = nullptr; s.qsrc = nullptr;
 		s.cap_reads = 0;
 		const uint64_t cap = std::max<uint64_t>(n, 1 << 14);
-		if (hipMalloc(&s.off, (cap + 1) * 8) != hipSuccess || hipMalloc(&s.len, (cap + 1) * 4) != hipSuccess ||
-		    hipMalloc(&s.src, cap * 8) != hipSuccess || (s.split_src && hipMalloc(&s.qsrc, cap * 8) != hipSuccess))
+		if (s.off.reserve((cap + 1) * 8) || s.len.reserve((cap + 1) * 4) || s.src.reserve(cap * 8) || (s.split_src && s.qsrc.reserve(cap * 8)))
 			return DBGK_ERR_NOMEM;
 		s.cap_reads = cap;
 	}
-	size_t need = 0;
-	if (n && dbgk_internal_scan_lengths(nullptr, &need, s.len, s.off, n + 1, stream)) return DBGK_ERR_HIP;
-	if (need > s.tmp_bytes) {
-		HIPCHK(hipStreamSynchronize(stream));
-		(void)hipFree(s.tmp);
-		s.tmp = nullptr;
-		s.tmp_bytes = 0;
-		if (hipMalloc(&s.tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-		s.tmp_bytes = need;
-	}
+	if (n && (rc = stage_scan_reserve(s.tmp, stream, s.len, s.off, n + 1))) return rc;
 	HIPCHK(hipMemsetAsync(s.ctr, 0, s.n_counters * sizeof(unsigned long long), stream));
 	HIPCHK(hipEventRecord(s.ev[0], stream));
 	if (n) {
 		launch_len((unsigned)std::min<uint64_t>((n + emitk::kEmitBlock) / emitk::kEmitBlock, (uint64_t)n_cu * 16), s.len, s.src, s.ctr);
 		HIPCHK(hipGetLastError());
-		size_t bytes = s.tmp_bytes;
-		if (dbgk_internal_scan_lengths(s.tmp, &bytes, s.len, s.off, n + 1, stream)) return DBGK_ERR_HIP;
+		if ((rc = stage_scan(s.tmp, stream, s.len, s.off, n + 1))) return rc;
 	} else {
 		HIPCHK(hipMemsetAsync(s.off, 0, 8, stream));
 	}
@@ -123,11 +107,9 @@ static int emit_run(EmitStage &s, hipStream_t stream, int n_cu, uint64_t n, cons
 		rc = emit_reclaim(s, stream, true);
 		if (rc) return rc;
 		const bool keep_qual = with_qual || s.quals; // a stage that has held a quality plane keeps one, as the cleaner's batch buffers do
-		(void)hipFree(s.bases); (void)hipFree(s.quals);
-		s.bases = s.quals = nullptr;
 		const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, s.cap_bytes), 1 << 20);
 		s.cap_bytes = 0;
-		if (hipMalloc(&s.bases, cap) != hipSuccess || (keep_qual && hipMalloc(&s.quals, cap) != hipSuccess)) return DBGK_ERR_NOMEM;
+		if (s.bases.reserve(cap) || (keep_qual && s.quals.reserve(cap))) return DBGK_ERR_NOMEM;
 		s.cap_bytes = cap;
 	}
 	s.n = n;
@@ -138,13 +120,13 @@ static int emit_run(EmitStage &s, hipStream_t stream, int n_cu, uint64_t n, cons
 		HIPCHK(hipEventRecord(s.ev[2], stream)); // directly in front of the kernel: the copies, the host round trip and an allocation lie before it
 		if (s.split_src) { // one launch per plane, both from `seq`, under the one set of offsets
 			hipLaunchKernelGGL((emitk::k_emit_gather<false, false>), dim3(grid), dim3(emitk::kEmitBlock), 0, stream, seq, (const uint8_t *)nullptr, s.src,
-			                   s.off, (uint32_t)n, total, 0u, reinterpret_cast<uint4 *>(s.bases), (uint4 *)nullptr);
+			                   s.off, (uint32_t)n, total, 0u, reinterpret_cast<uint4 *>(s.bases.p), (uint4 *)nullptr);
 			if (with_qual)
 				hipLaunchKernelGGL((emitk::k_emit_gather<false, false>), dim3(grid), dim3(emitk::kEmitBlock), 0, stream, seq, (const uint8_t *)nullptr,
-				                   s.qsrc, s.off, (uint32_t)n, total, 0u, reinterpret_cast<uint4 *>(s.quals), (uint4 *)nullptr);
+				                   s.qsrc, s.off, (uint32_t)n, total, 0u, reinterpret_cast<uint4 *>(s.quals.p), (uint4 *)nullptr);
 		} else if (!with_qual && s.lds_one_plane)
 			hipLaunchKernelGGL(emitk::k_emit_gather_lds, dim3(grid), dim3(emitk::kEmitBlock), 0, stream, seq, s.src, s.off, (uint32_t)n, total,
-			                   reinterpret_cast<uint4 *>(s.bases));
+			                   reinterpret_cast<uint4 *>(s.bases.p));
 		else if (!with_qual) emit_launch_gather<false, false>(s, stream, grid, seq, qual, shift_word);
 		else if (subst) emit_launch_gather<true, true>(s, stream, grid, seq, qual, shift_word);
 		else emit_launch_gather<true, false>(s, stream, grid, seq, qual, shift_word);
@@ -178,8 +160,8 @@ static int emit_results(EmitStage &s, hipStream_t stream, char *bases, char *qua
 
 static void emit_device(const EmitStage &s, const char **d_bases, const char **d_quals, const uint64_t **d_offsets, uint64_t *n_reads, uint64_t *n_bases)
 {
-	*d_bases = (const char *)s.bases;
-	if (d_quals) *d_quals = s.has_qual ? (const char *)s.quals : nullptr;
+	*d_bases = (const char *)s.bases.p;
+	if (d_quals) *d_quals = s.has_qual ? (const char *)s.quals.p : nullptr;
 	*d_offsets = s.off;
 	*n_reads = s.n;
 	*n_bases = s.total;
@@ -197,7 +179,7 @@ static int emit_push(dbgk_handle *h, EmitStage &s)
 	// `read` is ONE event: a push into another handle re-records it.  That handle's stream first waits for the earlier record, so
 	// the new one lies behind every reader so far, whichever handles they were pushed to.
 	if (s.lent) HIPCHK(hipStreamWaitEvent(h->stream, s.read, 0));
-	rc = dbgk_push_reads_device(h, (const char *)s.bases, s.off, s.n, s.total);
+	rc = dbgk_push_reads_device(h, (const char *)s.bases.p, s.off, s.n, s.total);
 	// (also after a failed push: part of its work may have been queued)
 	if (hipEventRecord(s.read, h->stream) == hipSuccess) s.lent = true;
 	else if (rc == DBGK_OK) rc = DBGK_ERR_HIP;

@@ -6,13 +6,13 @@ struct dbgk_fill {
 	dbgk_link *L = nullptr;
 	dbgk_fill_params p{};
 	// per record, in record order
-	uint64_t *d_pair_keys = nullptr, *d_skeys = nullptr, *d_svals = nullptr;
-	int4 *d_rinfo = nullptr;
+	DevBuf<uint64_t> d_pair_keys, d_skeys, d_svals;
+	DevBuf<int4> d_rinfo;
 	uint64_t n_records = 0, cap_records = 0;
-	fillk::Counters *d_fctr = nullptr;
+	DevBuf<fillk::Counters> d_fctr;
 	// reads
-	uint8_t *d_reads = nullptr;
-	uint64_t *d_read_off = nullptr;
+	DevBuf<uint8_t> d_reads;
+	DevBuf<uint64_t> d_read_off;
 	uint64_t n_reads = 0;
 	bool reads_set = false;
 	// gap statistics, ascending by key
@@ -24,7 +24,7 @@ struct dbgk_fill {
 	std::vector<dbgk_fill_item> items;
 	std::vector<dbgk_fill_gap> gaps;
 	std::vector<int32_t> repeats;
-	uint8_t *d_cons = nullptr;
+	DevBuf<uint8_t> d_cons;
 	uint64_t cons_bytes = 0;
 	dbgk_fill_summary summary{};
 	dbgk_fill_timing stats{};
@@ -45,7 +45,7 @@ extern "C" int dbgk_fill_create(const dbgk_fill_params *p, int device, dbgk_fill
 	f->p = *p;
 	dbgk_link_params lp{0, p->pair_num_cut, 1};    // (the orientation and gap of a record are FILL's own: no -m, no -i)
 	int rc = dbgk_link_create(&lp, device, &f->L);
-	if (!rc && hipMalloc(&f->d_fctr, sizeof(fillk::Counters)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (!rc) rc = f->d_fctr.reserve(sizeof(fillk::Counters));
 	if (!rc && hipMemsetAsync(f->d_fctr, 0, sizeof(fillk::Counters), f->L->stream) != hipSuccess) rc = DBGK_ERR_HIP;
 	if (rc) {
 		dbgk_fill_destroy(f);
@@ -58,14 +58,10 @@ extern "C" int dbgk_fill_create(const dbgk_fill_params *p, int device, dbgk_fill
 extern "C" int dbgk_fill_destroy(dbgk_fill *f)
 {
 	if (!f) return DBGK_ERR_ARG;
-	if (f->L) {
-		(void)hipSetDevice(f->L->device);
-		(void)hipStreamSynchronize(f->L->stream);
-	}
-	(void)hipFree(f->d_pair_keys); (void)hipFree(f->d_skeys); (void)hipFree(f->d_svals); (void)hipFree(f->d_rinfo); (void)hipFree(f->d_fctr);
-	(void)hipFree(f->d_reads); (void)hipFree(f->d_read_off); (void)hipFree(f->d_cons);
-	if (f->L) dbgk_link_destroy(f->L);
-	delete f;
+	dbgk_link *l = f->L;
+	if (l) stage_drain(l->device, l->stream);
+	delete f; // (its buffers go before the link's stream does)
+	if (l) dbgk_link_destroy(l);
 	return DBGK_OK;
 }
 
@@ -81,12 +77,10 @@ extern "C" int dbgk_fill_set_reads(dbgk_fill *f, const char *bases, const uint64
 	if (f->resolved) return DBGK_ERR_STATE;
 	dbgk_link *l = f->L;
 	HIPCHK(hipSetDevice(l->device));
-	(void)hipFree(f->d_reads); (void)hipFree(f->d_read_off);
-	f->d_reads = nullptr;
-	f->d_read_off = nullptr;
 	f->reads_set = false;
+	f->d_reads.release(); f->d_read_off.release();
 	const uint64_t nb = offsets[n_reads];
-	if (hipMalloc(&f->d_reads, nb + 16) != hipSuccess || hipMalloc(&f->d_read_off, (n_reads + 1) * 8) != hipSuccess) return DBGK_ERR_NOMEM;
+	if (f->d_reads.reserve(nb + 16) || f->d_read_off.reserve((n_reads + 1) * 8)) return DBGK_ERR_NOMEM;
 	if (nb) HIPCHK(hipMemcpyAsync(f->d_reads, bases, nb, hipMemcpyHostToDevice, l->stream));
 	HIPCHK(hipMemcpyAsync(f->d_read_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, l->stream));
 	HIPCHK(hipStreamSynchronize(l->stream));
@@ -101,22 +95,20 @@ static int fill_reserve(dbgk_fill *f, uint64_t n_new)
 	if (f->n_records + n_new <= f->cap_records) return DBGK_OK;
 	dbgk_link *l = f->L;
 	const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(f->n_records + n_new, 2 * f->cap_records), 1 << 15);
-	void *a[4] = {nullptr, nullptr, nullptr, nullptr};
-	void *old[4] = {f->d_pair_keys, f->d_skeys, f->d_svals, f->d_rinfo};
-	const uint64_t width[4] = {8, 8, 8, 16};
-	bool ok = true;
-	for (int i = 0; i < 4 && ok; ++i) ok = hipMalloc(&a[i], cap * width[i]) == hipSuccess;
-	if (!ok) {
-		for (void *x : a) (void)hipFree(x);
-		return DBGK_ERR_NOMEM;
+	DevBuf<uint64_t> pk, sk, sv;
+	DevBuf<int4> ri;
+	if (pk.reserve(cap * 8) || sk.reserve(cap * 8) || sv.reserve(cap * 8) || ri.reserve(cap * 16)) return DBGK_ERR_NOMEM;
+	if (f->n_records) {
+		HIPCHK(hipMemcpyAsync(pk, f->d_pair_keys, f->n_records * 8, hipMemcpyDeviceToDevice, l->stream));
+		HIPCHK(hipMemcpyAsync(sk, f->d_skeys, f->n_records * 8, hipMemcpyDeviceToDevice, l->stream));
+		HIPCHK(hipMemcpyAsync(sv, f->d_svals, f->n_records * 8, hipMemcpyDeviceToDevice, l->stream));
+		HIPCHK(hipMemcpyAsync(ri, f->d_rinfo, f->n_records * 16, hipMemcpyDeviceToDevice, l->stream));
 	}
-	for (int i = 0; i < 4 && f->n_records; ++i) HIPCHK(hipMemcpyAsync(a[i], old[i], f->n_records * width[i], hipMemcpyDeviceToDevice, l->stream));
 	HIPCHK(hipStreamSynchronize(l->stream));
-	for (void *x : old) (void)hipFree(x);
-	f->d_pair_keys = (uint64_t *)a[0];
-	f->d_skeys = (uint64_t *)a[1];
-	f->d_svals = (uint64_t *)a[2];
-	f->d_rinfo = (int4 *)a[3];
+	f->d_pair_keys.take(pk);
+	f->d_skeys.take(sk);
+	f->d_svals.take(sv);
+	f->d_rinfo.take(ri);
 	f->cap_records = cap;
 	return DBGK_OK;
 }
@@ -137,11 +129,11 @@ static int fill_add(dbgk_fill *f, const void *src, uint64_t n, bool from_hits, u
 	const uint32_t nc = (uint32_t)l->lens.size();
 	if (from_hits)
 		hipLaunchKernelGGL(fillk::k_fill_orient<true>, dim3(link_grid(l, n)), dim3(fillk::kFillThreads), 0, l->stream, (const fillk::Rec *)nullptr,
-		                   static_cast<const linkk::Hit *>(l->d_in), n, nc, (uint32_t)first_read, f->n_records, l->d_keys, l->d_vals, f->d_pair_keys,
+		                   reinterpret_cast<const linkk::Hit *>(l->d_in.p), n, nc, (uint32_t)first_read, f->n_records, l->d_keys, l->d_vals, f->d_pair_keys,
 		                   f->d_skeys, f->d_svals, f->d_rinfo, l->d_ctr, f->d_fctr);
 	else
 		hipLaunchKernelGGL(fillk::k_fill_orient<false>, dim3(link_grid(l, n)), dim3(fillk::kFillThreads), 0, l->stream,
-		                   static_cast<const fillk::Rec *>(l->d_in), (const linkk::Hit *)nullptr, n, nc, 0u, f->n_records, l->d_keys, l->d_vals,
+		                   reinterpret_cast<const fillk::Rec *>(l->d_in.p), (const linkk::Hit *)nullptr, n, nc, 0u, f->n_records, l->d_keys, l->d_vals,
 		                   f->d_pair_keys, f->d_skeys, f->d_svals, f->d_rinfo, l->d_ctr, f->d_fctr);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(l->ev[1], l->stream));
@@ -214,8 +206,8 @@ extern "C" int dbgk_fill_build(dbgk_fill *f)
 	t0 = std::chrono::steady_clock::now();
 	if ((rc = dbgk_internal_sort_pairs(f->d_skeys, f->d_svals, n, l->stream))) return rc;
 	f->stats.ms_sort += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	fillk::PairStat *d_stat = nullptr;
-	if (hipMalloc(&d_stat, fc.pooled * sizeof(fillk::PairStat)) != hipSuccess) return DBGK_ERR_NOMEM;   // at most one pair per record
+	DevBuf<fillk::PairStat> d_stat;
+	if (d_stat.reserve(fc.pooled * sizeof(fillk::PairStat))) return DBGK_ERR_NOMEM;   // at most one pair per record
 	auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, "dbgk_fill_build", __LINE__); };
 	step(hipEventRecord(l->ev[0], l->stream));
 	hipLaunchKernelGGL(fillk::k_fill_gapstat, dim3(link_grid(l, fc.pooled)), dim3(fillk::kFillThreads), 0, l->stream, f->d_skeys, f->d_svals, fc.pooled,
@@ -230,7 +222,6 @@ extern "C" int dbgk_fill_build(dbgk_fill *f)
 		f->pairs.resize(fc.pairs);
 		step(hipMemcpy(f->pairs.data(), d_stat, fc.pairs * sizeof(fillk::PairStat), hipMemcpyDeviceToHost));
 	}
-	(void)hipFree(d_stat);
 	if (rc) return rc;
 	// the slots come in no particular order
 	std::sort(f->pairs.begin(), f->pairs.end(), [](const fillk::PairStat &a, const fillk::PairStat &b) { return a.key < b.key; });
@@ -378,19 +369,14 @@ extern "C" int dbgk_fill_resolve(dbgk_fill *f, dbgk_fill_summary *out)
 		std::vector<uint2> work;
 		for (size_t g = 0; g < desc.size(); ++g)
 			for (uint32_t b = 0; b < ((uint32_t)desc[g].gap + 63) / 64; ++b) work.push_back(make_uint2((uint32_t)g, b));
-		fillk::GapDesc *d_desc = nullptr;
-		uint2 *d_work = nullptr;
-		uint32_t *d_freq = nullptr;
-		int *d_status = nullptr;
-		auto release = [&]() { (void)hipFree(d_desc); (void)hipFree(d_work); (void)hipFree(d_freq); (void)hipFree(d_status); };
-		(void)hipFree(f->d_cons);
-		f->d_cons = nullptr;
-		if (hipMalloc(&f->d_cons, cons_bytes + 16) != hipSuccess || hipMalloc(&d_desc, desc.size() * sizeof(fillk::GapDesc)) != hipSuccess ||
-		    hipMalloc(&d_work, work.size() * sizeof(uint2)) != hipSuccess || hipMalloc(&d_freq, cons_bytes * 4) != hipSuccess ||
-		    hipMalloc(&d_status, desc.size() * 4) != hipSuccess) {
-			release();
+		DevBuf<fillk::GapDesc> d_desc;
+		DevBuf<uint2> d_work;
+		DevBuf<uint32_t> d_freq;
+		DevBuf<int> d_status;
+		f->d_cons.release();
+		if (f->d_cons.reserve(cons_bytes + 16) || d_desc.reserve(desc.size() * sizeof(fillk::GapDesc)) || d_work.reserve(work.size() * sizeof(uint2)) ||
+		    d_freq.reserve(cons_bytes * 4) || d_status.reserve(desc.size() * 4))
 			return DBGK_ERR_NOMEM;
-		}
 		int rc = DBGK_OK;
 		auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, "dbgk_fill_resolve", __LINE__); };
 		std::vector<int> status(desc.size(), 0);
@@ -412,7 +398,6 @@ extern "C" int dbgk_fill_resolve(dbgk_fill *f, dbgk_fill_summary *out)
 		step(hipStreamSynchronize(l->stream));
 		float ms = 0;
 		if (!rc) step(hipEventElapsedTime(&ms, l->ev[0], l->ev[1]));
-		release();
 		if (rc) return rc;
 		f->stats.ms_consensus = ms;
 		for (size_t g = 0; g < desc.size(); ++g)

@@ -2,30 +2,25 @@
 // its read-back and its device view.  The launches of a call follow each other on one stream; the host reads the counters and the
 // total in between, which size the text.
 
-struct dbgk_fmt {
-	int device = 0;
-	int n_cu = 256;
+struct dbgk_fmt : StageDev {
 	int format = 1;
 	uint32_t marker = 0;
-	hipStream_t stream = nullptr;
-	uint8_t *out = nullptr; // 16-byte vectors, the pad of the last one 0, 64 readable bytes behind
-	uint64_t cap_out = 0, n_out = 0;
+	DevBuf<uint8_t> out; // 16-byte vectors, the pad of the last one 0, 64 readable bytes behind
+	uint64_t n_out = 0;
 	bool have = false;
-	uint32_t *len = nullptr; // n + 1 output lengths and their exclusive scan
-	uint64_t *coff = nullptr;
+	DevBuf<uint32_t> len; // n + 1 output lengths and their exclusive scan
+	DevBuf<uint64_t> coff;
 	uint64_t cap_recs = 0;
-	void *tmp = nullptr; // the scan's temporary storage
-	size_t tmp_bytes = 0;
-	unsigned long long *ctr = nullptr;
-	uint8_t *suf = nullptr; // the uploaded suffix plane
-	uint64_t *soff = nullptr;
-	uint64_t cap_suf = 0, cap_soff = 0;
+	ScanTmp tmp; // the scan's temporary storage
+	DevBuf<unsigned long long> ctr;
+	DevBuf<uint8_t> suf; // the uploaded suffix plane
+	DevBuf<uint64_t> soff;
 	// dbgk_fmt_records: the uploaded batch
-	uint8_t *in_text = nullptr, *in_b = nullptr, *in_q = nullptr;
-	uint64_t *in_off = nullptr;
-	dbgk_parse_rec *in_rec = nullptr;
-	uint64_t in_cap_text = 0, in_cap_b = 0, in_cap_q = 0, in_cap_recs = 0;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // length + scan: [0] .. [1]; gather: [2] .. [3]
+	DevBuf<uint8_t> in_text, in_b, in_q;
+	DevBuf<uint64_t> in_off;
+	DevBuf<dbgk_parse_rec> in_rec;
+	uint64_t in_cap_recs = 0;
+	StageEvents<4> ev; // length + scan: [0] .. [1]; gather: [2] .. [3]
 };
 
 extern "C" int dbgk_fmt_create(int32_t format, int32_t marker, int device, dbgk_fmt **out)
@@ -33,28 +28,13 @@ extern "C" int dbgk_fmt_create(int32_t format, int32_t marker, int device, dbgk_
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
 	if (device < 0 || (format != 1 && format != 2) || marker < 0 || marker > 255) return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_fmt *f = new (std::nothrow) dbgk_fmt;
 	if (!f) return DBGK_ERR_NOMEM;
-	f->device = device;
 	f->format = format;
 	f->marker = (uint32_t)marker;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) f->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 4; ++i)
-		if (hipEventCreate(&f->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && hipMalloc(&f->ctr, fmtk::FC_COUNT * sizeof(unsigned long long)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	int rc = stage_open(*f, device);
+	if (!rc) rc = f->ev.create();
+	if (!rc) rc = f->ctr.reserve(fmtk::FC_COUNT * sizeof(unsigned long long));
 	if (rc) {
 		dbgk_fmt_destroy(f);
 		return rc;
@@ -66,28 +46,8 @@ extern "C" int dbgk_fmt_create(int32_t format, int32_t marker, int device, dbgk_
 extern "C" int dbgk_fmt_destroy(dbgk_fmt *f)
 {
 	if (!f) return DBGK_ERR_ARG;
-	(void)hipSetDevice(f->device);
-	if (f->stream) (void)hipStreamSynchronize(f->stream);
-	(void)hipFree(f->out); (void)hipFree(f->len); (void)hipFree(f->coff); (void)hipFree(f->tmp); (void)hipFree(f->ctr); (void)hipFree(f->suf);
-	(void)hipFree(f->soff); (void)hipFree(f->in_text); (void)hipFree(f->in_b); (void)hipFree(f->in_q); (void)hipFree(f->in_off); (void)hipFree(f->in_rec);
-	for (hipEvent_t e : f->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (f->stream) (void)hipStreamDestroy(f->stream);
+	stage_drain(f->device, f->stream);
 	delete f;
-	return DBGK_OK;
-}
-
-// a device buffer of at least `want` bytes (the stream is idle: nothing queued reads the old one)
-template <class T>
-static int fmt_ensure(T *&buf, uint64_t &cap, uint64_t want, uint64_t least)
-{
-	if (want <= cap && buf) return DBGK_OK;
-	(void)hipFree(buf);
-	buf = nullptr;
-	cap = 0;
-	const uint64_t bytes = std::max<uint64_t>(want, least);
-	if (hipMalloc(&buf, bytes) != hipSuccess) return DBGK_ERR_NOMEM;
-	cap = bytes;
 	return DBGK_OK;
 }
 
@@ -107,29 +67,22 @@ static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk
 	}
 	const bool with_suf = n_suf != 0; // (a plane of empty suffixes is no plane)
 	HIPCHK(hipStreamSynchronize(f->stream));
-	uint64_t cap_len = f->cap_recs * 4, cap_coff = f->cap_recs * 8;
 	if (n + 1 > f->cap_recs || !f->len || !f->coff) {
 		const uint64_t cap = std::max<uint64_t>(n + 1, 1 << 14);
 		f->cap_recs = 0;
-		cap_len = cap_coff = 0;
-		if (fmt_ensure(f->len, cap_len, cap * 4, 0) || fmt_ensure(f->coff, cap_coff, cap * 8, 0)) return DBGK_ERR_NOMEM;
+		if (f->len.reserve(cap * 4) || f->coff.reserve(cap * 8)) return DBGK_ERR_NOMEM;
 		f->cap_recs = cap;
 	}
 	if (with_suf) {
-		if (fmt_ensure(f->suf, f->cap_suf, n_suf + 16, 1 << 16) || fmt_ensure(f->soff, f->cap_soff, (n + 1) * 8, 1 << 17)) return DBGK_ERR_NOMEM;
+		if (f->suf.reserve(n_suf + 16, 1 << 16) || f->soff.reserve((n + 1) * 8, 1 << 17)) return DBGK_ERR_NOMEM;
 		HIPCHK(hipMemcpyAsync(f->suf, suffix, n_suf, hipMemcpyHostToDevice, f->stream));
 		HIPCHK(hipMemcpyAsync(f->soff, suffix_offsets, (n + 1) * 8, hipMemcpyHostToDevice, f->stream));
 	}
-	size_t need = 0;
-	if (n && dbgk_internal_scan_lengths(nullptr, &need, f->len, f->coff, n + 1, f->stream)) return DBGK_ERR_HIP;
-	if (need > f->tmp_bytes) {
-		(void)hipFree(f->tmp);
-		f->tmp = nullptr;
-		f->tmp_bytes = 0;
-		if (hipMalloc(&f->tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-		f->tmp_bytes = need;
+	if (n) {
+		const int rc = stage_scan_reserve(f->tmp, f->stream, f->len, f->coff, n + 1);
+		if (rc) return rc;
 	}
-	const fmtk::FmtIn in{text, recs, bases, quals, off, with_suf ? f->suf : nullptr, with_suf ? f->soff : nullptr};
+	const fmtk::FmtIn in{text, recs, bases, quals, off, with_suf ? f->suf.p : nullptr, with_suf ? f->soff.p : nullptr};
 	unsigned long long ctr[fmtk::FC_COUNT] = {0};
 	uint64_t total = 0;
 	HIPCHK(hipEventRecord(f->ev[0], f->stream));
@@ -139,8 +92,8 @@ static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk
 		hipLaunchKernelGGL(fmtk::k_fmt_len, dim3(grid), dim3(emitk::kEmitBlock), 0, f->stream, in, (uint32_t)n, (uint32_t)n_text, (uint32_t)fastq, f->len,
 		                   f->ctr);
 		HIPCHK(hipGetLastError());
-		size_t bytes = f->tmp_bytes;
-		if (dbgk_internal_scan_lengths(f->tmp, &bytes, f->len, f->coff, n + 1, f->stream)) return DBGK_ERR_HIP;
+		const int rc = stage_scan(f->tmp, f->stream, f->len, f->coff, n + 1);
+		if (rc) return rc;
 	}
 	HIPCHK(hipEventRecord(f->ev[1], f->stream));
 	if (n) {
@@ -150,17 +103,17 @@ static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk
 	HIPCHK(hipStreamSynchronize(f->stream)); // the total sizes the text; the caller's suffix plane is free from here on
 	if (ctr[fmtk::FC_BAD]) return DBGK_ERR_ARG; // a header that leaves the text, offsets that decrease, a record of 2^32 bytes
 	// whole vectors, and room behind the end for the 16-byte reads of the kernels that take the text as their input
-	if (fmt_ensure(f->out, f->cap_out, ((total + 15) & ~15ull) + 64, 1 << 20)) return DBGK_ERR_NOMEM;
+	if (f->out.reserve(((total + 15) & ~15ull) + 64, 1 << 20)) return DBGK_ERR_NOMEM;
 	if (total) {
 		const uint64_t tiles = (total + emitk::kEmitTile - 1) / emitk::kEmitTile;
 		const unsigned grid = (unsigned)std::min<uint64_t>(tiles, (uint64_t)f->n_cu * 64);
 		HIPCHK(hipEventRecord(f->ev[2], f->stream));
 		if (fastq)
 			hipLaunchKernelGGL(fmtk::k_fmt_gather<true>, dim3(grid), dim3(emitk::kEmitBlock), 0, f->stream, in, (const uint64_t *)f->coff, (uint32_t)n, total,
-			                   f->marker, reinterpret_cast<uint4 *>(f->out));
+			                   f->marker, reinterpret_cast<uint4 *>(f->out.p));
 		else
 			hipLaunchKernelGGL(fmtk::k_fmt_gather<false>, dim3(grid), dim3(emitk::kEmitBlock), 0, f->stream, in, (const uint64_t *)f->coff, (uint32_t)n, total,
-			                   f->marker, reinterpret_cast<uint4 *>(f->out));
+			                   f->marker, reinterpret_cast<uint4 *>(f->out.p));
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(f->ev[3], f->stream));
 		HIPCHK(hipStreamSynchronize(f->stream));
@@ -201,7 +154,7 @@ extern "C" int dbgk_fmt_records_device(dbgk_fmt *f, const char *d_text, uint64_t
 		return DBGK_ERR_ARG;
 	for (const char *p : {d_text, d_bases, d_quals}) { // the text the call is about to write
 		const uint8_t *u = (const uint8_t *)p;
-		if (u && f->out && u >= f->out && u < f->out + f->cap_out) return DBGK_ERR_ARG;
+		if (u && f->out && u >= f->out && u < f->out + f->out.cap) return DBGK_ERR_ARG;
 	}
 	HIPCHK(hipSetDevice(f->device));
 	return fmt_run(f, (const uint8_t *)d_text, n_text, d_recs, (const uint8_t *)d_bases, (const uint8_t *)d_quals, d_offsets, n, suffix, suffix_offsets,
@@ -221,16 +174,13 @@ extern "C" int dbgk_fmt_records(dbgk_fmt *f, const char *text, uint64_t n_text, 
 	}
 	HIPCHK(hipSetDevice(f->device));
 	HIPCHK(hipStreamSynchronize(f->stream));
-	uint64_t cap_off = f->in_cap_recs * 8, cap_rec = f->in_cap_recs * sizeof(dbgk_parse_rec);
 	if (n + 1 > f->in_cap_recs || !f->in_off || !f->in_rec) {
 		const uint64_t cap = std::max<uint64_t>(n + 1, 1 << 14);
 		f->in_cap_recs = 0;
-		cap_off = cap_rec = 0;
-		if (fmt_ensure(f->in_off, cap_off, cap * 8, 0) || fmt_ensure(f->in_rec, cap_rec, cap * sizeof(dbgk_parse_rec), 0)) return DBGK_ERR_NOMEM;
+		if (f->in_off.reserve(cap * 8) || f->in_rec.reserve(cap * sizeof(dbgk_parse_rec))) return DBGK_ERR_NOMEM;
 		f->in_cap_recs = cap;
 	}
-	if (fmt_ensure(f->in_text, f->in_cap_text, n_text + 16, 1 << 20) || fmt_ensure(f->in_b, f->in_cap_b, nb + 16, 1 << 20) ||
-	    (quals && fmt_ensure(f->in_q, f->in_cap_q, nb + 16, 1 << 20)))
+	if (f->in_text.reserve(n_text + 16, 1 << 20) || f->in_b.reserve(nb + 16, 1 << 20) || (quals && f->in_q.reserve(nb + 16, 1 << 20)))
 		return DBGK_ERR_NOMEM;
 	if (n_text) HIPCHK(hipMemcpyAsync(f->in_text, text, n_text, hipMemcpyHostToDevice, f->stream));
 	if (nb) HIPCHK(hipMemcpyAsync(f->in_b, bases, nb, hipMemcpyHostToDevice, f->stream));
@@ -240,7 +190,7 @@ extern "C" int dbgk_fmt_records(dbgk_fmt *f, const char *text, uint64_t n_text, 
 		HIPCHK(hipMemcpyAsync(f->in_rec, recs, n * sizeof(dbgk_parse_rec), hipMemcpyHostToDevice, f->stream));
 	}
 	HIPCHK(hipStreamSynchronize(f->stream)); // the caller's buffers are free on return
-	return fmt_run(f, f->in_text, n_text, f->in_rec, f->in_b, quals ? f->in_q : nullptr, f->in_off, n, suffix, suffix_offsets, out);
+	return fmt_run(f, f->in_text, n_text, f->in_rec, f->in_b, quals ? f->in_q.p : nullptr, f->in_off, n, suffix, suffix_offsets, out);
 }
 
 extern "C" int dbgk_fmt_results(dbgk_fmt *f, void *out, uint64_t capacity)
@@ -258,7 +208,7 @@ extern "C" int dbgk_fmt_device(dbgk_fmt *f, const void **d_out, uint64_t *n_out)
 {
 	if (!f || !d_out || !n_out) return DBGK_ERR_ARG;
 	if (!f->have) return DBGK_ERR_STATE;
-	*d_out = f->out;
+	*d_out = f->out.p;
 	*n_out = f->n_out;
 	return DBGK_OK;
 }
@@ -267,7 +217,7 @@ extern "C" int dbgk_parse_recs_device(dbgk_parse *p, const dbgk_parse_rec **d_re
 {
 	if (!p || !d_recs) return DBGK_ERR_ARG;
 	if (!p->out.have) return DBGK_ERR_STATE;
-	*d_recs = p->rec;
+	*d_recs = p->rec.p;
 	return DBGK_OK;
 }
 

@@ -2,25 +2,19 @@
 // launches on the handle's stream -- members, the scan of their sizes, the gather -- and one read-back of the total in between,
 // which sizes the output.  Calls are stateless: nothing but the buffers outlives one.
 
-struct dbgk_gz {
-	int device = 0;
-	int n_cu = 256;
+struct dbgk_gz : StageDev {
 	int level = 1;
-	hipStream_t stream = nullptr;
-	uint8_t *text = nullptr; // dbgk_gz_deflate: the uploaded text
-	uint64_t cap_text = 0;
-	uint32_t *slots = nullptr; // cap_slots slots of kGzSlot bytes
-	uint32_t *sizes = nullptr; // cap_slots + 1
-	uint32_t *tokens = nullptr; // level 2: kGzPiece tokens per slot
-	uint64_t *off = nullptr;
+	DevBuf<uint8_t> text; // dbgk_gz_deflate: the uploaded text
+	DevBuf<uint32_t> slots; // cap_slots slots of kGzSlot bytes
+	DevBuf<uint32_t> sizes; // cap_slots + 1
+	DevBuf<uint32_t> tokens; // level 2: kGzPiece tokens per slot
+	DevBuf<uint64_t> off;
 	uint64_t cap_slots = 0;
-	uint8_t *out = nullptr;
-	uint64_t cap_out = 0;
-	void *tmp = nullptr; // the scan's
-	size_t tmp_bytes = 0;
-	uint32_t *x8 = nullptr;
-	unsigned long long *ctr = nullptr;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // members, scan + gather
+	DevBuf<uint8_t> out;
+	ScanTmp tmp; // the scan's
+	DevBuf<uint32_t> x8;
+	DevBuf<unsigned long long> ctr;
+	StageEvents<4> ev; // members, scan + gather
 	bool have = false;
 	dbgk_gz_info info{};
 	dbgk_gz_timing timing{};
@@ -29,13 +23,7 @@ struct dbgk_gz {
 extern "C" int dbgk_gz_destroy(dbgk_gz *z)
 {
 	if (!z) return DBGK_ERR_ARG;
-	(void)hipSetDevice(z->device);
-	if (z->stream) (void)hipStreamSynchronize(z->stream);
-	(void)hipFree(z->text); (void)hipFree(z->slots); (void)hipFree(z->sizes); (void)hipFree(z->off); (void)hipFree(z->out); (void)hipFree(z->tmp);
-	(void)hipFree(z->x8); (void)hipFree(z->ctr); (void)hipFree(z->tokens);
-	for (hipEvent_t e : z->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (z->stream) (void)hipStreamDestroy(z->stream);
+	stage_drain(z->device, z->stream);
 	delete z;
 	return DBGK_OK;
 }
@@ -52,28 +40,12 @@ extern "C" int dbgk_gz_create(int level, dbgk_gz **out)
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
 	if (level < 0 || level > DBGK_GZ_MAX_LEVEL) return DBGK_ERR_ARG;
-	int n_dev = 0, device = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
-	if (hipGetDevice(&device) != hipSuccess) device = 0;
 	dbgk_gz *z = new (std::nothrow) dbgk_gz;
 	if (!z) return DBGK_ERR_NOMEM;
-	z->device = device;
 	z->level = level;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) z->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 4; ++i)
-		if (hipEventCreate(&z->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && (hipMalloc(&z->x8, 16 * 4) != hipSuccess || hipMalloc(&z->ctr, gzk::GC_COUNT * 8) != hipSuccess)) rc = DBGK_ERR_NOMEM;
+	int rc = stage_open(*z, kStageCurrentDevice);
+	if (!rc) rc = z->ev.create();
+	if (!rc && (z->x8.reserve(16 * 4) || z->ctr.reserve(gzk::GC_COUNT * 8))) rc = DBGK_ERR_NOMEM;
 	if (!rc) {
 		const gzf::GzPowers t = gzf::gz_powers();
 		if (hipMemcpy(z->x8, t.x8, 16 * 4, hipMemcpyHostToDevice) != hipSuccess) rc = DBGK_ERR_HIP;
@@ -91,12 +63,10 @@ extern "C" int dbgk_gz_create(int level, dbgk_gz **out)
 static int gz_ensure_slots(dbgk_gz *z, uint64_t n_slots)
 {
 	if (n_slots <= z->cap_slots && z->slots) return DBGK_OK;
-	(void)hipFree(z->slots); (void)hipFree(z->sizes); (void)hipFree(z->off); (void)hipFree(z->tokens);
-	z->slots = z->sizes = z->tokens = nullptr; z->off = nullptr;
 	z->cap_slots = 0;
 	const uint64_t cap = std::max<uint64_t>(n_slots, 64);
-	if (hipMalloc(&z->slots, cap * gzf::kGzSlot) != hipSuccess || hipMalloc(&z->sizes, (cap + 1) * 4) != hipSuccess ||
-	    hipMalloc(&z->off, (cap + 1) * 8) != hipSuccess || (z->level == 2 && hipMalloc(&z->tokens, cap * gzf::kGzPiece * 4) != hipSuccess))
+	if (z->slots.reserve(cap * gzf::kGzSlot) || z->sizes.reserve((cap + 1) * 4) || z->off.reserve((cap + 1) * 8) ||
+	    (z->level == 2 && z->tokens.reserve(cap * gzf::kGzPiece * 4)))
 		return DBGK_ERR_NOMEM;
 	z->cap_slots = cap;
 	return DBGK_OK;
@@ -121,19 +91,11 @@ static int gz_run(dbgk_gz *z, const uint8_t *text, uint64_t n_bytes, bool last, 
 		                   z->tokens, z->ctr);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(z->ev[1], z->stream));
-		size_t need = 0;
-		if (dbgk_internal_scan_lengths(nullptr, &need, z->sizes, z->off, (uint64_t)n_slots + 1, z->stream)) return DBGK_ERR_HIP;
-		if (need > z->tmp_bytes) {
-			HIPCHK(hipStreamSynchronize(z->stream));
-			(void)hipFree(z->tmp);
-			z->tmp = nullptr;
-			z->tmp_bytes = 0;
-			if (hipMalloc(&z->tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-			z->tmp_bytes = need;
-		}
-		size_t bytes = z->tmp_bytes;
+		rc = stage_scan_reserve(z->tmp, z->stream, z->sizes, z->off, (uint64_t)n_slots + 1);
+		if (rc) return rc;
 		HIPCHK(hipEventRecord(z->ev[2], z->stream));
-		if (dbgk_internal_scan_lengths(z->tmp, &bytes, z->sizes, z->off, (uint64_t)n_slots + 1, z->stream)) return DBGK_ERR_HIP;
+		rc = stage_scan(z->tmp, z->stream, z->sizes, z->off, (uint64_t)n_slots + 1);
+		if (rc) return rc;
 		uint64_t total = 0;
 		unsigned long long ctr[gzk::GC_COUNT] = {0};
 		HIPCHK(hipMemcpyAsync(&total, z->off + n_slots, 8, hipMemcpyDeviceToHost, z->stream));
@@ -143,16 +105,9 @@ static int gz_run(dbgk_gz *z, const uint8_t *text, uint64_t n_bytes, bool last, 
 			g_last_error = "member sizes exceed their slots";
 			return DBGK_ERR_STATE;
 		}
-		if (total + 16 > z->cap_out) {
-			(void)hipFree(z->out);
-			z->out = nullptr;
-			z->cap_out = 0;
-			const uint64_t cap = std::max<uint64_t>(total + 16, 1 << 20);
-			if (hipMalloc(&z->out, cap) != hipSuccess) return DBGK_ERR_NOMEM;
-			z->cap_out = cap;
-		}
+		if (z->out.reserve(total + 16, 1 << 20)) return DBGK_ERR_NOMEM;
 		hipLaunchKernelGGL(gzk::k_gz_gather, dim3(std::min<uint32_t>(n_slots, (uint32_t)z->n_cu * 16)), dim3(gzk::kGzBlock), 0, z->stream,
-		                   reinterpret_cast<const uint8_t *>(z->slots), (const uint64_t *)z->off, n_slots, z->out);
+		                   reinterpret_cast<const uint8_t *>(z->slots.p), (const uint64_t *)z->off, n_slots, z->out);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(z->ev[3], z->stream));
 		HIPCHK(hipStreamSynchronize(z->stream));
@@ -186,7 +141,7 @@ extern "C" int dbgk_gz_deflate_device(dbgk_gz *z, const void *d_text, uint64_t n
 {
 	if (!z || n_bytes >= (1ull << 31) || (n_bytes && !d_text) || ((uintptr_t)d_text & 15u)) return DBGK_ERR_ARG;
 	const uint8_t *u = (const uint8_t *)d_text;
-	if (u && z->out && u + n_bytes > z->out && u < z->out + z->cap_out) return DBGK_ERR_ARG; // the output the call is about to write
+	if (u && z->out && u + n_bytes > z->out && u < z->out + z->out.cap) return DBGK_ERR_ARG; // the output the call is about to write
 	HIPCHK(hipSetDevice(z->device));
 	return gz_run(z, u, n_bytes, last != 0, info);
 }
@@ -196,14 +151,9 @@ extern "C" int dbgk_gz_deflate(dbgk_gz *z, const void *text, uint64_t n_bytes, i
 	if (!z || n_bytes >= (1ull << 31) || (n_bytes && !text)) return DBGK_ERR_ARG;
 	z->have = false;
 	HIPCHK(hipSetDevice(z->device));
-	if (n_bytes + 16 > z->cap_text) {
+	if (n_bytes + 16 > z->text.cap) {
 		HIPCHK(hipStreamSynchronize(z->stream));
-		(void)hipFree(z->text);
-		z->text = nullptr;
-		z->cap_text = 0;
-		const uint64_t cap = std::max<uint64_t>(n_bytes + 16, 1 << 20);
-		if (hipMalloc(&z->text, cap) != hipSuccess) return DBGK_ERR_NOMEM;
-		z->cap_text = cap;
+		if (z->text.reserve(n_bytes + 16, 1 << 20)) return DBGK_ERR_NOMEM;
 	}
 	if (n_bytes) HIPCHK(hipMemcpyAsync(z->text, text, n_bytes, hipMemcpyHostToDevice, z->stream));
 	HIPCHK(hipStreamSynchronize(z->stream)); // the caller's buffer is free on return
@@ -225,7 +175,7 @@ extern "C" int dbgk_gz_device(dbgk_gz *z, const void **d_out, uint64_t *n_out)
 {
 	if (!z || !d_out || !n_out) return DBGK_ERR_ARG;
 	if (!z->have) return DBGK_ERR_STATE;
-	*d_out = z->info.out_bytes ? z->out : nullptr;
+	*d_out = z->info.out_bytes ? z->out.p : nullptr;
 	*n_out = z->info.out_bytes;
 	return DBGK_OK;
 }

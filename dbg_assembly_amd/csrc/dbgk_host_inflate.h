@@ -2,24 +2,19 @@
 // call: the member table goes up, k_inf_sizes and the scan of ISIZE give every member its place, one read-back of the total sizes the
 // output, then decode and resolve once per round of kInfRound members.  Calls are stateless: nothing but the buffers outlives one.
 
-struct dbgk_inf {
-	int device = 0;
+struct dbgk_inf : StageDev {
 	uint64_t max_out = 0;
-	hipStream_t stream = nullptr;
-	uint8_t *gz = nullptr; // dbgk_inf_inflate: the uploaded members
-	uint64_t cap_gz = 0;
-	uint64_t *off = nullptr, *place = nullptr; // cap_members + 1 each
-	uint32_t *isize = nullptr, *crc = nullptr, *status = nullptr;
+	DevBuf<uint8_t> gz; // dbgk_inf_inflate: the uploaded members
+	DevBuf<uint64_t> off, place; // cap_members + 1 each
+	DevBuf<uint32_t> isize, crc, status;
 	uint64_t cap_members = 0;
-	uint32_t *tokens = nullptr, *n_tok = nullptr; // cap_round slots of kGzPiece tokens
+	DevBuf<uint32_t> tokens, n_tok; // cap_round slots of kGzPiece tokens
 	uint64_t cap_round = 0;
-	uint8_t *out = nullptr;
-	uint64_t cap_out = 0;
-	void *tmp = nullptr; // the scan's
-	size_t tmp_bytes = 0;
-	uint32_t *x8 = nullptr;
-	unsigned long long *ctr = nullptr;
-	hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+	DevBuf<uint8_t> out;
+	ScanTmp tmp; // the scan's
+	DevBuf<uint32_t> x8;
+	DevBuf<unsigned long long> ctr;
+	StageEvents<3> ev;
 	bool have = false;
 	dbgk_inf_info info{};
 	dbgk_inf_timing timing{};
@@ -32,13 +27,7 @@ static_assert(DBGK_INF_ROUND == infk::kInfRound && DBGK_INF_FRAME == inf::R_FRAM
 extern "C" int dbgk_inf_destroy(dbgk_inf *z)
 {
 	if (!z) return DBGK_ERR_ARG;
-	(void)hipSetDevice(z->device);
-	if (z->stream) (void)hipStreamSynchronize(z->stream);
-	(void)hipFree(z->gz); (void)hipFree(z->off); (void)hipFree(z->place); (void)hipFree(z->isize); (void)hipFree(z->crc); (void)hipFree(z->status);
-	(void)hipFree(z->tokens); (void)hipFree(z->n_tok); (void)hipFree(z->out); (void)hipFree(z->tmp); (void)hipFree(z->x8); (void)hipFree(z->ctr);
-	for (hipEvent_t e : z->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (z->stream) (void)hipStreamDestroy(z->stream);
+	stage_drain(z->device, z->stream);
 	delete z;
 	return DBGK_OK;
 }
@@ -56,27 +45,12 @@ extern "C" int dbgk_inf_create(uint64_t max_out_bytes, dbgk_inf **out)
 	*out = nullptr;
 	const uint64_t top = (1ull << 31) - 65536;
 	if (max_out_bytes > top) return DBGK_ERR_ARG;
-	int n_dev = 0, device = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
-	if (hipGetDevice(&device) != hipSuccess) device = 0;
 	dbgk_inf *z = new (std::nothrow) dbgk_inf;
 	if (!z) return DBGK_ERR_NOMEM;
-	z->device = device;
 	z->max_out = max_out_bytes ? max_out_bytes : top;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc && hipStreamCreateWithFlags(&z->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 3; ++i)
-		if (hipEventCreate(&z->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && (hipMalloc(&z->x8, 16 * 4) != hipSuccess || hipMalloc(&z->ctr, infk::IC_COUNT * 8) != hipSuccess)) rc = DBGK_ERR_NOMEM;
+	int rc = stage_open(*z, kStageCurrentDevice);
+	if (!rc) rc = z->ev.create();
+	if (!rc && (z->x8.reserve(16 * 4) || z->ctr.reserve(infk::IC_COUNT * 8))) rc = DBGK_ERR_NOMEM;
 	if (!rc) {
 		const gzf::GzPowers t = gzf::gz_powers();
 		if (hipMemcpy(z->x8, t.x8, 16 * 4, hipMemcpyHostToDevice) != hipSuccess) rc = DBGK_ERR_HIP;
@@ -94,22 +68,18 @@ extern "C" int dbgk_inf_create(uint64_t max_out_bytes, dbgk_inf **out)
 static int inf_ensure_members(dbgk_inf *z, uint64_t n)
 {
 	if (n > z->cap_members || !z->off) {
-		(void)hipFree(z->off); (void)hipFree(z->place); (void)hipFree(z->isize); (void)hipFree(z->crc); (void)hipFree(z->status);
-		z->off = z->place = nullptr; z->isize = z->crc = z->status = nullptr;
 		z->cap_members = 0;
 		const uint64_t cap = std::max<uint64_t>(n, 1024);
-		if (hipMalloc(&z->off, (cap + 1) * 8) != hipSuccess || hipMalloc(&z->place, (cap + 1) * 8) != hipSuccess || hipMalloc(&z->isize, (cap + 1) * 4) != hipSuccess ||
-		    hipMalloc(&z->crc, cap * 4) != hipSuccess || hipMalloc(&z->status, cap * 4) != hipSuccess)
+		if (z->off.reserve((cap + 1) * 8) || z->place.reserve((cap + 1) * 8) || z->isize.reserve((cap + 1) * 4) || z->crc.reserve(cap * 4) ||
+		    z->status.reserve(cap * 4))
 			return DBGK_ERR_NOMEM;
 		z->cap_members = cap;
 	}
 	const uint64_t round = std::min<uint64_t>(n, infk::kInfRound);
 	if (round > z->cap_round || !z->tokens) {
-		(void)hipFree(z->tokens); (void)hipFree(z->n_tok);
-		z->tokens = z->n_tok = nullptr;
 		z->cap_round = 0;
 		const uint64_t cap = std::min<uint64_t>(std::max<uint64_t>(round, 64), infk::kInfRound);
-		if (hipMalloc(&z->tokens, cap * gzf::kGzPiece * 4) != hipSuccess || hipMalloc(&z->n_tok, cap * 4) != hipSuccess) return DBGK_ERR_NOMEM;
+		if (z->tokens.reserve(cap * gzf::kGzPiece * 4) || z->n_tok.reserve(cap * 4)) return DBGK_ERR_NOMEM;
 		z->cap_round = cap;
 	}
 	return DBGK_OK;
@@ -131,22 +101,14 @@ static int inf_run(dbgk_inf *z, const uint8_t *gz, const uint64_t *off, uint64_t
 		const uint32_t nm = (uint32_t)n;
 		HIPCHK(hipMemcpyAsync(z->off, off, (n + 1) * 8, hipMemcpyHostToDevice, z->stream));
 		HIPCHK(hipMemsetAsync(z->ctr, 0, infk::IC_COUNT * 8, z->stream));
-		size_t need = 0;
-		if (dbgk_internal_scan_lengths(nullptr, &need, z->isize, z->place, n + 1, z->stream)) return DBGK_ERR_HIP;
-		if (need > z->tmp_bytes) {
-			HIPCHK(hipStreamSynchronize(z->stream));
-			(void)hipFree(z->tmp);
-			z->tmp = nullptr;
-			z->tmp_bytes = 0;
-			if (hipMalloc(&z->tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-			z->tmp_bytes = need;
-		}
+		rc = stage_scan_reserve(z->tmp, z->stream, z->isize, z->place, n + 1);
+		if (rc) return rc;
 		HIPCHK(hipEventRecord(z->ev[0], z->stream));
 		hipLaunchKernelGGL(infk::k_inf_sizes, dim3(nm / infk::kInfBlock + 1), dim3(infk::kInfBlock), 0, z->stream, gz, (const uint64_t *)z->off, nm, z->isize, z->crc,
 		                   z->status, z->ctr);
 		HIPCHK(hipGetLastError());
-		size_t bytes = z->tmp_bytes;
-		if (dbgk_internal_scan_lengths(z->tmp, &bytes, z->isize, z->place, n + 1, z->stream)) return DBGK_ERR_HIP;
+		rc = stage_scan(z->tmp, z->stream, z->isize, z->place, n + 1);
+		if (rc) return rc;
 		HIPCHK(hipEventRecord(z->ev[1], z->stream));
 		uint64_t total = 0;
 		HIPCHK(hipMemcpyAsync(&total, z->place + n, 8, hipMemcpyDeviceToHost, z->stream));
@@ -158,14 +120,7 @@ static int inf_run(dbgk_inf *z, const uint8_t *gz, const uint64_t *off, uint64_t
 		float ms = 0;
 		HIPCHK(hipEventElapsedTime(&ms, z->ev[0], z->ev[1]));
 		T.ms_scan = ms;
-		if (total + 16 > z->cap_out) {
-			(void)hipFree(z->out);
-			z->out = nullptr;
-			z->cap_out = 0;
-			const uint64_t cap = std::max<uint64_t>(total + 16, 1 << 20);
-			if (hipMalloc(&z->out, cap) != hipSuccess) return DBGK_ERR_NOMEM;
-			z->cap_out = cap;
-		}
+		if (z->out.reserve(total + 16, 1 << 20)) return DBGK_ERR_NOMEM;
 		for (uint32_t r0 = 0; r0 < nm; r0 += infk::kInfRound) {
 			const uint32_t nr = std::min<uint32_t>(nm - r0, infk::kInfRound);
 			HIPCHK(hipEventRecord(z->ev[0], z->stream));
@@ -218,7 +173,7 @@ extern "C" int dbgk_inf_inflate_device(dbgk_inf *z, const void *d_gz, uint64_t n
 		if (member_offsets[m + 1] < member_offsets[m]) return DBGK_ERR_ARG;
 	if (member_offsets[n_members] > n_bytes) return DBGK_ERR_ARG;
 	const uint8_t *u = (const uint8_t *)d_gz;
-	if (u && z->out && u + n_bytes > z->out && u < z->out + z->cap_out) return DBGK_ERR_ARG; // the output the call is about to write
+	if (u && z->out && u + n_bytes > z->out && u < z->out + z->out.cap) return DBGK_ERR_ARG; // the output the call is about to write
 	HIPCHK(hipSetDevice(z->device));
 	return inf_run(z, u, member_offsets, n_members, info);
 }
@@ -250,14 +205,9 @@ extern "C" int dbgk_inf_inflate(dbgk_inf *z, const void *gz, uint64_t n_bytes, i
 	}
 	const uint64_t n = off.size() - 1, used = off[n];
 	HIPCHK(hipSetDevice(z->device));
-	if (used + 16 > z->cap_gz) {
+	if (used + 16 > z->gz.cap) {
 		HIPCHK(hipStreamSynchronize(z->stream));
-		(void)hipFree(z->gz);
-		z->gz = nullptr;
-		z->cap_gz = 0;
-		const uint64_t cap = std::max<uint64_t>(used + 16, 1 << 20);
-		if (hipMalloc(&z->gz, cap) != hipSuccess) return DBGK_ERR_NOMEM;
-		z->cap_gz = cap;
+		if (z->gz.reserve(used + 16, 1 << 20)) return DBGK_ERR_NOMEM;
 	}
 	if (used) HIPCHK(hipMemcpyAsync(z->gz, gz, used, hipMemcpyHostToDevice, z->stream));
 	HIPCHK(hipStreamSynchronize(z->stream)); // the caller's buffer is free on return
@@ -279,7 +229,7 @@ extern "C" int dbgk_inf_device(dbgk_inf *z, const void **d_text, uint64_t *n_byt
 {
 	if (!z || !d_text || !n_bytes) return DBGK_ERR_ARG;
 	if (!z->have) return DBGK_ERR_STATE;
-	*d_text = z->info.out_bytes ? z->out : nullptr;
+	*d_text = z->info.out_bytes ? z->out.p : nullptr;
 	*n_bytes = z->info.out_bytes;
 	return DBGK_OK;
 }

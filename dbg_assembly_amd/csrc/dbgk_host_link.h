@@ -1,22 +1,18 @@
 // LINK: host side of link_scaffold on the GPU (include/dbgk.h, LINK section; kernels in dbgk_link.h).  The device builds the link
 // table; the reference's clean-up passes and its walk are serial and order-dependent, O(contigs + links), and run here in its order.
 
-struct dbgk_link {
-	int device = 0;
-	int n_cu = 256;
-	hipStream_t stream = nullptr;
+struct dbgk_link : StageDev {
 	dbgk_link_params p{};
 	// contigs
 	std::vector<uint32_t> lens;
-	uint32_t *d_lens = nullptr;
+	DevBuf<uint32_t> d_lens;
 	bool contigs_set = false;
 	// the entries of every batch so far, two per record, in record order; sorted in place by dbgk_link_build
-	uint64_t *d_keys = nullptr, *d_vals = nullptr;
+	DevBuf<uint64_t> d_keys, d_vals;
 	uint64_t n_entries = 0, cap_entries = 0;
-	void *d_in = nullptr;       // staging of one batch of records or hits
-	uint64_t cap_in = 0;
-	linkk::Counters *d_ctr = nullptr;
-	hipEvent_t ev[2] = {nullptr, nullptr};
+	DevBuf<uint8_t> d_in;       // staging of one batch of records or hits
+	DevBuf<linkk::Counters> d_ctr;
+	StageEvents<2> ev;
 	bool built = false;
 	// the table on the host: links of node i are links[first[i] .. first[i + 1]) in chain order
 	std::vector<uint64_t> first;
@@ -44,27 +40,12 @@ extern "C" int dbgk_link_create(const dbgk_link_params *p, int device, dbgk_link
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
 	if (!p || device < 0 || (p->mate_pair != 0 && p->mate_pair != 1) || p->pair_num_cut < 0 || p->insert_size <= 0) return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_link *l = new (std::nothrow) dbgk_link;
 	if (!l) return DBGK_ERR_NOMEM;
-	l->device = device;
 	l->p = *p;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) l->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 2; ++i)
-		if (hipEventCreate(&l->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && hipMalloc(&l->d_ctr, sizeof(linkk::Counters)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	int rc = stage_open(*l, device);
+	if (!rc) rc = l->ev.create();
+	if (!rc) rc = l->d_ctr.reserve(sizeof(linkk::Counters));
 	if (!rc && hipMemsetAsync(l->d_ctr, 0, sizeof(linkk::Counters), l->stream) != hipSuccess) rc = DBGK_ERR_HIP;
 	if (rc) {
 		dbgk_link_destroy(l);
@@ -77,12 +58,7 @@ extern "C" int dbgk_link_create(const dbgk_link_params *p, int device, dbgk_link
 extern "C" int dbgk_link_destroy(dbgk_link *l)
 {
 	if (!l) return DBGK_ERR_ARG;
-	(void)hipSetDevice(l->device);
-	if (l->stream) (void)hipStreamSynchronize(l->stream);
-	(void)hipFree(l->d_lens); (void)hipFree(l->d_keys); (void)hipFree(l->d_vals); (void)hipFree(l->d_in); (void)hipFree(l->d_ctr);
-	for (auto &e : l->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (l->stream) (void)hipStreamDestroy(l->stream);
+	stage_drain(l->device, l->stream);
 	delete l;
 	return DBGK_OK;
 }
@@ -95,10 +71,9 @@ extern "C" int dbgk_link_set_contigs(dbgk_link *l, const uint32_t *lengths, uint
 		if (lengths[i] >= (1u << 31)) return DBGK_ERR_ARG;
 	if (l->n_entries || l->built) return DBGK_ERR_STATE;
 	HIPCHK(hipSetDevice(l->device));
-	(void)hipFree(l->d_lens);
-	l->d_lens = nullptr;
 	l->contigs_set = false;
-	if (hipMalloc(&l->d_lens, (n_contigs + 1) * 4) != hipSuccess) return DBGK_ERR_NOMEM;
+	l->d_lens.release();
+	if (l->d_lens.reserve((n_contigs + 1) * 4)) return DBGK_ERR_NOMEM;
 	if (n_contigs) HIPCHK(hipMemcpyAsync(l->d_lens, lengths, n_contigs * 4, hipMemcpyHostToDevice, l->stream));
 	HIPCHK(hipStreamSynchronize(l->stream));
 	l->lens.assign(lengths, lengths + n_contigs);
@@ -111,29 +86,18 @@ static int link_reserve(dbgk_link *l, uint64_t n_new, uint64_t in_bytes)
 {
 	if (l->n_entries + n_new > l->cap_entries) {
 		const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(l->n_entries + n_new, 2 * l->cap_entries), 1 << 16);
-		uint64_t *k = nullptr, *v = nullptr;
-		if (hipMalloc(&k, cap * 8) != hipSuccess || hipMalloc(&v, cap * 8) != hipSuccess) {
-			(void)hipFree(k);
-			return DBGK_ERR_NOMEM;
-		}
+		DevBuf<uint64_t> k, v;
+		if (k.reserve(cap * 8) || v.reserve(cap * 8)) return DBGK_ERR_NOMEM;
 		if (l->n_entries) {
 			HIPCHK(hipMemcpyAsync(k, l->d_keys, l->n_entries * 8, hipMemcpyDeviceToDevice, l->stream));
 			HIPCHK(hipMemcpyAsync(v, l->d_vals, l->n_entries * 8, hipMemcpyDeviceToDevice, l->stream));
 			HIPCHK(hipStreamSynchronize(l->stream));
 		}
-		(void)hipFree(l->d_keys); (void)hipFree(l->d_vals);
-		l->d_keys = k;
-		l->d_vals = v;
+		l->d_keys.take(k);
+		l->d_vals.take(v);
 		l->cap_entries = cap;
 	}
-	if (in_bytes > l->cap_in) {
-		(void)hipFree(l->d_in);
-		l->d_in = nullptr;
-		l->cap_in = 0;
-		const uint64_t cap = std::max<uint64_t>(in_bytes, 1 << 20);
-		if (hipMalloc(&l->d_in, cap) != hipSuccess) return DBGK_ERR_NOMEM;
-		l->cap_in = cap;
-	}
+	if (l->d_in.reserve(in_bytes, 1 << 20)) return DBGK_ERR_NOMEM;
 	return DBGK_OK;
 }
 
@@ -153,16 +117,16 @@ static int link_add(dbgk_link *l, const void *a, const void *b, uint64_t n, bool
 	int rc = link_reserve(l, 2 * n, from_hits ? 2 * bytes : bytes);
 	if (rc) return rc;
 	HIPCHK(hipMemcpyAsync(l->d_in, a, bytes, hipMemcpyHostToDevice, l->stream));
-	if (from_hits) HIPCHK(hipMemcpyAsync(static_cast<char *>(l->d_in) + bytes, b, bytes, hipMemcpyHostToDevice, l->stream));
+	if (from_hits) HIPCHK(hipMemcpyAsync(l->d_in + bytes, b, bytes, hipMemcpyHostToDevice, l->stream));
 	HIPCHK(hipEventRecord(l->ev[0], l->stream));
 	const uint32_t nc = (uint32_t)l->lens.size();
 	if (from_hits) {
-		const linkk::Hit *h1 = static_cast<const linkk::Hit *>(l->d_in);
+		const linkk::Hit *h1 = reinterpret_cast<const linkk::Hit *>(l->d_in.p);
 		hipLaunchKernelGGL(linkk::k_link_orient<true>, dim3(link_grid(l, n)), dim3(linkk::kLinkThreads), 0, l->stream, (const linkk::Pair *)nullptr,
 		                   h1, h1 + n, n, l->d_lens, nc, l->p.mate_pair, l->p.insert_size, l->n_entries, l->d_keys, l->d_vals, l->d_ctr);
 	} else {
 		hipLaunchKernelGGL(linkk::k_link_orient<false>, dim3(link_grid(l, n)), dim3(linkk::kLinkThreads), 0, l->stream,
-		                   static_cast<const linkk::Pair *>(l->d_in), (const linkk::Hit *)nullptr, (const linkk::Hit *)nullptr, n, l->d_lens, nc,
+		                   reinterpret_cast<const linkk::Pair *>(l->d_in.p), (const linkk::Hit *)nullptr, (const linkk::Hit *)nullptr, n, l->d_lens, nc,
 		                   l->p.mate_pair, l->p.insert_size, l->n_entries, l->d_keys, l->d_vals, l->d_ctr);
 	}
 	HIPCHK(hipGetLastError());
@@ -213,16 +177,11 @@ extern "C" int dbgk_link_build(dbgk_link *l)
 		// stable, so the entries of one (source, target) stay in record order; the dropped entries end up behind position n_kept
 		if (int rc = dbgk_internal_sort_pairs(l->d_keys, l->d_vals, n, l->stream)) return rc;
 		l->stats.ms_sort += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-		uint64_t *d_okeys = nullptr, *d_ovals = nullptr;
-		linkk::Entry *d_slots = nullptr, *d_out = nullptr;
-		uint32_t *d_src = nullptr;
-		auto release = [&]() { (void)hipFree(d_okeys); (void)hipFree(d_ovals); (void)hipFree(d_slots); (void)hipFree(d_out); (void)hipFree(d_src); };
+		DevBuf<uint64_t> d_okeys, d_ovals;
+		DevBuf<linkk::Entry> d_slots, d_out;
+		DevBuf<uint32_t> d_src;
 		// at most one link per kept entry
-		if (hipMalloc(&d_okeys, n_kept * 8) != hipSuccess || hipMalloc(&d_ovals, n_kept * 8) != hipSuccess ||
-		    hipMalloc(&d_slots, n_kept * 16) != hipSuccess) {
-			release();
-			return DBGK_ERR_NOMEM;
-		}
+		if (d_okeys.reserve(n_kept * 8) || d_ovals.reserve(n_kept * 8) || d_slots.reserve(n_kept * 16)) return DBGK_ERR_NOMEM;
 		int rc = DBGK_OK;
 		auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, "dbgk_link_build", __LINE__); };
 		step(hipEventRecord(l->ev[0], l->stream));
@@ -241,7 +200,7 @@ extern "C" int dbgk_link_build(dbgk_link *l)
 			t0 = std::chrono::steady_clock::now();
 			if (dbgk_internal_sort_pairs(d_okeys, d_ovals, n_links, l->stream)) rc = DBGK_ERR_HIP;
 			l->stats.ms_sort += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-			if (!rc && (hipMalloc(&d_out, n_links * 16) != hipSuccess || hipMalloc(&d_src, n_links * 4) != hipSuccess)) rc = DBGK_ERR_NOMEM;
+			if (!rc && (d_out.reserve(n_links * 16) || d_src.reserve(n_links * 4))) rc = DBGK_ERR_NOMEM;
 			std::vector<uint32_t> src(n_links);
 			l->links.resize(n_links);
 			if (!rc) {
@@ -261,7 +220,6 @@ extern "C" int dbgk_link_build(dbgk_link *l)
 				for (uint64_t i = 0; i < n_nodes; ++i) l->first[i + 1] += l->first[i];
 			}
 		}
-		release();
 		if (rc) return rc;
 	}
 	l->stats.links = n_links;
@@ -615,16 +573,11 @@ static int link_run_emit(dbgk_link *l, const char *who, const char *bases, const
 {
 	const uint64_t nb = offsets[n_contigs], total = item_off.back();
 	HIPCHK(hipSetDevice(l->device));
-	uint8_t *d_bases = nullptr, *d_out = nullptr;
-	uint64_t *d_coff = nullptr, *d_ioff = nullptr;
-	void *d_items = nullptr;
-	auto release = [&]() { (void)hipFree(d_bases); (void)hipFree(d_out); (void)hipFree(d_coff); (void)hipFree(d_ioff); (void)hipFree(d_items); };
-	if (hipMalloc(&d_bases, nb + 16) != hipSuccess || hipMalloc(&d_out, ((total + 7) & ~7ull) + 16) != hipSuccess ||
-	    (with_contig_off && hipMalloc(&d_coff, (n_contigs + 1) * 8) != hipSuccess) || hipMalloc(&d_ioff, item_off.size() * 8) != hipSuccess ||
-	    hipMalloc(&d_items, item_bytes) != hipSuccess) {
-		release();
+	DevBuf<uint8_t> d_bases, d_out, d_items;
+	DevBuf<uint64_t> d_coff, d_ioff;
+	if (d_bases.reserve(nb + 16) || d_out.reserve(((total + 7) & ~7ull) + 16) || (with_contig_off && d_coff.reserve((n_contigs + 1) * 8)) ||
+	    d_ioff.reserve(item_off.size() * 8) || d_items.reserve(item_bytes))
 		return DBGK_ERR_NOMEM;
-	}
 	int rc = DBGK_OK;
 	auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, who, __LINE__); };
 	if (nb) step(hipMemcpyAsync(d_bases, bases, nb, hipMemcpyHostToDevice, l->stream));
@@ -640,7 +593,6 @@ static int link_run_emit(dbgk_link *l, const char *who, const char *bases, const
 	step(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, l->stream));
 	step(hipStreamSynchronize(l->stream));
 	if (!rc) step(hipEventElapsedTime(ms, l->ev[0], l->ev[1]));
-	release();
 	return rc;
 }
 

@@ -1,28 +1,24 @@
 // MAP: host side of map_reads / map_pair on the GPU (include/dbgk.h, MAP section; kernels in dbgk_map.h)
 
-struct dbgk_map {
+struct dbgk_map : StageDev {
 	dbgk_map_params p{};
-	int device = 0;
-	int n_cu = 256;
 	uint32_t chunk0 = 4;          // first chunk of the seed scan's ramp (dbgk_map_set_ramp; profiles/map_measure.json)
-	hipStream_t stream = nullptr;
 	dbgk_handle *index = nullptr; // the finalized SEEDIDX handle of the contigs
-	uint8_t *d_ctg = nullptr;     // contig text as written
-	uint64_t *d_ctg_off = nullptr;
+	DevBuf<uint8_t> d_ctg;        // contig text as written
+	DevBuf<uint64_t> d_ctg_off;
 	uint64_t n_contigs = 0;
 	// identity: accept[align_len] = the largest mis_match the reference's float test lets through, -1 = none
 	std::vector<int32_t> accept;
-	int32_t *d_accept = nullptr;
-	uint64_t cap_accept = 0;
+	DevBuf<int32_t> d_accept;
 	// batch buffers, grown on demand
-	uint8_t *d_seq = nullptr;
-	uint64_t *d_off = nullptr;
-	mapk::Hit *d_hits = nullptr;
-	uint32_t *d_long = nullptr;
-	mapk::MapCounters *d_ctr = nullptr;
-	unsigned long long *d_chk = nullptr; // dbgk_map_reads_device: what k_map_check_batch found
+	DevBuf<uint8_t> d_seq;
+	DevBuf<uint64_t> d_off;
+	DevBuf<mapk::Hit> d_hits;
+	DevBuf<uint32_t> d_long;
+	DevBuf<mapk::MapCounters> d_ctr;
+	DevBuf<unsigned long long> d_chk; // dbgk_map_reads_device: what k_map_check_batch found
 	uint64_t cap_bytes = 0, cap_reads = 0;
-	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+	StageEvents<4> ev;
 	dbgk_map_stats last{};
 };
 
@@ -52,20 +48,12 @@ static bool map_accepts(int mis_match, int align_len, double min_identity)
 	return !(identity < min_identity);
 }
 
-static void map_free_batch(dbgk_map *m)
-{
-	(void)hipFree(m->d_seq); (void)hipFree(m->d_off); (void)hipFree(m->d_hits); (void)hipFree(m->d_long);
-	m->d_seq = nullptr; m->d_off = nullptr; m->d_hits = nullptr; m->d_long = nullptr;
-	m->cap_bytes = m->cap_reads = 0;
-}
-
 static void map_free_contigs(dbgk_map *m)
 {
 	if (m->index) (void)dbgk_destroy(m->index);
 	m->index = nullptr;
 	(void)hipSetDevice(m->device);
-	(void)hipFree(m->d_ctg); (void)hipFree(m->d_ctg_off);
-	m->d_ctg = nullptr; m->d_ctg_off = nullptr;
+	m->d_ctg.release(); m->d_ctg_off.release();
 	m->n_contigs = 0;
 }
 
@@ -76,27 +64,12 @@ extern "C" int dbgk_map_create(const dbgk_map_params *p, int device, dbgk_map **
 	if (p->k < 1 || p->k > 31 || p->seed_kmers < 1 || p->seed_kmers > (1 << 29) || p->min_read_len < 0 ||
 	    (p->second_alignment != 0 && p->second_alignment != 1) || p->min_identity != p->min_identity || device < 0)
 		return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_map *m = new (std::nothrow) dbgk_map;
 	if (!m) return DBGK_ERR_NOMEM;
 	m->p = *p;
-	m->device = device;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) m->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
-	for (int i = 0; !rc && i < 4; ++i)
-		if (hipEventCreate(&m->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && hipMalloc(&m->d_ctr, sizeof(mapk::MapCounters)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	int rc = stage_open(*m, device);
+	if (!rc) rc = m->ev.create();
+	if (!rc) rc = m->d_ctr.reserve(sizeof(mapk::MapCounters));
 	if (rc) {
 		dbgk_map_destroy(m);
 		return rc;
@@ -108,16 +81,8 @@ extern "C" int dbgk_map_create(const dbgk_map_params *p, int device, dbgk_map **
 extern "C" int dbgk_map_destroy(dbgk_map *m)
 {
 	if (!m) return DBGK_ERR_ARG;
-	(void)hipSetDevice(m->device);
-	if (m->stream) (void)hipStreamSynchronize(m->stream);
-	map_free_batch(m);
-	map_free_contigs(m);
-	(void)hipFree(m->d_accept);
-	(void)hipFree(m->d_ctr);
-	(void)hipFree(m->d_chk);
-	for (auto &e : m->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (m->stream) (void)hipStreamDestroy(m->stream);
+	stage_drain(m->device, m->stream);
+	if (m->index) (void)dbgk_destroy(m->index);
 	delete m;
 	return DBGK_OK;
 }
@@ -158,7 +123,7 @@ extern "C" int dbgk_map_set_contigs(dbgk_map *m, const char *bases, const uint64
 		return rc;
 	}
 	HIPCHK(hipSetDevice(m->device));
-	if (hipMalloc(&m->d_ctg, total + 16) != hipSuccess || hipMalloc(&m->d_ctg_off, (n_contigs + 1) * 8) != hipSuccess) {
+	if (m->d_ctg.reserve(total + 16) || m->d_ctg_off.reserve((n_contigs + 1) * 8)) {
 		map_free_contigs(m);
 		return DBGK_ERR_NOMEM;
 	}
@@ -184,14 +149,7 @@ static int map_ensure_accept(dbgk_map *m, uint64_t max_len)
 		}
 		m->accept[len] = (int32_t)lo;
 	}
-	if (m->accept.size() > m->cap_accept) {
-		(void)hipFree(m->d_accept);
-		m->d_accept = nullptr;
-		m->cap_accept = 0;
-		const uint64_t cap = std::max<uint64_t>(m->accept.size(), 4096);
-		if (hipMalloc(&m->d_accept, cap * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		m->cap_accept = cap;
-	}
+	if (m->d_accept.reserve(m->accept.size() * 4, 4096 * 4)) return DBGK_ERR_NOMEM;
 	HIPCHK(hipMemcpyAsync(m->d_accept, m->accept.data(), m->accept.size() * 4, hipMemcpyHostToDevice, m->stream));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	return DBGK_OK;
@@ -202,15 +160,11 @@ static int map_ensure_batch(dbgk_map *m, uint64_t n_bytes, uint64_t n_reads)
 {
 	if (n_bytes + 16 > m->cap_bytes || n_reads > m->cap_reads) {
 		const uint64_t bytes = std::max<uint64_t>(n_bytes + 16, 1 << 20), reads = std::max<uint64_t>(n_reads, 1 << 14);
-		map_free_batch(m);
+		m->cap_bytes = m->cap_reads = 0;
+		if (m->d_seq.reserve(bytes) || m->d_off.reserve((reads + 1) * 8) || m->d_hits.reserve(reads * 2 * sizeof(mapk::Hit)) || m->d_long.reserve(reads * 4))
+			return DBGK_ERR_NOMEM;
 		m->cap_bytes = bytes;
 		m->cap_reads = reads;
-		if (hipMalloc(&m->d_seq, m->cap_bytes) != hipSuccess || hipMalloc(&m->d_off, (m->cap_reads + 1) * 8) != hipSuccess ||
-		    hipMalloc(&m->d_hits, m->cap_reads * 2 * sizeof(mapk::Hit)) != hipSuccess ||
-		    hipMalloc(&m->d_long, m->cap_reads * 4) != hipSuccess) {
-			map_free_batch(m);
-			return DBGK_ERR_NOMEM;
-		}
 	}
 	return DBGK_OK;
 }
@@ -227,7 +181,7 @@ static int map_run(dbgk_map *m, const uint8_t *d_seq, const uint64_t *d_off, uin
 	const unsigned grid = (unsigned)std::min<uint64_t>(groups, (uint64_t)m->n_cu * 32);
 	HIPCHK(hipEventRecord(m->ev[0], m->stream));
 	hipLaunchKernelGGL(mapk::k_map_reads<false>, dim3(grid), dim3(mapk::kMapWaves * 64), 0, m->stream, d_seq, d_off, nr, P, X,
-	                   (const int32_t *)m->d_accept, m->d_hits, m->d_long, m->d_ctr);
+	                   (const int32_t *)m->d_accept.p, m->d_hits, m->d_long, m->d_ctr);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(m->ev[1], m->stream));
 	mapk::MapCounters hc{};
@@ -237,7 +191,7 @@ static int map_run(dbgk_map *m, const uint8_t *d_seq, const uint64_t *d_off, uin
 		const unsigned grid_long = (unsigned)std::min<uint64_t>((hc.n_long + mapk::kMapWaves - 1) / mapk::kMapWaves, (uint64_t)m->n_cu * 32);
 		HIPCHK(hipEventRecord(m->ev[2], m->stream));
 		hipLaunchKernelGGL(mapk::k_map_reads<true>, dim3(grid_long), dim3(mapk::kMapWaves * 64), 0, m->stream, d_seq, d_off, nr, P, X,
-		                   (const int32_t *)m->d_accept, m->d_hits, m->d_long, m->d_ctr);
+		                   (const int32_t *)m->d_accept.p, m->d_hits, m->d_long, m->d_ctr);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipEventRecord(m->ev[3], m->stream));
 		HIPCHK(hipMemcpyAsync(&hc, m->d_ctr, sizeof hc, hipMemcpyDeviceToHost, m->stream));
@@ -295,7 +249,7 @@ extern "C" int dbgk_map_reads_device(dbgk_map *m, const char *d_bases, const uin
 	if (!n_reads) return DBGK_OK;
 	HIPCHK(hipSetDevice(m->device));
 	// what dbgk_map_reads learns from its host loop over the offsets, learned on the device, before any read is mapped
-	if (!m->d_chk && hipMalloc(&m->d_chk, 3 * sizeof(unsigned long long)) != hipSuccess) return DBGK_ERR_NOMEM;
+	if (m->d_chk.reserve(3 * sizeof(unsigned long long))) return DBGK_ERR_NOMEM;
 	unsigned long long chk[3] = {0, 0, 0};
 	HIPCHK(hipMemsetAsync(m->d_chk, 0, sizeof chk, m->stream));
 	hipLaunchKernelGGL(mapk::k_map_check_batch, dim3((unsigned)std::min<uint64_t>((n_reads + 255) / 256, (uint64_t)m->n_cu * 16)), dim3(256), 0,

@@ -2,20 +2,17 @@
 // the two outputs as EmitStage structs, so that their read-back, their device view and their hand-over to a graph handle are
 // dbgk_host_emit.h's, with its event ordering.
 
-struct dbgk_pair {
-	int device = 0;
-	int n_cu = 256;
-	hipStream_t stream = nullptr;
+struct dbgk_pair : StageDev {
 	// out[DBGK_PAIR_PAIRED], out[DBGK_PAIR_SINGLE].  Of an EmitStage this stage uses the planes, off, src, len and their capacities,
 	// the events and have / has_qual / lent; the counters and the scan's storage of both outputs are out[0]'s.
 	EmitStage out[2];
-	uint32_t *id[2] = {nullptr, nullptr};  // source id 2 i + mate per output read
-	uint32_t *flag[2] = {nullptr, nullptr}; // n + 1 flags: the pair goes to PAIR / to SINGLE
-	uint64_t *rank[2] = {nullptr, nullptr}; // their exclusive scans
+	DevBuf<uint32_t> id[2];   // source id 2 i + mate per output read
+	DevBuf<uint32_t> flag[2]; // n + 1 flags: the pair goes to PAIR / to SINGLE
+	DevBuf<uint64_t> rank[2]; // their exclusive scans
 	uint64_t cap_pairs = 0;
 	// dbgk_pair_split_from: the uploaded batches
-	uint8_t *in_b[2] = {nullptr, nullptr}, *in_q[2] = {nullptr, nullptr};
-	uint64_t *in_off[2] = {nullptr, nullptr};
+	DevBuf<uint8_t> in_b[2], in_q[2];
+	DevBuf<uint64_t> in_off[2];
 	uint64_t in_cap_bytes = 0, in_cap_qual = 0, in_cap_reads = 0;
 };
 
@@ -26,23 +23,9 @@ extern "C" int dbgk_pair_create(int device, dbgk_pair **out)
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
 	if (device < 0) return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_pair *p = new (std::nothrow) dbgk_pair;
 	if (!p) return DBGK_ERR_NOMEM;
-	p->device = device;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) p->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
+	int rc = stage_open(*p, device);
 	for (int w = 0; !rc && w < 2; ++w) rc = emit_create(p->out[w], pairk::PC_COUNT, false);
 	if (rc) {
 		dbgk_pair_destroy(p);
@@ -55,14 +38,8 @@ extern "C" int dbgk_pair_create(int device, dbgk_pair **out)
 extern "C" int dbgk_pair_destroy(dbgk_pair *p)
 {
 	if (!p) return DBGK_ERR_ARG;
-	(void)hipSetDevice(p->device);
-	if (p->stream) (void)hipStreamSynchronize(p->stream);
-	for (int w = 0; w < 2; ++w) {
-		emit_destroy(p->out[w]);
-		(void)hipFree(p->id[w]); (void)hipFree(p->flag[w]); (void)hipFree(p->rank[w]);
-		(void)hipFree(p->in_b[w]); (void)hipFree(p->in_q[w]); (void)hipFree(p->in_off[w]);
-	}
-	if (p->stream) (void)hipStreamDestroy(p->stream);
+	stage_drain(p->device, p->stream);
+	for (EmitStage &s : p->out) emit_destroy(s);
 	delete p;
 	return DBGK_OK;
 }
@@ -71,44 +48,22 @@ extern "C" int dbgk_pair_destroy(dbgk_pair *p)
 static int pair_ensure_reads(dbgk_pair *p, uint64_t n)
 {
 	if (n <= p->cap_pairs && p->out[0].off) return DBGK_OK;
-	for (int w = 0; w < 2; ++w) {
-		EmitStage &s = p->out[w];
+	for (EmitStage &s : p->out) {
 		int rc = emit_reclaim(s, p->stream, true);
 		if (rc) return rc;
-		(void)hipFree(s.off); (void)hipFree(s.len); (void)hipFree(s.src); (void)hipFree(p->id[w]); (void)hipFree(p->flag[w]); (void)hipFree(p->rank[w]);
-		s.off = nullptr; s.len = nullptr; s.src = nullptr; p->id[w] = nullptr; p->flag[w] = nullptr; p->rank[w] = nullptr;
 	}
 	p->cap_pairs = 0;
 	const uint64_t cap = std::max<uint64_t>(n, 1 << 14);
 	for (int w = 0; w < 2; ++w) {
 		EmitStage &s = p->out[w];
 		const uint64_t reads = w == DBGK_PAIR_PAIRED ? 2 * cap : cap;
-		if (hipMalloc(&s.off, (reads + 1) * 8) != hipSuccess || hipMalloc(&s.len, (reads + 1) * 4) != hipSuccess ||
-		    hipMalloc(&s.src, reads * 8) != hipSuccess || hipMalloc(&p->id[w], reads * 4) != hipSuccess ||
-		    hipMalloc(&p->flag[w], (cap + 1) * 4) != hipSuccess || hipMalloc(&p->rank[w], (cap + 1) * 8) != hipSuccess)
+		if (s.off.reserve((reads + 1) * 8) || s.len.reserve((reads + 1) * 4) || s.src.reserve(reads * 8) || p->id[w].reserve(reads * 4) ||
+		    p->flag[w].reserve((cap + 1) * 4) || p->rank[w].reserve((cap + 1) * 8))
 			return DBGK_ERR_NOMEM;
 		s.cap_reads = reads;
 	}
 	p->cap_pairs = cap;
 	return DBGK_OK;
-}
-
-// an exclusive scan of n_items lengths on the stage's stream; its storage is out[0]'s and grows here (the stream is drained first)
-static int pair_scan(dbgk_pair *p, const uint32_t *len, uint64_t *off, uint64_t n_items)
-{
-	EmitStage &s = p->out[0];
-	size_t need = 0;
-	if (dbgk_internal_scan_lengths(nullptr, &need, len, off, n_items, p->stream)) return DBGK_ERR_HIP;
-	if (need > s.tmp_bytes) {
-		HIPCHK(hipStreamSynchronize(p->stream));
-		(void)hipFree(s.tmp);
-		s.tmp = nullptr;
-		s.tmp_bytes = 0;
-		if (hipMalloc(&s.tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-		s.tmp_bytes = need;
-	}
-	size_t bytes = s.tmp_bytes;
-	return dbgk_internal_scan_lengths(s.tmp, &bytes, len, off, n_items, p->stream) ? DBGK_ERR_HIP : DBGK_OK;
 }
 
 // the planes of one output for `total` bytes: whole vectors and the room behind the end that the emit planes have
@@ -119,11 +74,9 @@ static int pair_ensure_planes(dbgk_pair *p, EmitStage &s, uint64_t total, bool w
 	int rc = emit_reclaim(s, p->stream, true);
 	if (rc) return rc;
 	const bool keep_qual = with_qual || s.quals;
-	(void)hipFree(s.bases); (void)hipFree(s.quals);
-	s.bases = s.quals = nullptr;
 	const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(want, s.cap_bytes), 1 << 20);
 	s.cap_bytes = 0;
-	if (hipMalloc(&s.bases, cap) != hipSuccess || (keep_qual && hipMalloc(&s.quals, cap) != hipSuccess)) return DBGK_ERR_NOMEM;
+	if (s.bases.reserve(cap) || (keep_qual && s.quals.reserve(cap))) return DBGK_ERR_NOMEM;
 	s.cap_bytes = cap;
 	return DBGK_OK;
 }
@@ -149,7 +102,7 @@ static int pair_run(dbgk_pair *p, const uint8_t *b1, const uint8_t *q1, const ui
 	if (n) {
 		hipLaunchKernelGGL(pairk::k_pair_classify, dim3(grid), dim3(emitk::kEmitBlock), 0, p->stream, o1, o2, n32, p->flag[0], p->flag[1], P.ctr);
 		HIPCHK(hipGetLastError());
-		for (int w = 0; w < 2 && !rc; ++w) rc = pair_scan(p, p->flag[w], p->rank[w], n + 1);
+		for (int w = 0; w < 2 && !rc; ++w) rc = stage_scan(P.tmp, p->stream, p->flag[w], p->rank[w], n + 1);
 		if (rc) return rc;
 		hipLaunchKernelGGL(pairk::k_pair_scatter, dim3(grid), dim3(emitk::kEmitBlock), 0, p->stream, o1, o2, n32, (const uint64_t *)p->rank[0],
 		                   (const uint64_t *)p->rank[1], pairk::PairOut{P.len, P.src, p->id[0]}, pairk::PairOut{S.len, S.src, p->id[1]});
@@ -162,7 +115,7 @@ static int pair_run(dbgk_pair *p, const uint8_t *b1, const uint8_t *q1, const ui
 	S.n = ctr[pairk::PC_SINGLE_READS], S.total = ctr[pairk::PC_SINGLE_BASES];
 	for (int w = 0; w < 2; ++w) {
 		EmitStage &s = p->out[w];
-		if (s.n) rc = pair_scan(p, s.len, s.off, s.n + 1);
+		if (s.n) rc = stage_scan(P.tmp, p->stream, s.len, s.off, s.n + 1);
 		else if (hipMemsetAsync(s.off, 0, 8, p->stream) != hipSuccess) rc = DBGK_ERR_HIP;
 		if (rc) return rc;
 	}
@@ -180,10 +133,10 @@ static int pair_run(dbgk_pair *p, const uint8_t *b1, const uint8_t *q1, const ui
 		const unsigned g = (unsigned)std::min<uint64_t>(tiles, (uint64_t)p->n_cu * 64);
 		if (with_qual)
 			hipLaunchKernelGGL(pairk::k_pair_gather<true>, dim3(g), dim3(emitk::kEmitBlock), 0, p->stream, in, (const uint64_t *)s.src,
-			                   (const uint64_t *)s.off, (uint32_t)s.n, s.total, reinterpret_cast<uint4 *>(s.bases), reinterpret_cast<uint4 *>(s.quals));
+			                   (const uint64_t *)s.off, (uint32_t)s.n, s.total, reinterpret_cast<uint4 *>(s.bases.p), reinterpret_cast<uint4 *>(s.quals.p));
 		else
 			hipLaunchKernelGGL(pairk::k_pair_gather<false>, dim3(g), dim3(emitk::kEmitBlock), 0, p->stream, in, (const uint64_t *)s.src,
-			                   (const uint64_t *)s.off, (uint32_t)s.n, s.total, reinterpret_cast<uint4 *>(s.bases), (uint4 *)nullptr);
+			                   (const uint64_t *)s.off, (uint32_t)s.n, s.total, reinterpret_cast<uint4 *>(s.bases.p), (uint4 *)nullptr);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipEventRecord(P.ev[3], p->stream));
@@ -212,7 +165,7 @@ static bool pair_device_plane_ok(const dbgk_pair *p, const char *ptr)
 	if ((uintptr_t)ptr & 15u) return false;
 	const uint8_t *u = (const uint8_t *)ptr;
 	for (int w = 0; w < 2; ++w)
-		for (const uint8_t *own : {p->out[w].bases, p->out[w].quals})
+		for (const uint8_t *own : {p->out[w].bases.p, p->out[w].quals.p})
 			if (u && own && u >= own && u < own + p->out[w].cap_bytes) return false;
 	return true;
 }
@@ -252,15 +205,8 @@ extern "C" int dbgk_pair_split_from(dbgk_pair *p, const char *bases1, const char
 		const uint64_t reads = std::max<uint64_t>(std::max<uint64_t>(n, p->in_cap_reads), 1 << 14);
 		const bool qual = with_qual || p->in_cap_qual;
 		p->in_cap_bytes = p->in_cap_qual = p->in_cap_reads = 0;
-		for (int w = 0; w < 2; ++w) {
-			(void)hipFree(p->in_b[w]); (void)hipFree(p->in_q[w]); (void)hipFree(p->in_off[w]);
-			p->in_b[w] = p->in_q[w] = nullptr;
-			p->in_off[w] = nullptr;
-		}
 		for (int w = 0; w < 2; ++w)
-			if (hipMalloc(&p->in_b[w], bytes) != hipSuccess || (qual && hipMalloc(&p->in_q[w], bytes) != hipSuccess) ||
-			    hipMalloc(&p->in_off[w], (reads + 1) * 8) != hipSuccess)
-				return DBGK_ERR_NOMEM;
+			if (p->in_b[w].reserve(bytes) || (qual && p->in_q[w].reserve(bytes)) || p->in_off[w].reserve((reads + 1) * 8)) return DBGK_ERR_NOMEM;
 		p->in_cap_bytes = bytes;
 		p->in_cap_qual = qual ? bytes : 0;
 		p->in_cap_reads = reads;
@@ -272,7 +218,7 @@ extern "C" int dbgk_pair_split_from(dbgk_pair *p, const char *bases1, const char
 		HIPCHK(hipMemcpyAsync(p->in_off[w], offsets[w], (n + 1) * 8, hipMemcpyHostToDevice, p->stream));
 	}
 	HIPCHK(hipStreamSynchronize(p->stream)); // the caller's buffers are free on return
-	return pair_run(p, p->in_b[0], with_qual ? p->in_q[0] : nullptr, p->in_off[0], p->in_b[1], with_qual ? p->in_q[1] : nullptr, p->in_off[1], n, out);
+	return pair_run(p, p->in_b[0], with_qual ? p->in_q[0].p : nullptr, p->in_off[0], p->in_b[1], with_qual ? p->in_q[1].p : nullptr, p->in_off[1], n, out);
 }
 
 extern "C" int dbgk_pair_results(dbgk_pair *p, int which, char *bases, char *quals, uint64_t *offsets, uint32_t *src_ids)

@@ -3,28 +3,23 @@
 // dbgk_host_emit.h's, with its event ordering.  The launches of a chunk follow each other on one stream; the host reads three
 // numbers in between (newlines, records, output bytes), each of which sizes what the next launches write.
 
-struct dbgk_parse {
-	int device = 0;
-	int n_cu = 256;
+struct dbgk_parse : StageDev {
 	int format = 1;
 	bool with_quals = false;
-	hipStream_t stream = nullptr;
 	EmitStage out; // split_src; its counters are parsek::Counter, its scan storage serves every scan of the stage
-	uint8_t *text = nullptr; // dbgk_parse_chunk: the uploaded chunk
-	uint64_t cap_text = 0;
+	DevBuf<uint8_t> text; // dbgk_parse_chunk: the uploaded chunk
 	const uint8_t *last_text = nullptr; // the text of the last chunk where it lies (dbgk_parse_text_device)
 	uint64_t last_n = 0;
-	uint32_t *tile_cnt = nullptr; // per tile of the text: newlines, and their exclusive scan
-	uint64_t *tile_off = nullptr;
+	DevBuf<uint32_t> tile_cnt; // per tile of the text: newlines, and their exclusive scan
+	DevBuf<uint64_t> tile_off;
 	uint64_t cap_tiles = 0;
-	uint32_t *table = nullptr, *flag = nullptr; // per line (+ 1): the line table, header flags and their exclusive scan
-	uint64_t *rank = nullptr;
-	uint8_t *agg = nullptr, *entry = nullptr; // per kLineChunk lines: the chunk's map, the state it is entered in
+	DevBuf<uint32_t> table, flag; // per line (+ 1): the line table, header flags and their exclusive scan
+	DevBuf<uint64_t> rank;
+	DevBuf<uint8_t> agg, entry; // per kLineChunk lines: the chunk's map, the state it is entered in
 	uint64_t cap_lines = 0;
-	dbgk_parse_rec *rec = nullptr;
-	uint64_t cap_recs = 0;
-	parsek::ParseMisc *misc = nullptr;
-	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // count + scan, lines, states + scan
+	DevBuf<dbgk_parse_rec> rec;
+	DevBuf<parsek::ParseMisc> misc;
+	StageEvents<6> ev; // count + scan, lines, states + scan
 };
 
 extern "C" int dbgk_parse_create(int32_t format, int32_t with_quals, int device, dbgk_parse **out)
@@ -32,30 +27,15 @@ extern "C" int dbgk_parse_create(int32_t format, int32_t with_quals, int device,
 	if (!out) return DBGK_ERR_ARG;
 	*out = nullptr;
 	if (device < 0 || (format != 1 && format != 2) || (with_quals && format != 1)) return DBGK_ERR_ARG;
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device >= n_dev) {
-		g_last_error = "no usable HIP device";
-		return DBGK_ERR_HIP;
-	}
 	dbgk_parse *p = new (std::nothrow) dbgk_parse;
 	if (!p) return DBGK_ERR_NOMEM;
-	p->device = device;
 	p->format = format;
 	p->with_quals = with_quals != 0;
-	int rc = DBGK_OK;
-	hipDeviceProp_t prop;
-	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		rc = DBGK_ERR_HIP;
-	}
-	if (!rc) p->n_cu = prop.multiProcessorCount;
-	if (!rc && hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) rc = DBGK_ERR_HIP;
+	int rc = stage_open(*p, device);
 	if (!rc) rc = emit_create(p->out, parsek::PC_COUNT, false);
 	p->out.split_src = true;
-	for (int i = 0; !rc && i < 6; ++i)
-		if (hipEventCreate(&p->ev[i]) != hipSuccess) rc = DBGK_ERR_HIP;
-	if (!rc && hipMalloc(&p->misc, sizeof(parsek::ParseMisc)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (!rc) rc = p->ev.create();
+	if (!rc) rc = p->misc.reserve(sizeof(parsek::ParseMisc));
 	if (rc) {
 		dbgk_parse_destroy(p);
 		return rc;
@@ -67,46 +47,19 @@ extern "C" int dbgk_parse_create(int32_t format, int32_t with_quals, int device,
 extern "C" int dbgk_parse_destroy(dbgk_parse *p)
 {
 	if (!p) return DBGK_ERR_ARG;
-	(void)hipSetDevice(p->device);
-	if (p->stream) (void)hipStreamSynchronize(p->stream);
+	stage_drain(p->device, p->stream);
 	emit_destroy(p->out);
-	(void)hipFree(p->text); (void)hipFree(p->tile_cnt); (void)hipFree(p->tile_off); (void)hipFree(p->table); (void)hipFree(p->flag);
-	(void)hipFree(p->rank); (void)hipFree(p->agg); (void)hipFree(p->entry); (void)hipFree(p->rec); (void)hipFree(p->misc);
-	for (hipEvent_t e : p->ev)
-		if (e) (void)hipEventDestroy(e);
-	if (p->stream) (void)hipStreamDestroy(p->stream);
 	delete p;
 	return DBGK_OK;
-}
-
-// an exclusive scan of n_items 32-bit values on the stage's stream; the storage is the output stage's and grows here (the stream is
-// drained first)
-static int parse_scan(dbgk_parse *p, const uint32_t *in, uint64_t *out, uint64_t n_items)
-{
-	EmitStage &s = p->out;
-	size_t need = 0;
-	if (dbgk_internal_scan_lengths(nullptr, &need, in, out, n_items, p->stream)) return DBGK_ERR_HIP;
-	if (need > s.tmp_bytes) {
-		HIPCHK(hipStreamSynchronize(p->stream));
-		(void)hipFree(s.tmp);
-		s.tmp = nullptr;
-		s.tmp_bytes = 0;
-		if (hipMalloc(&s.tmp, need) != hipSuccess) return DBGK_ERR_NOMEM;
-		s.tmp_bytes = need;
-	}
-	size_t bytes = s.tmp_bytes;
-	return dbgk_internal_scan_lengths(s.tmp, &bytes, in, out, n_items, p->stream) ? DBGK_ERR_HIP : DBGK_OK;
 }
 
 // (the stream is idle: every caller has just read a number back)
 static int parse_ensure_tiles(dbgk_parse *p, uint64_t n_tiles)
 {
 	if (n_tiles <= p->cap_tiles && p->tile_cnt) return DBGK_OK;
-	(void)hipFree(p->tile_cnt); (void)hipFree(p->tile_off);
-	p->tile_cnt = nullptr; p->tile_off = nullptr;
 	p->cap_tiles = 0;
 	const uint64_t cap = std::max<uint64_t>(n_tiles, 1 << 10);
-	if (hipMalloc(&p->tile_cnt, (cap + 1) * 4) != hipSuccess || hipMalloc(&p->tile_off, (cap + 1) * 8) != hipSuccess) return DBGK_ERR_NOMEM;
+	if (p->tile_cnt.reserve((cap + 1) * 4) || p->tile_off.reserve((cap + 1) * 8)) return DBGK_ERR_NOMEM;
 	p->cap_tiles = cap;
 	return DBGK_OK;
 }
@@ -115,12 +68,10 @@ static int parse_ensure_tiles(dbgk_parse *p, uint64_t n_tiles)
 static int parse_ensure_lines(dbgk_parse *p, uint64_t n_lines)
 {
 	if (n_lines <= p->cap_lines && p->table) return DBGK_OK;
-	(void)hipFree(p->table); (void)hipFree(p->flag); (void)hipFree(p->rank); (void)hipFree(p->agg); (void)hipFree(p->entry);
-	p->table = p->flag = nullptr; p->rank = nullptr; p->agg = p->entry = nullptr;
 	p->cap_lines = 0;
 	const uint64_t cap = std::max<uint64_t>(n_lines, 1 << 16), chunks = (cap + 1 + parsek::kLineChunk - 1) / parsek::kLineChunk;
-	if (hipMalloc(&p->table, (cap + 1) * 4) != hipSuccess || hipMalloc(&p->flag, (cap + 1) * 4) != hipSuccess ||
-	    hipMalloc(&p->rank, (cap + 1) * 8) != hipSuccess || hipMalloc(&p->agg, chunks) != hipSuccess || hipMalloc(&p->entry, chunks) != hipSuccess)
+	if (p->table.reserve((cap + 1) * 4) || p->flag.reserve((cap + 1) * 4) || p->rank.reserve((cap + 1) * 8) || p->agg.reserve(chunks) ||
+	    p->entry.reserve(chunks))
 		return DBGK_ERR_NOMEM;
 	p->cap_lines = cap;
 	return DBGK_OK;
@@ -149,7 +100,7 @@ static int parse_run(dbgk_parse *p, const uint8_t *text, uint64_t n_bytes, bool 
 		hipLaunchKernelGGL(parsek::k_parse_count, dim3(grid + 1), dim3(parsek::kParseBlock), 0, p->stream, reinterpret_cast<const uint4 *>(text), nb,
 		                   n_tiles, p->tile_cnt);
 		HIPCHK(hipGetLastError());
-		rc = parse_scan(p, p->tile_cnt, p->tile_off, (uint64_t)n_tiles + 1);
+		rc = stage_scan(s.tmp, p->stream, p->tile_cnt, p->tile_off, (uint64_t)n_tiles + 1);
 		if (rc) return rc;
 		HIPCHK(hipEventRecord(p->ev[1], p->stream));
 		uint8_t last_byte = 0;
@@ -175,7 +126,7 @@ static int parse_run(dbgk_parse *p, const uint8_t *text, uint64_t n_bytes, bool 
 		hipLaunchKernelGGL(parsek::k_parse_states, dim3(chunks), dim3(parsek::kParseBlock), 0, p->stream, (const uint32_t *)p->table, (uint32_t)n_lines,
 		                   (uint32_t)fastq, (const uint8_t *)p->entry, p->flag, p->misc);
 		HIPCHK(hipGetLastError());
-		rc = parse_scan(p, p->flag, p->rank, n_lines + 1);
+		rc = stage_scan(s.tmp, p->stream, p->flag, p->rank, n_lines + 1);
 		if (rc) return rc;
 		HIPCHK(hipEventRecord(p->ev[5], p->stream));
 		HIPCHK(hipMemcpyAsync(&n_rec, p->rank + n_lines, 8, hipMemcpyDeviceToHost, p->stream));
@@ -207,14 +158,7 @@ static int parse_run(dbgk_parse *p, const uint8_t *text, uint64_t n_bytes, bool 
 			I.consumed = 0;
 		}
 	}
-	if (n_rec > p->cap_recs || !p->rec) {
-		(void)hipFree(p->rec);
-		p->rec = nullptr;
-		p->cap_recs = 0;
-		const uint64_t cap = std::max<uint64_t>(n_rec, 1 << 14);
-		if (hipMalloc(&p->rec, cap * sizeof(dbgk_parse_rec)) != hipSuccess) return DBGK_ERR_NOMEM;
-		p->cap_recs = cap;
-	}
+	if (p->rec.reserve(n_rec * sizeof(dbgk_parse_rec), (1 << 14) * sizeof(dbgk_parse_rec))) return DBGK_ERR_NOMEM;
 	unsigned long long ctr[parsek::PC_COUNT] = {0};
 	const uint32_t n_lines32 = (uint32_t)n_lines, n_nl32 = (uint32_t)n_nl, n32 = (uint32_t)n_rec;
 	const uint64_t line_blocks = (n_lines + parsek::kParseBlock) / parsek::kParseBlock;
@@ -222,7 +166,7 @@ static int parse_run(dbgk_parse *p, const uint8_t *text, uint64_t n_bytes, bool 
 	auto launch_len = [&](unsigned, uint32_t *len, uint64_t *src, unsigned long long *d_ctr) {
 		hipLaunchKernelGGL(parsek::k_parse_records, dim3((unsigned)std::min<uint64_t>(line_blocks, (uint64_t)p->n_cu * 16)), dim3(parsek::kParseBlock), 0,
 		                   p->stream, (const uint32_t *)p->table, (const uint32_t *)p->flag, (const uint64_t *)p->rank, n_lines32, n_nl32, nb, n32,
-		                   (uint32_t)fastq, (uint32_t)p->with_quals, parsek::ParseOut{p->rec, len, src, s.qsrc}, d_ctr);
+		                   (uint32_t)fastq, (uint32_t)p->with_quals, parsek::ParseOut{p->rec.p, len, src, s.qsrc.p}, d_ctr);
 	};
 	int rc = emit_run(s, p->stream, p->n_cu, n_rec, text, p->with_quals ? text : nullptr, false, 0u, launch_len, ctr, &I.ms_scan, &I.ms_gather);
 	if (rc) return rc;
@@ -239,7 +183,7 @@ extern "C" int dbgk_parse_chunk_device(dbgk_parse *p, const char *d_text, uint64
 {
 	if (!p || !out || n_bytes >= (1ull << 31) || (n_bytes && !d_text) || ((uintptr_t)d_text & 15u)) return DBGK_ERR_ARG;
 	const uint8_t *u = (const uint8_t *)d_text;
-	for (const uint8_t *own : {p->out.bases, p->out.quals}) // the batch the call is about to write
+	for (const uint8_t *own : {p->out.bases.p, p->out.quals.p}) // the batch the call is about to write
 		if (u && own && u + n_bytes > own && u < own + p->out.cap_bytes) return DBGK_ERR_ARG;
 	HIPCHK(hipSetDevice(p->device));
 	return parse_run(p, u, n_bytes, last != 0, out);
@@ -250,14 +194,9 @@ extern "C" int dbgk_parse_chunk(dbgk_parse *p, const char *text, uint64_t n_byte
 	if (!p || !out || n_bytes >= (1ull << 31) || (n_bytes && !text)) return DBGK_ERR_ARG;
 	p->out.have = false;
 	HIPCHK(hipSetDevice(p->device));
-	if (n_bytes + 16 > p->cap_text) {
+	if (n_bytes + 16 > p->text.cap) {
 		HIPCHK(hipStreamSynchronize(p->stream));
-		(void)hipFree(p->text);
-		p->text = nullptr;
-		p->cap_text = 0;
-		const uint64_t cap = std::max<uint64_t>(n_bytes + 16, 1 << 20);
-		if (hipMalloc(&p->text, cap) != hipSuccess) return DBGK_ERR_NOMEM;
-		p->cap_text = cap;
+		if (p->text.reserve(n_bytes + 16, 1 << 20)) return DBGK_ERR_NOMEM;
 	}
 	if (n_bytes) HIPCHK(hipMemcpyAsync(p->text, text, n_bytes, hipMemcpyHostToDevice, p->stream));
 	HIPCHK(hipStreamSynchronize(p->stream)); // the caller's buffer is free on return

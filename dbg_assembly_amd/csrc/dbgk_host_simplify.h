@@ -217,7 +217,7 @@ extern "C" int dbgk_simplify_update(dbgk_contig *c, const uint64_t *slots, uint6
 	HIPCHK(hipMemcpyAsync(d_byte_at, byte_at.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipMemcpyAsync(d_byte_val, byte_val.data(), nb, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipEventRecord(c->ev[0], c->stream));
-	uint8_t *array = c->wide ? reinterpret_cast<uint8_t *>(c->d_array32) : reinterpret_cast<uint8_t *>(c->d_array);
+	uint8_t *array = c->wide ? reinterpret_cast<uint8_t *>(c->d_array32.p) : reinterpret_cast<uint8_t *>(c->d_array.p);
 	hipLaunchKernelGGL(simpk::k_simp_update, dim3(contig_grid(c, m)), dim3(simpk::kSimpThreads), 0, c->stream, array,
 	                   (uint32_t)(c->wide ? sizeof(dbgk_node32) : sizeof(dbgk_node)), (uint32_t)(c->wide ? offsetof(dbgk_node32, l_link) : offsetof(dbgk_node, l_link)),
 	                   c->d_klink, c->d_del, d_slot, d_links, d_records, (uint32_t)m, d_byte_at, d_byte_val, (uint32_t)nb);

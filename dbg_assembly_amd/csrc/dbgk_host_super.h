@@ -9,7 +9,7 @@ struct dbgk_super {
 	bool reads_set = false;
 	// gap statistics, ascending by key
 	std::vector<superk::PairStat> pairs;
-	superk::Counters *d_sctr = nullptr;
+	DevBuf<superk::Counters> d_sctr;
 	// dbgk_super_resolve
 	bool resolved = false;
 	std::vector<uint64_t> scaf_first;
@@ -17,7 +17,7 @@ struct dbgk_super {
 	std::vector<dbgk_super_junction> junctions;
 	std::vector<dbgk_super_slice> slices;
 	std::vector<int32_t> repeats;
-	uint8_t *d_slices = nullptr;
+	DevBuf<uint8_t> d_slices;
 	uint64_t slice_bytes = 0;
 	dbgk_super_summary summary{};
 	dbgk_super_timing stats{};
@@ -39,7 +39,7 @@ extern "C" int dbgk_super_create(const dbgk_super_params *p, int device, dbgk_su
 	s->p = *p;
 	dbgk_fill_params fp{p->pair_num_cut, {0, 0, 0}};
 	int rc = dbgk_fill_create(&fp, device, &s->F);
-	if (!rc && hipMalloc(&s->d_sctr, sizeof(superk::Counters)) != hipSuccess) rc = DBGK_ERR_NOMEM;
+	if (!rc) rc = s->d_sctr.reserve(sizeof(superk::Counters));
 	if (rc) {
 		dbgk_super_destroy(s);
 		return rc;
@@ -51,13 +51,10 @@ extern "C" int dbgk_super_create(const dbgk_super_params *p, int device, dbgk_su
 extern "C" int dbgk_super_destroy(dbgk_super *s)
 {
 	if (!s) return DBGK_ERR_ARG;
-	if (s->F) {
-		(void)hipSetDevice(s->F->L->device);
-		(void)hipStreamSynchronize(s->F->L->stream);
-	}
-	(void)hipFree(s->d_sctr); (void)hipFree(s->d_slices);
-	if (s->F) dbgk_fill_destroy(s->F);
-	delete s;
+	dbgk_fill *f = s->F;
+	if (f) stage_drain(f->L->device, f->L->stream);
+	delete s; // (its buffers go before the link's stream does)
+	if (f) dbgk_fill_destroy(f);
 	return DBGK_OK;
 }
 
@@ -105,17 +102,13 @@ extern "C" int dbgk_super_build(dbgk_super *s)
 	auto t0 = std::chrono::steady_clock::now();
 	if ((rc = dbgk_internal_sort_pairs(f->d_pair_keys, f->d_svals, n, l->stream))) return rc;
 	f->stats.ms_sort += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	superk::Acc *d_acc = nullptr;
-	superk::PairStat *d_stat = nullptr;
-	auto release = [&]() { (void)hipFree(d_acc); (void)hipFree(d_stat); };
+	DevBuf<superk::Acc> d_acc;
+	DevBuf<superk::PairStat> d_stat;
 	// One accumulator per sorted position, used at the first record of a pair: the reduce finds a pair's accumulator through that
 	// position, which every thread learns from the tile scan, so no table from positions to pairs is needed.  One result slot per
 	// record too (at most one pair per record).  Both are O(records), 80 bytes per record, freed before this call returns; sizing
 	// them by pairs would take an ordered compaction of the head positions first.  Not measured.
-	if (hipMalloc(&d_acc, pooled * sizeof(superk::Acc)) != hipSuccess || hipMalloc(&d_stat, pooled * sizeof(superk::PairStat)) != hipSuccess) {
-		release();
-		return DBGK_ERR_NOMEM;
-	}
+	if (d_acc.reserve(pooled * sizeof(superk::Acc)) || d_stat.reserve(pooled * sizeof(superk::PairStat))) return DBGK_ERR_NOMEM;
 	auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, "dbgk_super_build", __LINE__); };
 	superk::Counters sc{};
 	step(hipMemsetAsync(d_acc, 0, pooled * sizeof(superk::Acc), l->stream));
@@ -138,7 +131,6 @@ extern "C" int dbgk_super_build(dbgk_super *s)
 		s->pairs.resize(sc.pairs);
 		step(hipMemcpy(s->pairs.data(), d_stat, sc.pairs * sizeof(superk::PairStat), hipMemcpyDeviceToHost));
 	}
-	release();
 	if (rc) return rc;
 	// the slots come in no particular order
 	std::sort(s->pairs.begin(), s->pairs.end(), [](const superk::PairStat &a, const superk::PairStat &b) { return a.key < b.key; });
@@ -296,14 +288,10 @@ extern "C" int dbgk_super_resolve(dbgk_super *s, dbgk_super_summary *out)
 	if (pieces.size() >= (1ull << 32)) return DBGK_ERR_CAPACITY;
 
 	// every written slice in one launch
-	(void)hipFree(s->d_slices);
-	s->d_slices = nullptr;
+	s->d_slices.release();
 	if (slice_bytes) {
-		superk::Piece *d_pieces = nullptr;
-		if (hipMalloc(&s->d_slices, slice_bytes + 16) != hipSuccess || hipMalloc(&d_pieces, pieces.size() * sizeof(superk::Piece)) != hipSuccess) {
-			(void)hipFree(d_pieces);
-			return DBGK_ERR_NOMEM;
-		}
+		DevBuf<superk::Piece> d_pieces;
+		if (s->d_slices.reserve(slice_bytes + 16) || d_pieces.reserve(pieces.size() * sizeof(superk::Piece))) return DBGK_ERR_NOMEM;
 		int rc = DBGK_OK;
 		auto step = [&](hipError_t e) { if (e != hipSuccess && !rc) rc = hip_fail(e, "dbgk_super_resolve", __LINE__); };
 		step(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(superk::Piece), hipMemcpyHostToDevice, l->stream));
@@ -318,7 +306,6 @@ extern "C" int dbgk_super_resolve(dbgk_super *s, dbgk_super_summary *out)
 		step(hipStreamSynchronize(l->stream));
 		float ms = 0;
 		if (!rc) step(hipEventElapsedTime(&ms, l->ev[0], l->ev[1]));
-		(void)hipFree(d_pieces);
 		if (rc) return rc;
 		s->stats.ms_slices = ms;
 	}
