@@ -15,12 +15,17 @@ struct L1Row {
 	Fn fn;
 	uint32_t lds;
 };
-template <int DBG, int WIDE_D, int C, bool RAGGED, bool LIN, bool... REST>
-constexpr uint32_t uniform_lds() { return LIN ? sizeof(UniformLdsLin<LIN ? C : 8>) : sizeof(UniformLds); }
+template <int DBG, int WIDE_D, int C, bool RAGGED, bool LIN, bool REG, bool PACKED, bool FULL, bool K17>
+constexpr uint32_t uniform_lds()
+{
+	return LIN ? sizeof(UniformLdsLin<LIN ? C : 8>) : uniform_pipelined(DBG, WIDE_D, RAGGED, LIN, REG, K17) ? sizeof(UniformPipeLds) : sizeof(UniformLds);
+}
+template <int WIDE_D, int C, bool K17>
+constexpr uint32_t prefix_lds() { return K17 ? sizeof(PrefixPipeLds) : sizeof(PrefixLds); }
 #define DBGK_ROW(...) {l1_uniform(__VA_ARGS__), &k_extract_scatter_uniform<__VA_ARGS__>, uniform_lds<__VA_ARGS__>()},
 static const L1Row<decltype(&k_extract_scatter_uniform<>)> kL1UniformRows[] = {DBGK_L1_UNIFORM_ROWS(DBGK_ROW)};
 #undef DBGK_ROW
-#define DBGK_ROW(...) {l1_prefix(__VA_ARGS__), &k_extract_scatter_prefix<__VA_ARGS__>, sizeof(PrefixLds)},
+#define DBGK_ROW(...) {l1_prefix(__VA_ARGS__), &k_extract_scatter_prefix<__VA_ARGS__>, prefix_lds<__VA_ARGS__>()},
 static const L1Row<decltype(&k_extract_scatter_prefix<>)> kL1PrefixRows[] = {DBGK_L1_PREFIX_ROWS(DBGK_ROW)};
 #undef DBGK_ROW
 #define DBGK_ROW(...) {l1_flat(__VA_ARGS__), &k_extract_scatter<__VA_ARGS__>, sizeof(ScatterLds)},
@@ -151,6 +156,10 @@ static int launch_l1(dbgk_handle *h, const L1Plan &plan, const ReadBatch &rb, co
 		int rc = DBGK_ERR_ARG;
 		switch (l.form.family) {
 		case L1Family::Uniform: {
+			if (g.n_lanes >> 32) { // (the kernels count tiles in 32 bits; uniform_mode never plans such a launch)
+				g_last_error = "level 1: a launch of 2^32 lanes or more";
+				return DBGK_ERR_ARG;
+			}
 			ReadBatch r = rb;
 			if (l.n_reads != n_reads) { // regular tiles / the reads behind them: equal lengths, the launch's own reads
 				if (r.packed) r.packed += l.first_read * g.L / 16; // (a whole number of words: a tile is a multiple of 16 bases)

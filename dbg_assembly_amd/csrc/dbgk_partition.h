@@ -271,10 +271,14 @@ __device__ __forceinline__ uint32_t scan_hist(LDS &L)
 // The same prefix sum computed by EVERY wave for itself (level 1, whose fan-out is small next to its 16 waves): lane l of a wave owns
 // the buckets [E l, E l + E), E = ceil(n_buckets / 64) <= 16, scans them with wave shuffles and writes lbase -- all waves write the
 // same values -- so no wave_tot exchange and no barrier inside the scan: a wave reads back only what it has written itself.
+// lbase_off: where the first indices go, in words from L.lbase; first: the first index of bucket 0 (the pipelined level 1 counts in bytes
+// and starts at the stage buffer's own LDS offset: its lbase entries are addresses)
 template <class LDS>
-__device__ __forceinline__ void scan_hist_per_wave(LDS &L, uint32_t n_buckets, uint32_t hist_off = 0u) // hist_off: the histogram to scan, in words from L.hist (the pipelined level 1 has two)
+__device__ __forceinline__ void scan_hist_per_wave(LDS &L, uint32_t n_buckets, uint32_t hist_off = 0u, // hist_off: the histogram to scan, in words from L.hist (the pipelined level 1 has two)
+                                                   uint32_t lbase_off = 0u, uint32_t first = 0u)
 {
 	const uint32_t *hist = L.hist + hist_off;
+	uint32_t *lbase = L.lbase + lbase_off;
 	const uint32_t lane = fresh_tid() & 63u;
 	const uint32_t E = (n_buckets + 63u) >> 6; // (wave-uniform)
 	uint32_t sum = 0;
@@ -288,12 +292,12 @@ __device__ __forceinline__ void scan_hist_per_wave(LDS &L, uint32_t n_buckets, u
 		const uint32_t n = __shfl_up(inc, off, 64);
 		if ((int)lane >= off) inc += n;
 	}
-	uint32_t run = inc - sum;
+	uint32_t run = inc - sum + first;
 	for (uint32_t j = 0; j < E; j++) {
 		const uint32_t b = E * lane + j;
 		if (b < (uint32_t)LDS::kMaxB) {
 			const uint32_t c = hist[b];
-			L.lbase[b] = run;
+			lbase[b] = run;
 			run += c;
 		}
 	}
@@ -319,15 +323,59 @@ __device__ __forceinline__ uint32_t wave_scan_inclusive_dpp(uint32_t v)
 // one 16-byte store from the same registers: no loop, no guard, no second read of the histogram, no LDS round trip inside the scan.
 constexpr uint32_t kScanStraightB = 256;
 template <class LDS>
-__device__ __forceinline__ void scan_hist_per_wave_256(LDS &L, uint32_t hist_off = 0u)
+__device__ __forceinline__ void scan_hist_per_wave_256(LDS &L, uint32_t hist_off = 0u, uint32_t lbase_off = 0u, uint32_t first = 0u) // (as scan_hist_per_wave)
 {
 	static_assert(LDS::kMaxB >= (int)kScanStraightB && offsetof(LDS, hist) % 16 == 0 && offsetof(LDS, lbase) % 16 == 0, "16-byte LDS accesses of whole entries");
 	const uint32_t lane = fresh_tid() & 63u;
-	const uint4 v = *reinterpret_cast<const uint4 *>(L.hist + hist_off + 4u * lane); // (hist_off: a multiple of four words)
+	hist_off &= ~3u; // (multiples of four words, said so that the accesses are 16 bytes wide)
+	lbase_off &= ~3u;
+	const uint4 v = *reinterpret_cast<const uint4 *>(L.hist + hist_off + 4u * lane);
 	const uint32_t sum = (v.x + v.y) + (v.z + v.w);
-	const uint32_t run = wave_scan_inclusive_dpp(sum) - sum;
-	*reinterpret_cast<uint4 *>(L.lbase + 4u * lane) = make_uint4(run, run + v.x, run + v.x + v.y, run + v.x + v.y + v.z);
+	const uint32_t run = wave_scan_inclusive_dpp(sum) - sum + first;
+	*reinterpret_cast<uint4 *>(L.lbase + lbase_off + 4u * lane) = make_uint4(run, run + v.x, run + v.x + v.y, run + v.x + v.y + v.z);
 }
+
+// ---- the pipelined level-1 forms (L1Pipe, dbgk_partition_l1.h): their bucket word and their small LDS arrays --------------------
+// Ranks are counted in BYTES -- the rank atomic adds the record size, 8 or 4 -- and a position's bucket word says where its
+// histogram entry lies instead of which bucket it is:
+//     (LDS address of the entry) << 17 | rank in bytes
+// rank <= 8 * (16 * kL1Threads - 1) < 2^17.  The entry's address is its byte offset inside the histogram area, < 2 * (kL1MaxB + 64) * 4
+// < 2^14, plus the area's own LDS address: the area lies behind the tile's packed words at the start of the dynamic LDS (UniformPipeLds,
+// PrefixPipeLds), and the kernels that use it have no static LDS in front of that (tests/test_l1_bucket_word_cpu.py reads it from the
+// built library), so the sum stays inside the field's 15 bits.  The kernels take every address from the symbol, in scalar arithmetic.
+// The scan runs over byte counts and starts at the stage buffer's LDS address, so a bucket's lbase entry is the ADDRESS of its
+// first staged record, and lbase lies at one fixed distance from either histogram: a record is staged at
+// lbase-word(entry address + distance) + rank  -- a shift, an AND, an add, and no LDS base added to any of them (lds_ptr).
+constexpr uint32_t kL1HistWords = (uint32_t)kL1MaxB + 64u; // one histogram: the buckets and a dummy bin per lane (positions without a record)
+constexpr uint32_t kL1RankBits = 17;
+static_assert(8u * (16u * (uint32_t)kL1Threads - 1u) < (1u << kL1RankBits) && 2u * kL1HistWords * 4u <= (1u << (32u - kL1RankBits)), "the two fields of the bucket word");
+__host__ __device__ __forceinline__ uint32_t l1_bucket_word_pack(uint32_t entry_off, uint32_t rank_bytes)
+{
+	return (entry_off << kL1RankBits) | rank_bytes;
+}
+__host__ __device__ __forceinline__ void l1_bucket_word_unpack(uint32_t word, uint32_t &entry_off, uint32_t &rank_bytes)
+{
+	entry_off = word >> kL1RankBits;
+	rank_bytes = word & ((1u << kL1RankBits) - 1u);
+}
+// The small arrays come in FRONT of the 128 KiB stage buffer in the kernel's LDS: every access to them is an LDS instruction with
+// a constant offset (16 bits: 64 KiB), no base added to the index.  Two histograms (consecutive tiles rank in turn) and the first
+// addresses of either; the lbase half that is not in use carries the reserved places from the reserving threads to the copying waves.
+struct L1PipeLds {
+	static constexpr int kThreads = kL1Threads;
+	static constexpr int kRecords = kL1Threads * 16;
+	static constexpr int kMaxB = kL1MaxB;
+	static constexpr int kBpt = kL1MaxB / kL1Threads;
+	uint32_t hist[2 * kL1HistWords];
+	uint32_t lbase[kL1HistWords + kL1MaxB]; // lbase[h * kL1HistWords + b] belongs to hist[h * kL1HistWords + b]
+};
+constexpr uint32_t kL1LbaseDist = 2u * kL1HistWords * 4u; // bytes from a histogram entry to its lbase entry
+// LDS addresses as integers: where an index is already a byte count, a pointer made from it costs no "+ base" instruction (the base
+// of the dynamic LDS is a symbol the compiler adds with a VALU instruction of its own, even when it is 0)
+__device__ __forceinline__ uint32_t lds_address(const void *p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p; }
+template <class T>
+__device__ __forceinline__ T *lds_ptr(uint32_t address) { return (T *)(__attribute__((address_space(3))) T *)(uintptr_t)address; }
+static_assert(offsetof(L1PipeLds, hist) == 0 && offsetof(L1PipeLds, lbase) == kL1LbaseDist && sizeof(L1PipeLds) % 16 == 0, "L1PipeLds");
 
 // Phases of the workgroup-wide bucket scatter of one tile (<= 16 records per thread).
 //   br[u] = (bucket << 16) | rank-within-bucket, bucket >= kMaxBuckets = no record

@@ -27,16 +27,21 @@ namespace dbgk {
 // ZERO_POSSIBLE = false (SPECIAL or ROLL32 forms at k >= 31, chosen per wave and tile by the caller, l1_no_zero_key): no window of the
 // wave can have the canonical key 0 -- none of the packed words its lanes funnel their windows from is all A / N or all T -- so the
 // positions carry no test for it: no 64-bit compare, no zero flag, and the bucket word straight from the slot.  Returns false.
+// RANK_BYTES = 8 or 4 (the pipelined tile loop, L1Pipe; LDS = L1PipeLds): ranks in bytes of the record size and the bucket word that
+// carries the histogram entry's place (l1_bucket_word_pack), hist_off then being the LDS address of the histogram in use;
+// 0: bkt[i] = (bucket << 16) | rank
 struct NoMid { __device__ __forceinline__ void operator()(uint32_t) const {} };
 template <int WIDE_D, int NPOS = 16, class LDS = ScatterLds, bool SPECIAL = false, bool ROLL32 = SPECIAL, bool IN_REGS = false, bool ZERO_POSSIBLE = true,
-          class Mid = NoMid>
+          int RANK_BYTES = 0, class Mid = NoMid>
 __device__ __forceinline__ bool l1_positions(LDS &L, const PartGeom &G, Chunk16 c, uint32_t tid, uint64_t head_mask, uint32_t rc_shift,
                                              uint32_t rel_mask, uint32_t q_shift, uint32_t (&bkt)[16], uint64_t *rec = nullptr,
-                                             uint32_t hist_off = 0u, Mid mid = Mid()) // hist_off: the histogram in use, in words from L.hist
+                                             uint32_t hist_off = 0u, Mid mid = Mid()) // hist_off: the histogram in use, in words from L.hist (RANK_BYTES: its LDS address)
 {
 	static_assert(!IN_REGS || SPECIAL || ROLL32 || WIDE_D == 3, "records in registers: regular tiles of a graph handle, or a KFREQ handle with direct blocks (nothing to patch)");
 	static_assert(ZERO_POSSIBLE || ((SPECIAL || ROLL32) && WIDE_D != 3), "the positions without the zero-key test: the 32-bit-roll forms of a graph handle");
-	uint32_t *const hh = L.hist + (IN_REGS ? hist_off : 0u);
+	static_assert(RANK_BYTES == 0 || (IN_REGS && (RANK_BYTES == 8 || (RANK_BYTES == 4 && WIDE_D == 3))),
+	              "ranks in bytes: the pipelined tile loop, by the size of the records its L1Pipe stages (4: only a KFREQ handle with direct blocks has 32-bit records)");
+	[[maybe_unused]] uint32_t *const hh = L.hist + ((IN_REGS && !RANK_BYTES) ? hist_off : 0u);
 	// The per-position path assumes both neighbours exist; the ~2 % of positions at a read's
 	// first / last window are patched afterwards (rare per lane, so the loop stays lean).
 	// Complemented neighbour codes (3 - x == x ^ 3) for all 16 positions at once:
@@ -45,7 +50,8 @@ __device__ __forceinline__ bool l1_positions(LDS &L, const PartGeom &G, Chunk16 
 	bool zero_any = false; // some canonical k-mer of this lane is 0 (the key-0 node is kept apart, DBGgraph.cpp:418)
 	uint32_t zero_acc = 0u;
 #pragma unroll
-	for (uint32_t i = NPOS; i < 16; i++) bkt[i] = (uint32_t)kL1MaxB << 16; // lanes own NPOS positions: the rest never holds a record
+	for (uint32_t i = NPOS; i < 16; i++) // lanes own NPOS positions: the rest never holds a record
+		bkt[i] = RANK_BYTES ? l1_bucket_word_pack(hist_off + (uint32_t)kL1MaxB * 4u, 0u) : (uint32_t)kL1MaxB << 16;
 #pragma unroll
 	for (uint32_t i = 0; i < (uint32_t)NPOS; i++) {
 		mid(i);
@@ -125,7 +131,12 @@ __device__ __forceinline__ bool l1_positions(LDS &L, const PartGeom &G, Chunk16 
 		}
 		// positions without a record rank themselves in a per-lane dummy bin: no exec juggling around the LDS atomic
 		const uint32_t b = (valid && !zero) ? bucket : (uint32_t)kL1MaxB + (tid & 63u);
-		bkt[i] = (b << 16) | atomicAdd(&hh[b], 1u);
+		if constexpr (RANK_BYTES != 0) { // (the entry's address is formed for the atomic anyway: in this shape it is the bucket word's upper field)
+			const uint32_t entry = (b << 2) + hist_off;
+			bkt[i] = l1_bucket_word_pack(entry, atomicAdd(lds_ptr<uint32_t>(entry), (uint32_t)RANK_BYTES));
+		} else {
+			bkt[i] = (b << 16) | atomicAdd(&hh[b], 1u);
+		}
 		// roll to the next position (DBGgraph.cpp:71-73)
 		if constexpr (ROLL32) {
 			const uint32_t klo = (uint32_t)c.kbit, khi = (uint32_t)(c.kbit >> 32);
@@ -169,17 +180,18 @@ __device__ __forceinline__ bool l1_positions(LDS &L, const PartGeom &G, Chunk16 
 			}
 		}
 		return zero_acc != 0u;
+	} else { // (the records are parked in the stage buffer)
+		for (uint32_t fix = (WIDE_D == 3 || (!SPECIAL && G.kf)) ? 0u : ((no_l | no_r) & c.valid); fix; fix &= fix - 1u) {
+			const uint32_t i = (uint32_t)__builtin_ctz(fix);
+			const bool fwd = !((rev_mask >> ((uint32_t)NPOS - 1u - i)) & 1u), nl = (no_l >> i) & 1u, nr = (no_r >> i) & 1u;
+			uint64_t rec = L.stage[i * kL1Threads + tid];
+			uint32_t lb = ((uint32_t)rec >> 3) & 7u, rbb = (uint32_t)rec & 7u;
+			if (fwd ? nl : nr) lb = 4u;
+			if (fwd ? nr : nl) rbb = 4u;
+			L.stage[i * kL1Threads + tid] = (rec & ~63ull) | (lb << 3) | rbb;
+		}
+		return zero_any;
 	}
-	for (uint32_t fix = (WIDE_D == 3 || (!SPECIAL && G.kf)) ? 0u : ((no_l | no_r) & c.valid); fix; fix &= fix - 1u) {
-		const uint32_t i = (uint32_t)__builtin_ctz(fix);
-		const bool fwd = !((rev_mask >> ((uint32_t)NPOS - 1u - i)) & 1u), nl = (no_l >> i) & 1u, nr = (no_r >> i) & 1u;
-		uint64_t rec = L.stage[i * kL1Threads + tid];
-		uint32_t lb = ((uint32_t)rec >> 3) & 7u, rbb = (uint32_t)rec & 7u;
-		if (fwd ? nl : nr) lb = 4u;
-		if (fwd ? nr : nl) rbb = 4u;
-		L.stage[i * kL1Threads + tid] = (rec & ~63ull) | (lb << 3) | rbb;
-	}
-	return zero_any;
 }
 
 // after the positions of a tile: reserve, scan, move the parked records into sorted order, copy out
@@ -416,8 +428,19 @@ constexpr int kPkWords = 1792 * kTileThreads / 1024; // packed words of one tile
 struct UniformLds {
 	ScatterLds s;
 	uint32_t pk[kPkWords];
-	uint32_t gbase[kL1MaxB]; // pipelined regular tiles: a bucket's reserved place, from the thread that reserved it to the wave that copies the run
 };
+struct UniformPipeLds { // the pipelined tile loop (L1Pipe): the packed words and the small arrays first, in reach of an LDS instruction's offset
+	uint32_t pk[kPkWords]; // (at the very start: a lane's five words are two ds_read2_b32 and a ds_read_b32, whose offsets reach 1 KiB)
+	L1PipeLds s;
+	uint64_t stage[L1PipeLds::kRecords];
+};
+static_assert(offsetof(UniformPipeLds, stage) <= 64 * 1024 && offsetof(UniformPipeLds, stage) % 16 == 0 && sizeof(UniformPipeLds) <= 160 * 1024, "one workgroup per CU");
+static_assert(offsetof(UniformPipeLds, s) % 16 == 0 && offsetof(UniformPipeLds, s) + sizeof(L1PipeLds::hist) <= (1u << (32u - kL1RankBits)), "a histogram entry's LDS address is a field of the bucket word");
+// which instantiations of k_extract_scatter_uniform run the pipelined tile loop (and have its LDS layout)
+constexpr bool uniform_pipelined(int dbg, int wide_d, bool ragged, bool lin, bool reg, bool k17)
+{
+	return !lin && dbg == 0 && (reg || k17 || (wide_d == 3 && !ragged));
+}
 template <int C>
 struct UniformLdsLin {
 	ScatterLdsLin<C> s;
@@ -472,24 +495,30 @@ __device__ __forceinline__ void l1_key0_from_chunk(Chunk16 c, uint64_t head_mask
 // (round 5: level 1 4.74 -> 3.92 ms on cfg2, profiles/r05_l1_pipelined_ab.txt.)  The copy-out of a tile runs INSIDE the position loop
 // of the next one -- a run's LDS read and its store between two positions' arithmetic, instead of a phase of its own in which the
 // vector ALUs idle.  The records of a tile stay in registers until they are staged in sorted order (nothing is parked in the stage
-// buffer, which holds the tile before), the ranks of consecutive tiles go to two histograms in turn (the second one lives in the
-// descriptor array: the copying wave holds its buckets' descriptors in registers -- lane l of wave w copies bucket w + 16 l; count and
-// first staged index it reads itself, the reserved place comes from the reserving thread through `gbase` in LDS), the next tile is
+// buffer, which holds the tile before), the ranks of consecutive tiles go to two histograms in turn (the copying wave
+// holds its buckets' descriptors in registers -- lane l of wave w copies bucket w + 16 l; count and first staged record it reads
+// itself, the reserved place comes from the reserving thread through LDS), the next tile is
 // opened in the tail, and a tile costs TWO barriers: (C) ranks complete and the stage buffer read out, (E) records staged, the next
 // tile's words and cleared histogram in place.  Per tile:
 //     positions (l1_positions<..., IN_REGS>, mid(i) = copy_run(i)); copy_rest; fetch of the tile after; barrier (C);
 //     tail(rec, bkt, ..., open_next)   -- reserve, scan, stage, hand-over, open_next(histogram to clear), barrier (E)
 // and after the last tile copy_rest(0).  REC32: a KFREQ handle with direct blocks -- 32-bit records, four per lane and store, the
 // stage buffer used as 32-bit words.
-template <bool REC32>
+// LDS (L1PipeLds, dbgk_partition.h): the small arrays near the start of the kernel's LDS, the stage buffer STAGE_OFF bytes behind
+// them.  Counts, ranks and first indices are in BYTES (record size 8, REC32: 4) and lbase holds addresses: a record is staged at
+// lbase-of-its-histogram-entry + rank, and what reads a count shifts it back once per thread and tile (c_t, d_lo).  The reserved
+// places travel through the lbase half of the OTHER histogram: its addresses were last read before barrier (E) of the tile before
+// and are next written behind barrier (C) of the tile after; d_gb is read in between.
+template <bool REC32, uint32_t STAGE_OFF>
 struct L1Pipe {
 	static constexpr uint32_t kWaves = kL1Threads / 64;
-	static constexpr uint32_t kHist2 = (uint32_t)((offsetof(ScatterLds, desc) - offsetof(ScatterLds, hist)) / 4u);
-	static_assert(sizeof(ScatterLds::desc) >= sizeof(ScatterLds::hist), "the second histogram lives in the descriptor array");
+	static constexpr uint32_t kHist2 = kL1HistWords;
+	static constexpr uint32_t kRecShift = REC32 ? 2u : 3u; // log2 of the record size: counts and ranks are in bytes of it
 	static_assert(kL1MaxB <= kL1Threads, "thread b reserves bucket b");
 	static_assert(kHist2 % 4u == 0u, "scan_hist_per_wave_256 reads either histogram sixteen bytes at a time");
-	ScatterLds &L;
-	uint32_t *const gbase; // LDS, >= n1 words: a bucket's reserved place, from the thread that reserved it to the wave that copies the run
+	static_assert(STAGE_OFF % 16u == 0u && STAGE_OFF >= sizeof(L1PipeLds) && 160u * 1024u / 4u < (1u << 16),
+	              "a run's first staged record, in records from LDS address 0, travels in sixteen bits of d_lo");
+	L1PipeLds &L;
 	const PartGeom &G;
 	const PartStore &P;
 	Counters *const ctr;
@@ -497,11 +526,19 @@ struct L1Pipe {
 	uint64_t *out;
 	uint32_t *cnt;
 	uint64_t bucket_stride;
-	uint32_t d_lo = 0u, d_gb = 0u; // the runs this wave copies out of the stage buffer: lane l = records << 16 | first staged index, and the global base
+	uint32_t cap32; // min(cap1, 2^32 - 1)
+	uint32_t d_lo = 0u, d_gb = 0u; // the runs this wave copies out of the stage buffer: lane l = records << 16 | first staged record (counted in records
+	                               // from the start of the LDS), and the global base
 	uint32_t cur = 0u;             // the histogram of the current tile, in words from L.hist: 0 or kHist2
 
-	__device__ __forceinline__ L1Pipe(ScatterLds &L_, uint32_t *gbase_, const PartGeom &G_, const PartStore &P_, Counters *ctr_)
-	    : L(L_), gbase(gbase_), G(G_), P(P_), ctr(ctr_)
+	__device__ __forceinline__ uint32_t lds0() const { return lds_address(&L); }                      // (a constant: scalar arithmetic)
+	__device__ __forceinline__ uint32_t cur_at() const // the current histogram's LDS address
+	{
+		uint32_t at = lds0() + (uint32_t)offsetof(L1PipeLds, hist) + 4u * cur;
+		asm volatile("" : "+s"(at)); // (one scalar: folded into the index it would cost an add per position in front of the shift-and-add)
+		return at;
+	}
+	__device__ __forceinline__ L1Pipe(L1PipeLds &L_, const PartGeom &G_, const PartStore &P_, Counters *ctr_) : L(L_), G(G_), P(P_), ctr(ctr_)
 	{
 		tid = fresh_tid();
 		lane = tid & 63u;
@@ -512,36 +549,45 @@ struct L1Pipe {
 		out = P.l1 + (uint64_t)sub * G.cap1;
 		cnt = P.cnt1 + sub;
 		bucket_stride = (uint64_t)G.n_sub * G.cap1;
+		cap32 = __builtin_amdgcn_readfirstlane((uint32_t)(G.cap1 >> 32) ? 0xFFFFFFFFu : (uint32_t)G.cap1);
 	}
-	__device__ __forceinline__ uint32_t *stage32() const { return reinterpret_cast<uint32_t *>(L.stage); }
+	// staged record i, counted in records from LDS address 0 (d_lo)
+	__device__ __forceinline__ uint64_t staged64(uint32_t i) const { return *lds_ptr<const uint64_t>(8u * i); }
+	__device__ __forceinline__ uint32_t staged32(uint32_t i) const { return *lds_ptr<const uint32_t>(4u * i); }
 
 	__device__ __forceinline__ void copy_run(uint32_t kk, uint64_t &slow) const // (kk: wave-uniform)
 	{
 		const uint32_t lo = __builtin_amdgcn_readlane(d_lo, kk), dst = __builtin_amdgcn_readlane(d_gb, kk);
 		const uint32_t n = lo >> 16, src = lo & 0xFFFFu;
 		if (n == 0u) return;
-		if ((uint64_t)dst + n > G.cap1) { // the bucket is full: after the positions, record by record
+		// the bucket is full: after the positions, record by record.  (dst + n > cap1 as two scalar compares of 32-bit halves -- there
+		// is no scalar 64-bit compare; a cap1 of 2^32 and more is taken as 2^32 - 1: a run that would cross 2^32 goes the slow way,
+		// which tests every record against cap1 itself)
+		const uint64_t end = (uint64_t)dst + n;
+		uint32_t end_hi = (uint32_t)(end >> 32);
+		asm volatile("" : "+s"(end_hi)); // (or the two tests are put together again into one 64-bit compare on the vector ALU)
+		if (end_hi != 0u || (uint32_t)end > cap32) {
 			slow |= 1ull << kk;
 			return;
 		}
 		// (the bucket's address is scalar arithmetic redone per run: hoisted out of the tile loop, fifteen 64-bit bases cost more
-		// registers than the kernel has)
-		uint32_t b = wave + kWaves * kk;
-		asm volatile("" : "+s"(b));
+		// registers than the kernel has -- and fifteen bucket numbers come back from a parking register one v_readlane each)
+		uint32_t w = wave;
+		asm volatile("" : "+s"(w));
+		const uint32_t b = w + kWaves * kk;
 		if constexpr (REC32) { // (a level-1 record is (place in the bucket) << 6 | 4 and travels as 32 bits, scatter_stage_copy)
 			static_assert(kSubStores == 1, "the 32-bit level-1 store is addressed without sub-stores");
 			uint32_t *o32 = reinterpret_cast<uint32_t *>(out) + (uint64_t)b * G.cap1 + dst;
-			const uint32_t *s32 = stage32();
 			typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 			if (n >= 4u) { // (wave-uniform) the lane whose four would reach past the run takes the run's LAST four instead: one store
 				// instruction per 256 records whatever the run's length, a few records written twice with the same value
 				for (uint32_t i = 4u * lane; i < n; i += 256u) {
 					const uint32_t j = min(i, n - 4u);
-					const u32x4_a4 v = {s32[src + j], s32[src + j + 1u], s32[src + j + 2u], s32[src + j + 3u]};
+					const u32x4_a4 v = {staged32(src + j), staged32(src + j + 1u), staged32(src + j + 2u), staged32(src + j + 3u)};
 					*reinterpret_cast<u32x4_a4 *>(o32 + j) = v;
 				}
 			} else if (lane < n) {
-				o32[lane] = s32[src + lane];
+				o32[lane] = staged32(src + lane);
 			}
 			return;
 		}
@@ -551,12 +597,12 @@ struct L1Pipe {
 			// run's last TWO instead (one record written twice with the same value: no 8-byte store instruction behind the others)
 			for (uint32_t i = 2u * lane; i < n; i += 128u) {
 				const uint32_t j = min(i, n - 2u);
-				const uint64_t a = L.stage[src + j], b2 = L.stage[src + j + 1u];
+				const uint64_t a = staged64(src + j), b2 = staged64(src + j + 1u);
 				const u32x4_a8 v = {(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b2, (uint32_t)(b2 >> 32)};
 				*reinterpret_cast<u32x4_a8 *>(o + j) = v;
 			}
 		} else if (lane == 0u) {
-			o[0] = L.stage[src];
+			o[0] = staged64(src);
 		}
 	}
 	__device__ __forceinline__ void copy_slow(uint64_t slow) const
@@ -569,7 +615,7 @@ struct L1Pipe {
 			uint64_t *o = out + (uint64_t)b * G.n_sub * G.cap1 + dst;
 			uint32_t *o32 = reinterpret_cast<uint32_t *>(out) + (uint64_t)b * G.cap1 + dst;
 			for (uint32_t i = lane; i < n; i += 64u) {
-				const uint64_t rcd = REC32 ? (uint64_t)stage32()[src + i] : L.stage[src + i];
+				const uint64_t rcd = REC32 ? (uint64_t)staged32(src + i) : staged64(src + i);
 				if ((uint64_t)dst + i < G.cap1) {
 					if constexpr (REC32) o32[i] = (uint32_t)rcd;
 					else o[i] = rcd;
@@ -591,30 +637,44 @@ struct L1Pipe {
 		// one reservation per non-empty bucket, by thread b as everywhere else: consecutive lanes, consecutive counters -- a handful of
 		// atomic REQUESTS per tile.  (Reserved by the copying lanes themselves -- bucket w + 16 l, sixteen instructions of nine scattered
 		// lanes -- the same 144 atomics took 23 ms instead of 4.7: the counters' five cache lines saw sixteen times the requests.)
-		const uint32_t c_t = tid < G.n1 ? L.hist[cur + tid] : 0u;
+		uint32_t n1 = G.n1;
+		asm volatile("" : "+s"(n1)); // (scalar compares here, not condition masks held across the tile loop)
+		const uint32_t c_t = tid < n1 ? L.hist[cur + tid] >> kRecShift : 0u; // (the histogram counts bytes)
 		const uint32_t g_t = c_t ? atomicAdd(&cnt[tid * G.n_sub], c_t) : 0u;
 		const uint32_t c_mine = lane < per_wave ? L.hist[cur + mine] : 0u;
-		if (G.n1 <= kScanStraightB) scan_hist_per_wave_256(L, cur); // (kernel-uniform) four buckets per lane, straight-line
-		else scan_hist_per_wave(L, G.n1, cur);
-		d_lo = (c_mine << 16) | (lane < per_wave ? L.lbase[mine] : 0u);
+		if (n1 <= kScanStraightB) scan_hist_per_wave_256(L, cur, cur, lds0() + STAGE_OFF); // (kernel-uniform) four buckets per lane, straight-line
+		else scan_hist_per_wave(L, n1, cur, cur, lds0() + STAGE_OFF);
+		d_lo = (c_mine << (16u - kRecShift)) | (lane < per_wave ? L.lbase[cur + mine] >> kRecShift : 0u);
+		// a record's address: the lbase word that lies kL1LbaseDist behind its histogram entry, plus its rank
+		auto first_of = [&](uint32_t word) {
+			uint32_t entry, rank;
+			l1_bucket_word_unpack(word, entry, rank);
+			return *lds_ptr<const uint32_t>(entry + kL1LbaseDist);
+		};
+		auto put = [&](uint32_t first, uint32_t word, uint64_t r) {
+			uint32_t entry, rank;
+			l1_bucket_word_unpack(word, entry, rank);
+			if constexpr (REC32) *lds_ptr<uint32_t>(first + rank) = (uint32_t)r;
+			else *lds_ptr<uint64_t>(first + rank) = r;
+		};
 		if (SURE && __builtin_amdgcn_ballot_w64(zero_seen) == 0ull) { // (wave-uniform) every record of every lane has a bucket
 			uint32_t at[C];
 #pragma unroll
-			for (int u = 0; u < C; u++) at[u] = L.lbase[bkt[u] >> 16];
+			for (int u = 0; u < C; u++) at[u] = first_of(bkt[u]);
 #pragma unroll
-			for (int u = 0; u < C; u++) L.stage[at[u] + (bkt[u] & 0xFFFFu)] = rec[u];
+			for (int u = 0; u < C; u++) put(at[u], bkt[u], rec[u]);
 		} else {
+			// (a position without a record ranked itself in a dummy bin, whose entries lie behind the buckets': the entry field, and with
+			// it the whole word, is not below this)
+			const uint32_t no_bucket = l1_bucket_word_pack(cur_at() + (uint32_t)kL1MaxB * 4u, 0u);
 #pragma unroll
 			for (int u = 0; u < C; u++)
-				if ((bkt[u] >> 16) < (uint32_t)kL1MaxB) {
-					if constexpr (REC32) stage32()[L.lbase[bkt[u] >> 16] + (bkt[u] & 0xFFFFu)] = (uint32_t)rec[u];
-					else L.stage[L.lbase[bkt[u] >> 16] + (bkt[u] & 0xFFFFu)] = rec[u];
-				}
+				if (bkt[u] < no_bucket) put(first_of(bkt[u]), bkt[u], rec[u]);
 		}
-		if (tid < G.n1) gbase[tid] = g_t;
+		if (tid < n1) L.lbase[(cur ^ kHist2) + tid] = g_t;
 		open_next(cur ^ kHist2);
 		lds_barrier(); // (E) the tile is staged, the next one's packed words and cleared histogram are in place
-		d_gb = lane < per_wave ? gbase[mine] : 0u;
+		d_gb = lane < per_wave ? L.lbase[(cur ^ kHist2) + mine] : 0u;
 		cur ^= kHist2;
 	}
 };
@@ -643,8 +703,13 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 	static_assert(!PACKED || REG, "the other forms test rb.packed at run time");
 	static_assert(FULL || (REG && DBG == 0), "partly filled lanes: the pipelined regular tiles");
 	static_assert(K17 || !REG, "regular tiles: k >= 17");
-	using ULds = typename std::conditional<LIN, UniformLdsLin<LIN ? C : 8>, UniformLds>::type;
-	using SLds = typename std::conditional<LIN, ScatterLdsLin<LIN ? C : 8>, ScatterLds>::type;
+	// PIPELINED tile loop (L1Pipe): regular tiles, every batch of equal-length or mostly full-length reads from k = 17 on, and
+	// a KFREQ handle with direct blocks (WIDE_D == 3, equal-length reads of any length: 32-bit records).
+	constexpr bool kRec32 = WIDE_D == 3;
+	constexpr bool kPipe = uniform_pipelined(DBG, WIDE_D, RAGGED, LIN, REG, K17);
+	constexpr bool kZeroPerWave = K17 && !kRec32; // the 32-bit-roll forms of a graph handle: the zero-key test per wave and tile (k >= 31, l1_no_zero_key)
+	using ULds = typename std::conditional<LIN, UniformLdsLin<LIN ? C : 8>, typename std::conditional<kPipe, UniformPipeLds, UniformLds>::type>::type;
+	using SLds = typename std::conditional<LIN, ScatterLdsLin<LIN ? C : 8>, typename std::conditional<kPipe, L1PipeLds, ScatterLds>::type>::type;
 	extern __shared__ __align__(16) unsigned char lds_raw[];
 	ULds &UL = *reinterpret_cast<ULds *>(lds_raw);
 	SLds &L = UL.s;
@@ -679,11 +744,18 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 		else raw.a = raw.b = make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);
 		raw.B0 = raw.p = 0;
 		raw.n_blocks = raw.cc = raw.W = 0;
-		if (tile >= n_tiles) return raw;
+		if constexpr (REG) { // (a scalar compare of the low words: uniform_mode, dbgk_l1_form.h, refuses n_reads * Q >= 2^32 and launch_l1 checks the
+			// launch's n_lanes again, so n_tiles < 2^22 and tile + gridDim.x cannot wrap)
+			if ((uint32_t)tile >= (uint32_t)n_tiles) return raw;
+		} else {
+			if (tile >= n_tiles) return raw;
+		}
 		const uint32_t t = fresh_tid();
 		if constexpr (REG) { // every tile: kL1Threads / Q whole reads from a 16-byte boundary, all of them inside the buffer
-			raw.B0 = tile * ((uint64_t)U.tile_blocks * 16u);
-			raw.n_blocks = U.tile_blocks;
+			uint32_t tile_blocks = U.tile_blocks;
+			asm volatile("" : "+s"(tile_blocks)); // (one scalar of its own: as a part of the geometry's four-register group it came back from the parking register whole, three times per tile)
+			raw.B0 = tile * ((uint64_t)tile_blocks * 16u);
+			raw.n_blocks = tile_blocks;
 			if constexpr (PACKED) {
 				const uint32_t *words = rb.packed + (raw.B0 >> 4);
 				if (t < raw.n_blocks) raw.a = words[t];
@@ -748,31 +820,50 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 		}
 #pragma unroll
 		for (int j = 0; j < SLds::kBpt; j++) L.hist[hist_off + SLds::kBpt * tid + j] = 0;
+		if constexpr (kPipe) { // (the dummy bins as well: a rank in bytes that is never reset would grow out of its field of the bucket word)
+			if (tid < 64u) L.hist[hist_off + (uint32_t)kL1MaxB + tid] = 0;
+		}
 	};
+	// Regular tiles that fill their lanes: a lane's place in the tile's byte range depends on the thread index alone, so three words
+	// of it are worked out once and stay in registers across the tile loop -- the LDS address of the lane's first packed word, 32 - its
+	// shift, and the lane's chunk (the kernel has the three registers to spare and no more).
+	uint32_t lane_at = 0u, lane_nsh = 0u, lane_cc = 0u;
+	if constexpr (REG && FULL) {
+		const uint32_t t = fresh_tid();
+		lane_cc = t & (U.Q - 1u);
+		// (the packed stream starts one base before the lane's first window, the left neighbour -- except in a read's first chunk,
+		// whose first window has none; d + 4 <= tile_blocks + 2 < kPkWords: a tile is at most 1024 * 16 * (1 + (k - 1) / W) bases)
+		const uint32_t rel = (t >> U.lq) * U.L + (uint32_t)C * lane_cc - (lane_cc == 0u ? 0u : 1u);
+		lane_at = ((rel >> 4) << 2) + lds_address(UL.pk);
+		lane_nsh = 32u - 2u * (rel & 15u);
+	}
 	// a lane's window of 16 positions out of the tile's packed words
 	auto decode = [&](const RawU &raw, uint32_t *word_runs = nullptr) { // word_runs: l1_word_runs of the lane's packed words
 		if constexpr (REG && FULL) {
-			// Regular tiles that fill their lanes: every lane is live and every window valid, the lane's place in the tile's byte range
-			// is (its read in the tile) * L + C * chunk whatever the tile, and the masks depend on the chunk alone (first, last, other).
+			// Every lane is live and every window valid, and the masks depend on the chunk alone (first, last, other).
 			// No clamps, no `live` selects, nothing 64 bits wide, and nothing of the tile's RawU but its packed words.
-			const uint32_t t = fresh_tid();
-			const uint32_t cc = t & (U.Q - 1u);
-			const bool first = cc == 0u, last = cc == U.Q - 1u;
-			// (the packed stream starts one base before the lane's first window, the left neighbour -- except in a read's first chunk,
-			// whose first window has none; d + 4 <= tile_blocks + 2 < kPkWords: a tile is at most 1024 * 16 * (1 + (k - 1) / W) bases)
-			const uint32_t rel = (t >> U.lq) * U.L + (uint32_t)C * cc - (first ? 0u : 1u);
-			const uint32_t d = rel >> 4, sh = 2u * (rel & 15u);
-			const uint32_t x0 = UL.pk[d], x1 = UL.pk[d + 1], x2 = UL.pk[d + 2], x3 = UL.pk[d + 3], x4 = UL.pk[d + 4];
+			uint32_t at = lane_at, nsh = lane_nsh, cc = lane_cc;
+			asm volatile("" : "+v"(at), "+v"(nsh), "+v"(cc)); // (the conditions below are one compare each per tile, not condition masks held across the loop)
+			uint32_t ks = k;
+			asm volatile("" : "+s"(ks)); // (nor are the k-dependent ones: scalar compares per tile)
+			const bool first = cc == 0u, last = cc == U.Q - 1u, sh0 = nsh == 32u;
+			const uint32_t *const w = lds_ptr<const uint32_t>(at);
+			const uint32_t x0 = w[0], x1 = w[1], x2 = w[2], x3 = w[3], x4 = w[4];
 			if (word_runs) *word_runs = l1_word_runs(x0, x1, x2, x3, x4);
-			const uint32_t X0 = funnel_left(x0, x1, sh), X1 = funnel_left(x1, x2, sh), X2 = funnel_left(x2, x3, sh), X3 = funnel_left(x3, x4, sh);
+			auto funnel = [&](uint32_t hi, uint32_t lo) { // funnel_left by the lane's shift (v_alignbit takes its amount modulo 32)
+				uint32_t f = __builtin_amdgcn_alignbit(hi, lo, nsh);
+				asm volatile("" : "+v"(f));
+				return sh0 ? hi : f;
+			};
+			const uint32_t X0 = funnel(x0, x1), X1 = funnel(x1, x2), X2 = funnel(x2, x3), X3 = funnel(x3, x4);
 			const uint32_t adv = first ? 0u : 2u;
 			const uint32_t Y0 = funnel_left(X0, X1, adv), Y1 = funnel_left(X1, X2, adv), Y2 = funnel_left(X2, X3, adv), Y3 = X3 << adv;
 			Chunk16 c;
 			c.lw = first ? (X0 >> 2) : X0;
-			c.kbit = ((((uint64_t)Y0 << 32) | Y1)) >> (64u - 2u * k);
-			c.rc = revcomp_kbit(c.kbit, (int)k);
-			const bool k32 = (k >> 4) == 2u; // (regular tiles: 17 <= k <= 32, the entering bases p + k .. p + k + 15 start in word 1, at k = 32 in word 2)
-			const uint32_t wsh = 2u * (k & 15u);
+			c.kbit = ((((uint64_t)Y0 << 32) | Y1)) >> (64u - 2u * ks);
+			c.rc = revcomp_kbit(c.kbit, (int)ks);
+			const bool k32 = (ks >> 4) == 2u; // (regular tiles: 17 <= k <= 32, the entering bases p + k .. p + k + 15 start in word 1, at k = 32 in word 2)
+			const uint32_t wsh = 2u * (ks & 15u);
 			c.nb = funnel_left(k32 ? Y2 : Y1, k32 ? Y3 : Y2, wsh);
 			c.valid = (1u << C) - 1u;
 			c.has_r = last ? (1u << (C - 1)) - 1u : (1u << C) - 1u; // the read's last window has no right neighbour
@@ -808,13 +899,9 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 		c.has_l = raw.cc ? 0xFFFFu : 0xFFFEu; // its first window no left one
 		return c;
 	};
-	// PIPELINED tile loop (L1Pipe): regular tiles, every batch of equal-length or mostly full-length reads from k = 17 on, and
-	// a KFREQ handle with direct blocks (WIDE_D == 3, equal-length reads of any length: 32-bit records).
-	constexpr bool kRec32 = WIDE_D == 3;
-	constexpr bool kPipe = !LIN && DBG == 0 && (REG || K17 || (kRec32 && !RAGGED));
-	constexpr bool kZeroPerWave = K17 && !kRec32; // the 32-bit-roll forms of a graph handle: the zero-key test per wave and tile (k >= 31, l1_no_zero_key)
 	if constexpr (kPipe) {
-		L1Pipe<kRec32> pp(L, UL.gbase, G, P, ctr);
+		constexpr int kRB = kRec32 ? 4 : 8; // ranks in bytes of the record size
+		L1Pipe<kRec32, (uint32_t)(offsetof(UniformPipeLds, stage) - offsetof(UniformPipeLds, s))> pp(L, G, P, ctr);
 		const uint32_t tid = pp.tid;
 		if (blockIdx.x < n_tiles) {
 			open_tile(raw, 0u);
@@ -830,11 +917,11 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 			bool zero_seen;
 			if constexpr (kZeroPerWave) {
 				if (l1_no_zero_key(k, word_runs))
-					zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, false>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+					zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, false, kRB>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur_at(), mid);
 				else
-					zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+					zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, true, kRB>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur_at(), mid);
 			} else {
-				zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+				zero_seen = l1_positions<WIDE_D, C, SLds, REG && FULL, K17, true, true, kRB>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur_at(), mid);
 			}
 			pp.copy_rest((uint32_t)C, slow); // (more than 16 C buckets; the full ones)
 			if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
@@ -849,12 +936,11 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 			raw = nxt;
 		}
 		pp.copy_rest(0u, 0ull); // the runs of the workgroup's last tile
-		return;
 	}
 	// The LINEAR form pipelined (k >= 17, a graph handle): as L1Pipe, with the linear copy-out -- element u of the tile before (staged
 	// record u * 1024 + tid, its bucket from the tag array, its place = desc[bucket] + index) goes out in front of position u; ONE
 	// histogram, cleared by the thread that owns the entry right after it has read it; the classic scan (four barriers per tile).
-	if constexpr (LIN && K17 && DBG == 0) {
+	else if constexpr (LIN && K17 && DBG == 0) {
 		const uint32_t tid = fresh_tid();
 		const uint32_t sub = blockIdx.x % G.n_sub;
 		uint64_t *const out = P.l1 + (uint64_t)sub * G.cap1; // bucket b lives at out + b * n_sub * cap1
@@ -950,33 +1036,34 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_uniform(ReadBatc
 			for (uint32_t u = 0; u < (uint32_t)C; u++) copy_elem(u, slow);
 			if (slow) copy_slow(slow);
 		}
-		return;
-	}
-	for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-		const uint32_t tid = fresh_tid();
-		uint32_t bkt[16];
-		open_tile(raw);
-		lds_barrier();
-		const Chunk16 c = decode(raw);
-		const bool zero_seen = l1_positions<WIDE_D, C, SLds, REG>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt);
-		if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
-		// next tile
-		r0 += stride_r;
-		c0 += stride_c;
-		if (c0 >= U.Q) { c0 -= U.Q; r0 += 1u; }
-		if (DBG == 1) {
-			uint64_t xx = 0;
-#pragma unroll
-			for (int u = 0; u < 16; u++) xx ^= L.stage[u * kL1Threads + tid] + bkt[u];
-			if (xx == 0x1234567u) P.l1[threadIdx.x] = xx;
+	} else { // the plain form: a tile's phases one after the other.  (An else branch, not code behind a return: it reads L.stage, which the
+		// pipelined forms' L1PipeLds does not have, so for them it has to be a discarded constexpr branch)
+		for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+			const uint32_t tid = fresh_tid();
+			uint32_t bkt[16];
+			open_tile(raw);
 			lds_barrier();
-			raw = fetch(tile + gridDim.x, r0, c0);
-			continue;
+			const Chunk16 c = decode(raw);
+			const bool zero_seen = l1_positions<WIDE_D, C, SLds, REG>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt);
+			if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
+			// next tile
+			r0 += stride_r;
+			c0 += stride_c;
+			if (c0 >= U.Q) { c0 -= U.Q; r0 += 1u; }
+			if (DBG == 1) {
+				uint64_t xx = 0;
+#pragma unroll
+				for (int u = 0; u < 16; u++) xx ^= L.stage[u * kL1Threads + tid] + bkt[u];
+				if (xx == 0x1234567u) P.l1[threadIdx.x] = xx;
+				lds_barrier();
+				raw = fetch(tile + gridDim.x, r0, c0);
+				continue;
+			}
+			const RawU nxt = fetch(tile + gridDim.x, r0, c0);
+			if constexpr (LIN) l1_scatter_tail_linear<DBG, C, (WIDE_D >= 2)>(L, G, P, ctr, tid, bkt);
+			else l1_scatter_tail<DBG, (WIDE_D >= 2), (REG ? C : 0)>(L, G, P, ctr, tid, bkt, REG && !zero_seen);
+			raw = nxt;
 		}
-		const RawU nxt = fetch(tile + gridDim.x, r0, c0);
-		if constexpr (LIN) l1_scatter_tail_linear<DBG, C, (WIDE_D >= 2)>(L, G, P, ctr, tid, bkt);
-		else l1_scatter_tail<DBG, (WIDE_D >= 2), (REG ? C : 0)>(L, G, P, ctr, tid, bkt, REG && !zero_seen);
-		raw = nxt;
 	}
 }
 
@@ -1152,16 +1239,31 @@ struct PrefixLds {
 	unsigned long long starts[2][kL1Threads / 64]; // bit l: an entry begins at lane l of the tile (two tiles in turn: the pipelined loop opens the next tile in the tail of this one)
 };
 static_assert(sizeof(PrefixLds) <= 160 * 1024, "one workgroup per CU");
-// the pipelined loop's hand-over array lives behind the second histogram in the descriptor array: room for this many buckets
-constexpr uint32_t kPrefixPipeMaxB = (uint32_t)(sizeof(ScatterLds::desc) / 4u) - (uint32_t)(kL1MaxB + 64);
+struct PrefixPipeLds { // the pipelined tile loop (L1Pipe): the small arrays first, the stage buffer last (UniformPipeLds)
+	uint32_t pk[kPkWords];
+	L1PipeLds s;
+	uint32_t ent_start[kL1Threads];
+	uint32_t meta[kL1Threads];
+	unsigned long long starts[2][kL1Threads / 64];
+	uint64_t stage[L1PipeLds::kRecords];
+};
+static_assert(offsetof(PrefixPipeLds, stage) <= 64 * 1024 && offsetof(PrefixPipeLds, stage) % 16 == 0 && sizeof(PrefixPipeLds) <= 160 * 1024, "one workgroup per CU");
+static_assert(offsetof(PrefixPipeLds, s) == offsetof(UniformPipeLds, s), "the bucket word's entry field");
+// The level-1 buckets up to which a batch of mixed lengths takes the pipelined loop.  L1PipeLds has room for kL1MaxB; the plan
+// (dbgk_l1_form.h, L1Limits::prefix_pipe_max_b) and its tests are pinned at 960, and nothing was measured between the two: without a
+// hook the linear forms take over at kL1LinearAboveN1 = 320 buckets, far below either.
+constexpr uint32_t kPrefixPipeMaxB = 960;
+static_assert(kPrefixPipeMaxB <= (uint32_t)kL1MaxB, "L1PipeLds holds kL1MaxB buckets");
 
 template <int WIDE_D = 0, int C = 16, bool K17 = false> // K17: k >= 17 and n1 <= kPrefixPipeMaxB -- the 32-bit rolls of l1_positions and the pipelined tile loop (L1Pipe)
 __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch rb, const ReadLanes *__restrict__ ent, const PrefixTile *__restrict__ tiles,
                                                                         const PrefixTotals *__restrict__ tot, PartGeom G, PartStore P, Counters *__restrict__ ctr)
 {
 	extern __shared__ __align__(16) unsigned char lds_raw[];
-	PrefixLds &UL = *reinterpret_cast<PrefixLds *>(lds_raw);
-	ScatterLds &L = UL.s;
+	using ULds = typename std::conditional<K17, PrefixPipeLds, PrefixLds>::type;
+	using SLds = typename std::conditional<K17, L1PipeLds, ScatterLds>::type;
+	ULds &UL = *reinterpret_cast<ULds *>(lds_raw);
+	SLds &L = UL.s;
 	const uint64_t n_lanes = tot->n_lanes, n_entries = tot->n_entries;
 	const uint64_t n_tiles = (n_lanes + kL1Threads - 1) / kL1Threads;
 	const uint64_t n_words_total = (rb.n_bases + 15u) >> 4;
@@ -1212,7 +1314,10 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch
 			UL.meta[tid] = rw.meta;
 		}
 #pragma unroll
-		for (int j = 0; j < ScatterLds::kBpt; j++) L.hist[hist_off + ScatterLds::kBpt * tid + j] = 0;
+		for (int j = 0; j < SLds::kBpt; j++) L.hist[hist_off + SLds::kBpt * tid + j] = 0;
+		if constexpr (K17) { // (the dummy bins as well: a rank in bytes that is never reset would grow out of its field of the bucket word)
+			if (tid < 64u) L.hist[hist_off + (uint32_t)kL1MaxB + tid] = 0;
+		}
 	};
 	// the lane's read -- the number of entries that begin at or before this lane -- and its window of C positions
 	auto decode = [&](uint64_t tile, const PrefixTile &Mx, uint32_t sb, uint32_t *word_runs = nullptr) { // word_runs: l1_word_runs of the lane's packed words
@@ -1275,7 +1380,7 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch
 	RawP raw = fetch(blockIdx.x, M);
 	lds_barrier();
 	if constexpr (K17) { // the pipelined tile loop (L1Pipe)
-		L1Pipe<false> pp(L, reinterpret_cast<uint32_t *>(L.desc) + (kL1MaxB + 64), G, P, ctr);
+		L1Pipe<false, (uint32_t)(offsetof(PrefixPipeLds, stage) - offsetof(PrefixPipeLds, s))> pp(L, G, P, ctr);
 		const uint32_t tid = pp.tid;
 		uint32_t sb = 0u; // the bitmap of the current tile
 		if (blockIdx.x < n_tiles) {
@@ -1291,12 +1396,12 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch
 			auto mid = [&](uint32_t i) { pp.copy_run(i, slow); };
 			bool zero_seen;
 			if constexpr (WIDE_D == 3) {
-				zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, true, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+				zero_seen = l1_positions<WIDE_D, C, SLds, false, true, true, true, 8>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur_at(), mid);
 			} else { // the zero-key test per wave and tile (k >= 31, l1_no_zero_key)
 				if (l1_no_zero_key(k, word_runs))
-					zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, true, true, false>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+					zero_seen = l1_positions<WIDE_D, C, SLds, false, true, true, false, 8>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur_at(), mid);
 				else
-					zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, true, true, true>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur, mid);
+					zero_seen = l1_positions<WIDE_D, C, SLds, false, true, true, true, 8>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt, rec, pp.cur_at(), mid);
 			}
 			pp.copy_rest((uint32_t)C, slow);
 			if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
@@ -1315,34 +1420,34 @@ __global__ __launch_bounds__(kL1Threads) void k_extract_scatter_prefix(ReadBatch
 			M_next = M_after;
 		}
 		pp.copy_rest(0u, 0ull); // the runs of the workgroup's last tile
-		return;
-	}
-	for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-		const uint32_t tid = fresh_tid();
-		open(raw, M, 0u, 0u);
-		uint32_t bkt[16];
-		lds_barrier();
-		const Chunk16 c = decode(tile, M, 0u);
-		const bool zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, K17>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt);
-		if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
-		// next tile: its words and entries travel during this tile's scatter; the meta data of the tile after it as well
-		const uint64_t t1 = tile + gridDim.x, t2 = t1 + gridDim.x;
-		const RawP nxt = fetch(t1, M_next);
-		const PrefixTile M_after = tile_meta(t2);
-		lds_barrier(); // hist complete (as l1_scatter_tail begins) -- and every lane has read starts / ent_start / meta
-		if (tid < (uint32_t)(kL1Threads / 64)) UL.starts[0][tid] = 0ull; // (for the next tile: set again only after that tile's threads passed the barriers below)
-		{
-			uint64_t rec[16];
+	} else { // the plain form: a tile's phases one after the other (an else branch for the same reason as in k_extract_scatter_uniform)
+		for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+			const uint32_t tid = fresh_tid();
+			open(raw, M, 0u, 0u);
+			uint32_t bkt[16];
+			lds_barrier();
+			const Chunk16 c = decode(tile, M, 0u);
+			const bool zero_seen = l1_positions<WIDE_D, C, ScatterLds, false, K17>(L, G, c, tid, head_mask, rc_shift, rel_mask, q_shift, bkt);
+			if (zero_seen) l1_key0_from_chunk(c, head_mask, rc_shift, G.kf, ctr);
+			// next tile: its words and entries travel during this tile's scatter; the meta data of the tile after it as well
+			const uint64_t t1 = tile + gridDim.x, t2 = t1 + gridDim.x;
+			const RawP nxt = fetch(t1, M_next);
+			const PrefixTile M_after = tile_meta(t2);
+			lds_barrier(); // hist complete (as l1_scatter_tail begins) -- and every lane has read starts / ent_start / meta
+			if (tid < (uint32_t)(kL1Threads / 64)) UL.starts[0][tid] = 0ull; // (for the next tile: set again only after that tile's threads passed the barriers below)
+			{
+				uint64_t rec[16];
 #pragma unroll
-			for (int u = 0; u < 16; u++) rec[u] = L.stage[u * kL1Threads + tid];
-			uint32_t my_gbase[ScatterLds::kBpt];
-			const uint32_t sub = blockIdx.x % G.n_sub;
-			scatter_reserve_scan(L, G.n1, P.cnt1 + sub, my_gbase, G.n_sub);
-			scatter_stage_copy<16, 0, false, (WIDE_D >= 2)>(L, rec, bkt, my_gbase, G.n1, P.l1 + (uint64_t)sub * G.cap1, G.cap1, 0u, true, G, P, ctr, G.n_sub);
+				for (int u = 0; u < 16; u++) rec[u] = L.stage[u * kL1Threads + tid];
+				uint32_t my_gbase[ScatterLds::kBpt];
+				const uint32_t sub = blockIdx.x % G.n_sub;
+				scatter_reserve_scan(L, G.n1, P.cnt1 + sub, my_gbase, G.n_sub);
+				scatter_stage_copy<16, 0, false, (WIDE_D >= 2)>(L, rec, bkt, my_gbase, G.n1, P.l1 + (uint64_t)sub * G.cap1, G.cap1, 0u, true, G, P, ctr, G.n_sub);
+			}
+			raw = nxt;
+			M = M_next;
+			M_next = M_after;
 		}
-		raw = nxt;
-		M = M_next;
-		M_next = M_after;
 	}
 }
 
