@@ -4,6 +4,7 @@ Plumbing only: every compute call goes straight into the HIP library.  There is 
 fallback -- loading fails loudly if the library has not been built, and dbgk_create fails if no
 gfx950 device is present.
 """
+import collections
 import ctypes as C
 import os
 
@@ -106,6 +107,13 @@ class CorrCompactInfo(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("reads", "result_reads", "result_bases", "trimmed_reads", "trimmed_bases", "deleted_reads",
                                           "one_base", "tree", "node_limit_hits", "by_classify", "by_correct", "by_overflow")] + \
                [("ms_scan", C.c_double), ("ms_gather", C.c_double)]
+
+
+CORR_ANNOT_MAX = 120  # DBGK_CORR_ANNOT_MAX
+
+
+class CorrAnnotInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("suffix_bytes", C.c_uint64), ("ms_scan", C.c_double), ("ms_write", C.c_double)]
 
 
 class MapParams(C.Structure):
@@ -437,6 +445,9 @@ SYMBOLS = [
     ("dbgk_corr_compact_from", _i, [_vp, _vp, _vp, _vp, _u64, C.POINTER(CorrCompactInfo)]),
     ("dbgk_corr_compact_results", _i, [_vp, _vp, _vp]),
     ("dbgk_corr_compact_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("dbgk_corr_annot", _i, [_vp, C.POINTER(CorrAnnotInfo)]),
+    ("dbgk_corr_annot_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_u64)]),
+    ("dbgk_corr_annot_results", _i, [_vp, _vp, _vp]),
     ("dbgk_push_corrected", _i, [_vp, _vp]),
     ("dbgk_map_create", _i, [C.POINTER(MapParams), _i, C.POINTER(_vp)]),
     ("dbgk_map_destroy", _i, [_vp]),
@@ -475,6 +486,7 @@ SYMBOLS = [
     ("dbgk_fmt_create", _i, [C.c_int32, C.c_int32, _i, C.POINTER(_vp)]),
     ("dbgk_fmt_destroy", _i, [_vp]),
     ("dbgk_fmt_records_device", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, C.POINTER(FmtInfo)]),
+    ("dbgk_fmt_records_device_suffix", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, C.POINTER(FmtInfo)]),
     ("dbgk_fmt_records", _i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, C.POINTER(FmtInfo)]),
     ("dbgk_fmt_results", _i, [_vp, _vp, _u64]),
     ("dbgk_fmt_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
@@ -1257,6 +1269,12 @@ class _Handle:
         self.close()
 
 
+class DeviceSuffixes(collections.namedtuple("DeviceSuffixes", "d_suffix d_offsets n n_bytes")):
+    """A suffix plane in device memory: the pointer of its bytes (16-byte aligned; None with d_offsets None for all empty), the pointer of
+    its n + 1 uint64 offsets, the records and the bytes.  Corrector.annotate_device returns one; Formatter.format_device reads it where
+    it lies."""
+
+
 class Corrector(_Handle):
     """correct_error_reads on the GPU (CORRECT section of include/dbgk.h).  Defaults are the reference's: -m and -x are
     17 whatever k is.  Build the table with load_file (a 1-bit .cz file: raw blocks, then the loader's mirror) or
@@ -1360,6 +1378,27 @@ class Corrector(_Handle):
         offsets = np.empty(n + 1, dtype=np.uint64)
         _chk(lib().dbgk_corr_compact_results(self._h, bases.ctypes.data, offsets.ctypes.data), "dbgk_corr_compact_results")
         return bases[:nb], offsets
+
+    def annotate(self):
+        """the annotation of every header of the compact batch, composed on the device -> (suffix bytes uint8, offsets uint64[n + 1]);
+        the counters and device times (dbgk_corr_annot_info) are kept in `annot_info`"""
+        info = CorrAnnotInfo()
+        _chk(lib().dbgk_corr_annot(self._h, C.byref(info)), "dbgk_corr_annot")
+        self.annot_info = {f: getattr(info, f) for f, _ in CorrAnnotInfo._fields_}
+        suffix = np.empty(max(info.suffix_bytes, 1), dtype=np.uint8)
+        offsets = np.empty(info.n + 1, dtype=np.uint64)
+        _chk(lib().dbgk_corr_annot_results(self._h, suffix.ctypes.data, offsets.ctypes.data), "dbgk_corr_annot_results")
+        return suffix[:info.suffix_bytes], offsets
+
+    def annotate_device(self):
+        """annotate() without the read-back -> DeviceSuffixes(device pointer of the suffix bytes, of the n + 1 offsets, records,
+        bytes), what Formatter.format_device takes as `suffixes`"""
+        info = CorrAnnotInfo()
+        _chk(lib().dbgk_corr_annot(self._h, C.byref(info)), "dbgk_corr_annot")
+        self.annot_info = {f: getattr(info, f) for f, _ in CorrAnnotInfo._fields_}
+        s, o, n, nb = _vp(), _vp(), _u64(), _u64()
+        _chk(lib().dbgk_corr_annot_device(self._h, C.byref(s), C.byref(o), C.byref(n), C.byref(nb)), "dbgk_corr_annot_device")
+        return DeviceSuffixes(s.value, o.value, int(n.value), int(nb.value))
 
     def batch_stats(self):
         s = CorrStats()
@@ -1568,7 +1607,8 @@ class Parser(_Handle):
 
 class Formatter(_Handle):
     """A compact batch written as FASTQ (fmt 1) / FASTA (fmt 2) text on the GPU (FORMAT section of include/dbgk.h): the headers from the
-    text the parser parsed, the reads from the planes of a compact batch, an optional suffix per header from the host.  marker: 0,
+    text the parser parsed, the reads from the planes of a compact batch, an optional suffix per header from the host or, for
+    format_device, from a plane on the device (DeviceSuffixes).  marker: 0,
     or the byte that replaces the first byte of every header.  format / format_device return the info as a dict (also kept in
     `info`); results() and device() give the text."""
     _destroy = "dbgk_fmt_destroy"
@@ -1621,7 +1661,8 @@ class Formatter(_Handle):
     def format_device(self, source, planes, suffixes=None):
         """source: a Parser after a chunk (its text and records where they lie), (parser, d_text, n_text) -- a Parser and the chunk
         its last chunk_device parsed -- or the pointers (d_text, n_text, d_recs) themselves; planes: (d_bases, d_quals or None, d_offsets, n) as the device() of a Parser, Cleaner, Corrector or
-        Pairer gives them (further entries are ignored); suffixes as _suffix_plane takes them"""
+        Pairer gives them (further entries are ignored); suffixes as _suffix_plane takes them, or a DeviceSuffixes (a plane in device
+        memory, what Corrector.annotate_device returns)"""
         if isinstance(source, Parser):   # the chunk of its last call, where chunk() uploaded it or chunk_device() read it
             d_text, nt = _vp(), _u64()
             _chk(lib().dbgk_parse_text_device(source._h, C.byref(d_text), C.byref(nt)), "dbgk_parse_text_device")
@@ -1634,8 +1675,12 @@ class Formatter(_Handle):
         else:
             d_text, nt, d_recs = source
         d_bases, d_quals, d_off, n = planes[:4]
-        sd, so = self._suffix_plane(suffixes, n)
         info = FmtInfo()
+        if isinstance(suffixes, DeviceSuffixes):   # a plane on the device, read where it lies
+            _chk(lib().dbgk_fmt_records_device_suffix(self._h, d_text, nt, d_recs, d_bases, d_quals, d_off, n, suffixes.d_suffix, suffixes.d_offsets,
+                                                      C.byref(info)), "dbgk_fmt_records_device_suffix")
+            return self._done(info)
+        sd, so = self._suffix_plane(suffixes, n)
         _chk(lib().dbgk_fmt_records_device(self._h, d_text, nt, d_recs, d_bases, d_quals, d_off, n,
                                            sd.ctypes.data if sd is not None and sd.size else None, so.ctypes.data if so is not None else None,
                                            C.byref(info)), "dbgk_fmt_records_device")

@@ -33,6 +33,7 @@
 #include "dbgk_pair.h"
 #include "dbgk_parse.h"
 #include "dbgk_format.h"
+#include "dbgk_annot.h"
 #include "dbgk_gz.h"
 #include "dbgk_inflate.h"
 #include "dbgk_link.h"
@@ -475,6 +476,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_wide_links.h"
 #include "dbgk_host_stage.h"
 #include "dbgk_host_emit.h"
+#include "dbgk_host_annot.h"
 #include "dbgk_host_correct.h"
 #include "dbgk_host_spectrum.h"
 #include "dbgk_host_map.h"

@@ -21,6 +21,7 @@ struct dbgk_corr : StageDev {
 	bool have_batch = false;      // the last dbgk_corr_reads* / dbgk_corr_compact_from succeeded: batch_n reads are resident
 	uint64_t batch_n = 0;
 	EmitStage emit;
+	AnnotStage annot;             // the headers' annotation of the compact batch (dbgk_host_annot.h)
 };
 
 static int corr_use(dbgk_corr *c)
@@ -45,6 +46,7 @@ extern "C" int dbgk_corr_create(const dbgk_corr_params *p, int device, dbgk_corr
 	int rc = stage_open(*c, device);
 	if (!rc) rc = c->ev.create();
 	if (!rc) rc = emit_create(c->emit, emitk::CorrRule::kCounters, true);
+	if (!rc) rc = c->annot.ev.create();
 	if (!rc) rc = c->tab.reserve(c->tab_words * 4);
 	if (!rc) rc = c->d_cnt.reserve(4 * sizeof(uint64_t));
 	if (!rc && hipMemsetAsync(c->tab, 0, c->tab_words * 4, c->stream) != hipSuccess) rc = DBGK_ERR_HIP;
@@ -164,7 +166,7 @@ static int corr_batch_begin(dbgk_corr *c, const uint64_t *offsets, uint64_t n)
 	if (max_len >= (1ull << 29)) return DBGK_ERR_ARG;
 	c->last = dbgk_corr_stats{};
 	c->last.reads = n;
-	c->have_batch = c->emit.have = false;
+	c->have_batch = c->emit.have = c->annot.have = false;
 	if (!n) return DBGK_OK;
 	int rc = corr_use(c);
 	if (rc) return rc;
@@ -302,6 +304,7 @@ extern "C" int dbgk_corr_batch_stats(dbgk_corr *c, dbgk_corr_stats *out)
 static int corr_compact_run(dbgk_corr *c, dbgk_corr_compact_info *out)
 {
 	using R = emitk::CorrRule;
+	c->annot.have = false; // (it describes the compact batch this call replaces)
 	int rc = corr_use(c);
 	if (rc) return rc;
 	auto launch_len = [&](unsigned grid, uint32_t *len, uint64_t *src, unsigned long long *ctr) {
@@ -374,6 +377,40 @@ extern "C" int dbgk_corr_compact_device(dbgk_corr *c, const char **d_bases, cons
 	if (!c || !d_bases || !d_offsets || !n_reads || !n_bases) return DBGK_ERR_ARG;
 	if (!c->emit.have) return DBGK_ERR_STATE;
 	emit_device(c->emit, d_bases, nullptr, d_offsets, n_reads, n_bases);
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_annot(dbgk_corr *c, dbgk_corr_annot_info *out)
+{
+	if (!c || !out) return DBGK_ERR_ARG;
+	c->annot.have = false;
+	if (!c->emit.have) return DBGK_ERR_STATE;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	// d_rec and the compact offsets are complete: every call that writes them returns with the stream idle
+	return annot_run(c->annot, c->stream, c->n_cu, c->d_rec, c->emit.off, c->emit.n, out);
+}
+
+extern "C" int dbgk_corr_annot_device(dbgk_corr *c, const char **d_suffix, const uint64_t **d_suffix_offsets, uint64_t *n, uint64_t *n_bytes)
+{
+	if (!c || !d_suffix || !d_suffix_offsets || !n || !n_bytes) return DBGK_ERR_ARG;
+	if (!c->emit.have || !c->annot.have) return DBGK_ERR_STATE;
+	*d_suffix = (const char *)c->annot.suf.p;
+	*d_suffix_offsets = c->annot.off;
+	*n = c->annot.n;
+	*n_bytes = c->annot.total;
+	return DBGK_OK;
+}
+
+extern "C" int dbgk_corr_annot_results(dbgk_corr *c, char *suffix, uint64_t *suffix_offsets)
+{
+	if (!c) return DBGK_ERR_ARG;
+	if (!c->emit.have || !c->annot.have) return DBGK_ERR_STATE;
+	int rc = corr_use(c);
+	if (rc) return rc;
+	if (suffix && c->annot.total) HIPCHK(hipMemcpyAsync(suffix, c->annot.suf, c->annot.total, hipMemcpyDeviceToHost, c->stream));
+	if (suffix_offsets) HIPCHK(hipMemcpyAsync(suffix_offsets, c->annot.off, (c->annot.n + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
 	return DBGK_OK;
 }
 

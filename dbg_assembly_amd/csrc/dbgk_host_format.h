@@ -1,6 +1,7 @@
 // FORMAT stage, host side (include/dbgk.h, FORMAT section; kernels in dbgk_format.h): the output text of one batch on the device,
 // its read-back and its device view.  The launches of a call follow each other on one stream; the host reads the counters and the
-// total in between, which size the text.
+// total in between, which size the text.  The suffix plane comes from the host (checked there, uploaded) or lies on the device
+// (checked there by k_annot_check of dbgk_annot.h); fmt_run is the same for both.
 
 struct dbgk_fmt : StageDev {
 	int format = 1;
@@ -15,6 +16,7 @@ struct dbgk_fmt : StageDev {
 	DevBuf<unsigned long long> ctr;
 	DevBuf<uint8_t> suf; // the uploaded suffix plane
 	DevBuf<uint64_t> soff;
+	DevBuf<uint32_t> suf_bad; // what k_annot_check found in the offsets of a suffix plane on the device
 	// dbgk_fmt_records: the uploaded batch
 	DevBuf<uint8_t> in_text, in_b, in_q;
 	DevBuf<uint64_t> in_off;
@@ -51,12 +53,16 @@ extern "C" int dbgk_fmt_destroy(dbgk_fmt *f)
 	return DBGK_OK;
 }
 
-// n records that lie on the device (the stream is ordered behind whatever wrote them); the suffix plane on the host, checked here
-static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk_parse_rec *recs, const uint8_t *bases, const uint8_t *quals,
-                   const uint64_t *off, uint64_t n, const char *suffix, const uint64_t *suffix_offsets, dbgk_fmt_info *out)
+// The suffix plane of a call as the kernels read it: both null for all empty (a plane of empty suffixes is no plane).
+struct FmtSuffix {
+	const uint8_t *suf = nullptr;
+	const uint64_t *soff = nullptr;
+};
+
+// a plane on the host: checked here, uploaded on the stream
+static int fmt_suffix_from_host(dbgk_fmt *f, uint64_t n, const char *suffix, const uint64_t *suffix_offsets, FmtSuffix &S)
 {
 	f->have = false;
-	const bool fastq = f->format == 1;
 	uint64_t n_suf = 0;
 	if (suffix_offsets && n) {
 		if (suffix_offsets[0] != 0) return DBGK_ERR_ARG;
@@ -65,7 +71,48 @@ static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk
 		n_suf = suffix_offsets[n];
 		if (n_suf >= (1ull << 32) || (n_suf && !suffix)) return DBGK_ERR_ARG;
 	}
-	const bool with_suf = n_suf != 0; // (a plane of empty suffixes is no plane)
+	HIPCHK(hipStreamSynchronize(f->stream));
+	if (n_suf) {
+		if (f->suf.reserve(n_suf + 16, 1 << 16) || f->soff.reserve((n + 1) * 8, 1 << 17)) return DBGK_ERR_NOMEM;
+		HIPCHK(hipMemcpyAsync(f->suf, suffix, n_suf, hipMemcpyHostToDevice, f->stream));
+		HIPCHK(hipMemcpyAsync(f->soff, suffix_offsets, (n + 1) * 8, hipMemcpyHostToDevice, f->stream));
+		S.suf = f->suf;
+		S.soff = f->soff;
+	}
+	return DBGK_OK;
+}
+
+// a plane on the device: the same checks by k_annot_check (dbgk_annot.h), answered before a byte of the plane is read
+static int fmt_suffix_on_device(dbgk_fmt *f, uint64_t n, const uint8_t *d_suffix, const uint64_t *d_suffix_offsets, FmtSuffix &S)
+{
+	f->have = false;
+	if (!d_suffix_offsets || !n) return DBGK_OK;
+	HIPCHK(hipStreamSynchronize(f->stream));
+	if (f->suf_bad.reserve(sizeof(uint32_t))) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemsetAsync(f->suf_bad, 0, sizeof(uint32_t), f->stream));
+	const unsigned grid = (unsigned)std::min<uint64_t>((n + emitk::kEmitBlock - 1) / emitk::kEmitBlock, (uint64_t)f->n_cu * 16);
+	hipLaunchKernelGGL(annotk::k_annot_check, dim3(grid), dim3(emitk::kEmitBlock), 0, f->stream, d_suffix_offsets, (uint32_t)n, f->suf_bad.p);
+	HIPCHK(hipGetLastError());
+	uint32_t bad = 0;
+	uint64_t n_suf = 0;
+	HIPCHK(hipMemcpyAsync(&bad, f->suf_bad, sizeof bad, hipMemcpyDeviceToHost, f->stream));
+	HIPCHK(hipMemcpyAsync(&n_suf, d_suffix_offsets + n, 8, hipMemcpyDeviceToHost, f->stream));
+	HIPCHK(hipStreamSynchronize(f->stream));
+	if (bad || (n_suf && !d_suffix)) return DBGK_ERR_ARG;
+	if (n_suf) {
+		S.suf = d_suffix;
+		S.soff = d_suffix_offsets;
+	}
+	return DBGK_OK;
+}
+
+// n records that lie on the device (the stream is ordered behind whatever wrote them), and their suffix plane, checked by one of
+// the two functions above
+static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk_parse_rec *recs, const uint8_t *bases, const uint8_t *quals,
+                   const uint64_t *off, uint64_t n, const FmtSuffix &S, dbgk_fmt_info *out)
+{
+	f->have = false;
+	const bool fastq = f->format == 1;
 	HIPCHK(hipStreamSynchronize(f->stream));
 	if (n + 1 > f->cap_recs || !f->len || !f->coff) {
 		const uint64_t cap = std::max<uint64_t>(n + 1, 1 << 14);
@@ -73,16 +120,11 @@ static int fmt_run(dbgk_fmt *f, const uint8_t *text, uint64_t n_text, const dbgk
 		if (f->len.reserve(cap * 4) || f->coff.reserve(cap * 8)) return DBGK_ERR_NOMEM;
 		f->cap_recs = cap;
 	}
-	if (with_suf) {
-		if (f->suf.reserve(n_suf + 16, 1 << 16) || f->soff.reserve((n + 1) * 8, 1 << 17)) return DBGK_ERR_NOMEM;
-		HIPCHK(hipMemcpyAsync(f->suf, suffix, n_suf, hipMemcpyHostToDevice, f->stream));
-		HIPCHK(hipMemcpyAsync(f->soff, suffix_offsets, (n + 1) * 8, hipMemcpyHostToDevice, f->stream));
-	}
 	if (n) {
 		const int rc = stage_scan_reserve(f->tmp, f->stream, f->len, f->coff, n + 1);
 		if (rc) return rc;
 	}
-	const fmtk::FmtIn in{text, recs, bases, quals, off, with_suf ? f->suf.p : nullptr, with_suf ? f->soff.p : nullptr};
+	const fmtk::FmtIn in{text, recs, bases, quals, off, S.suf, S.soff};
 	unsigned long long ctr[fmtk::FC_COUNT] = {0};
 	uint64_t total = 0;
 	HIPCHK(hipEventRecord(f->ev[0], f->stream));
@@ -145,20 +187,44 @@ static bool fmt_args_ok(const dbgk_fmt *f, const void *text, uint64_t n_text, co
 	return true;
 }
 
+// what both device entries ask of the batch: alignment, and none of the planes (the suffix plane included) the text about to be written
+static bool fmt_device_args_ok(const dbgk_fmt *f, const char *d_text, const dbgk_parse_rec *d_recs, const char *d_bases, const char *d_quals,
+                               const uint64_t *d_offsets, const char *d_suffix)
+{
+	if (((uintptr_t)d_text & 15u) || ((uintptr_t)d_bases & 15u) || ((uintptr_t)d_quals & 15u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_recs & 3u))
+		return false;
+	for (const char *p : {d_text, d_bases, d_quals, d_suffix}) {
+		const uint8_t *u = (const uint8_t *)p;
+		if (u && f->out && u >= f->out && u < f->out + f->out.cap) return false;
+	}
+	return true;
+}
+
 extern "C" int dbgk_fmt_records_device(dbgk_fmt *f, const char *d_text, uint64_t n_text, const dbgk_parse_rec *d_recs, const char *d_bases,
                                        const char *d_quals, const uint64_t *d_offsets, uint64_t n, const char *suffix,
                                        const uint64_t *suffix_offsets, dbgk_fmt_info *out)
 {
 	if (!fmt_args_ok(f, d_text, n_text, d_recs, d_bases, d_quals, d_offsets, n, out)) return DBGK_ERR_ARG;
-	if (((uintptr_t)d_text & 15u) || ((uintptr_t)d_bases & 15u) || ((uintptr_t)d_quals & 15u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_recs & 3u))
-		return DBGK_ERR_ARG;
-	for (const char *p : {d_text, d_bases, d_quals}) { // the text the call is about to write
-		const uint8_t *u = (const uint8_t *)p;
-		if (u && f->out && u >= f->out && u < f->out + f->out.cap) return DBGK_ERR_ARG;
-	}
+	if (!fmt_device_args_ok(f, d_text, d_recs, d_bases, d_quals, d_offsets, nullptr)) return DBGK_ERR_ARG;
 	HIPCHK(hipSetDevice(f->device));
-	return fmt_run(f, (const uint8_t *)d_text, n_text, d_recs, (const uint8_t *)d_bases, (const uint8_t *)d_quals, d_offsets, n, suffix, suffix_offsets,
-	               out);
+	FmtSuffix S;
+	const int rc = fmt_suffix_from_host(f, n, suffix, suffix_offsets, S);
+	if (rc) return rc;
+	return fmt_run(f, (const uint8_t *)d_text, n_text, d_recs, (const uint8_t *)d_bases, (const uint8_t *)d_quals, d_offsets, n, S, out);
+}
+
+extern "C" int dbgk_fmt_records_device_suffix(dbgk_fmt *f, const char *d_text, uint64_t n_text, const dbgk_parse_rec *d_recs, const char *d_bases,
+                                              const char *d_quals, const uint64_t *d_offsets, uint64_t n, const char *d_suffix,
+                                              const uint64_t *d_suffix_offsets, dbgk_fmt_info *out)
+{
+	if (!fmt_args_ok(f, d_text, n_text, d_recs, d_bases, d_quals, d_offsets, n, out)) return DBGK_ERR_ARG;
+	if (!fmt_device_args_ok(f, d_text, d_recs, d_bases, d_quals, d_offsets, d_suffix)) return DBGK_ERR_ARG;
+	if (((uintptr_t)d_suffix & 15u) || ((uintptr_t)d_suffix_offsets & 7u)) return DBGK_ERR_ARG;
+	HIPCHK(hipSetDevice(f->device));
+	FmtSuffix S;
+	const int rc = fmt_suffix_on_device(f, n, (const uint8_t *)d_suffix, d_suffix_offsets, S);
+	if (rc) return rc;
+	return fmt_run(f, (const uint8_t *)d_text, n_text, d_recs, (const uint8_t *)d_bases, (const uint8_t *)d_quals, d_offsets, n, S, out);
 }
 
 extern "C" int dbgk_fmt_records(dbgk_fmt *f, const char *text, uint64_t n_text, const dbgk_parse_rec *recs, const char *bases, const char *quals,
@@ -190,7 +256,10 @@ extern "C" int dbgk_fmt_records(dbgk_fmt *f, const char *text, uint64_t n_text, 
 		HIPCHK(hipMemcpyAsync(f->in_rec, recs, n * sizeof(dbgk_parse_rec), hipMemcpyHostToDevice, f->stream));
 	}
 	HIPCHK(hipStreamSynchronize(f->stream)); // the caller's buffers are free on return
-	return fmt_run(f, f->in_text, n_text, f->in_rec, f->in_b, quals ? f->in_q.p : nullptr, f->in_off, n, suffix, suffix_offsets, out);
+	FmtSuffix S;
+	const int rc = fmt_suffix_from_host(f, n, suffix, suffix_offsets, S);
+	if (rc) return rc;
+	return fmt_run(f, f->in_text, n_text, f->in_rec, f->in_b, quals ? f->in_q.p : nullptr, f->in_off, n, S, out);
 }
 
 extern "C" int dbgk_fmt_results(dbgk_fmt *f, void *out, uint64_t capacity)

@@ -9,6 +9,7 @@
 
 #include "cli_common.h"
 #include "dbgk_env.h"
+#include "text_window.h"
 
 static const uint64_t BatchReads = 1 << 20;   // records per device batch
 static const uint64_t BatchBases = 256 << 20; // ... or this many bases, whichever comes first
@@ -61,17 +62,11 @@ struct RecordBatch {
 };
 
 // ---- DBGK_TEXT=device -----------------------------------------------------------------------------------------------------------
-// Window by window: the decompressed bytes of the input (zlib's gzread: plain and ordinary gzip alike; DBGK_GUNZIP is not looked
-// at) behind what the window before left unconsumed -> dbgk_parse_chunk with a quality plane -> the program's cleaner on the
+// Window by window (text_window.h): the decompressed bytes of the input behind what the window before left unconsumed ->
+// dbgk_parse_chunk with a quality plane -> the program's cleaner on the
 // parser's planes -> dbgk_clean_compact -> dbgk_fmt_records_device with the suffixes the program composes on the host from the
 // returned records -> GzWriter::write_device.  The output and the .stat file are byte for byte the host route's; the "reading num"
 // lines count a window's records.
-
-static bool text_on_device()
-{
-	const char *e = getenv("DBGK_TEXT");
-	return e && strcmp(e, "device") == 0;
-}
 
 struct DeviceTextTotals {
 	uint64_t raw_reads = 0, raw_bases = 0; // records, and the bytes of their sequence lines as the text has them
@@ -86,11 +81,8 @@ template <class Clean>
 static void clean_text_on_device(const string &in_path, GzWriter &out, dbgk_clean *cleaner, int min_len, bool refuse_mismatched, DeviceTextTotals &T,
                                  Clean clean)
 {
-	size_t window = (size_t)256 << 20;
-	if (const char *h = dbgk_hook("text_window")) // (tests: windows that end inside records of small files; every value gives the same files)
-		if (atoll(h) > 0) window = (size_t)atoll(h);
-	gzFile in = gzopen(in_path.c_str(), "rb");
-	if (!in) {
+	TextWindows in(in_path);
+	if (!in.ok()) {
 		cerr << "fail to open input file " << in_path << endl;
 		return;
 	}
@@ -100,33 +92,12 @@ static void clean_text_on_device(const string &in_path, GzWriter &out, dbgk_clea
 	if (rc) die("dbgk_parse_create", rc);
 	rc = dbgk_fmt_create(1, 0, 0, &formatter);
 	if (rc) die("dbgk_fmt_create", rc);
-	vector<char> chunk;
 	vector<uint64_t> offsets, lens, suffix_offsets;
 	vector<dbgk_parse_rec> recs;
 	string suffix;
-	size_t have = 0;
-	for (bool last = false; !last;) {
-		if (have + window >= ((size_t)1 << 31)) {
-			cerr << "a record of " << in_path << " does not end within 2 GiB of text: DBGK_TEXT=device cannot read this file" << endl;
-			exit(1);
-		}
-		chunk.resize(have + window);
-		size_t got = 0;
-		while (got < window) {
-			const int r = gzread(in, chunk.data() + have + got, (unsigned)min<size_t>(window - got, 1u << 30));
-			if (r < 0) {
-				cerr << "fail to read input file " << in_path << endl;
-				exit(1);
-			}
-			if (r == 0) {
-				last = true;
-				break;
-			}
-			got += (size_t)r;
-		}
-		const size_t n_text = have + got;
+	while (in.next()) {
 		dbgk_parse_info pi;
-		rc = dbgk_parse_chunk(parser, chunk.data(), n_text, last ? 1 : 0, &pi);
+		rc = dbgk_parse_chunk(parser, in.text(), in.n_text, in.last ? 1 : 0, &pi);
 		if (rc) die("dbgk_parse_chunk", rc);
 		const uint64_t n = pi.n_records;
 		cerr << "reading num " << n << endl;
@@ -174,11 +145,8 @@ static void clean_text_on_device(const string &in_path, GzWriter &out, dbgk_clea
 			if (rc) die("dbgk_fmt_records_device", rc);
 			out.write_device(formatter);
 		}
-		// what the window left unconsumed goes in front of the next one; a window without a whole record only makes the text longer
-		have = last ? 0 : n_text - (size_t)pi.consumed;
-		if (have && pi.consumed) memmove(chunk.data(), chunk.data() + pi.consumed, have);
+		in.keep_from(pi.consumed);
 	}
-	gzclose(in);
 	dbgk_fmt_destroy(formatter);
 	dbgk_parse_destroy(parser);
 }

@@ -38,8 +38,31 @@
 #include "cli_common.h"
 #include "kmer_spectrum.h"
 #include "reads_io.h"
+#include "text_window.h"
 
 static const uint64_t kBlockKmers = 8ull * 1024 * 1024;  // SrcBlockSize, correct_error/main_parallel_senior.cpp:71
+
+// DBGK_TEXT=device on a single GPU handle: the reads of one file without for_each_read_in_file and dbgk_push_reads.  Window by window
+// (text_window.h, windows of one batch) the text is parsed on the device without a quality plane -- the record rules are those of
+// for_each_read_in_file -- and the parser's batch is pushed where it lies.  false: the file cannot be opened.
+static bool count_file_on_device(dbgk_handle *h, dbgk_parse *parser, const string &path, size_t window, uint64_t &windows, uint64_t &records)
+{
+	TextWindows in(path, window);
+	if (!in.ok()) return false;
+	while (in.next()) {
+		dbgk_parse_info pi;
+		int rc = dbgk_parse_chunk(parser, in.text(), in.n_text, in.last ? 1 : 0, &pi);
+		if (rc) die("dbgk_parse_chunk", rc);
+		if (pi.n_records) {
+			rc = dbgk_push_parsed(h, parser);
+			if (rc) die("dbgk_push_parsed", rc);
+		}
+		records += pi.n_records;
+		in.keep_from(pi.consumed);
+	}
+	windows += in.windows;
+	return true;
+}
 
 int main(int argc, char **argv)
 {
@@ -141,9 +164,21 @@ int main(int argc, char **argv)
 	};
 	ifstream list(lib.c_str());
 	if (!list) { cerr << "fail to open " << lib << endl; return 1; }
+	// DBGK_TEXT=device: a single handle parses and pushes on the device; several GPUs keep the host reader.  No option filters or cuts
+	// reads on the host -- -q is accepted and ignored, -r and -e size the handle -- so none keeps the host reader under the switch.
+	dbgk_parse *parser = nullptr;
+	uint64_t text_windows = 0, text_records = 0;
+	if (text_on_device() && !comm) {
+		rc = dbgk_parse_create(fmt == 1 ? 1 : 2, 0, cfg.device_id, &parser);
+		if (rc) die("dbgk_parse_create", rc);
+	}
 	for (string path; getline(list, path);) {
 		if (path.empty()) continue;
 		cerr << "counting k-mers of " << path << endl;
+		if (parser) {
+			if (!count_file_on_device(h, parser, path, (size_t)batch_bytes, text_windows, text_records)) cerr << "fail to open reads file " << path << endl;
+			continue;
+		}
 		const bool ok = for_each_read_in_file(path, fmt, [&](const char *seq, size_t len) {
 			bases.insert(bases.end(), seq, seq + len);
 			offsets.push_back(bases.size());
@@ -155,6 +190,10 @@ int main(int argc, char **argv)
 	dbgk_stats st;
 	rc = comm ? dbgk_comm_finalize(comm, &st) : dbgk_finalize(h, &st);
 	if (rc) die("dbgk_finalize", rc);
+	if (parser) {
+		if (getenv("DBGK_TIMINGS")) cerr << "Text on device: " << text_windows << " windows, " << text_records << " records" << endl;
+		dbgk_parse_destroy(parser);
+	}
 	cerr << "reads " << st.total_reads << "  k-mers " << st.stored_kmers << "  distinct canonical k-mers " << st.count << endl;
 	if (st.other_bytes) cerr << "Alert message: " << st.other_bytes << " sequence bytes are none of ACGTNacgtn; they were read as A (like N)" << endl;
 

@@ -680,6 +680,30 @@ int dbgk_corr_compact_device(dbgk_corr *c, const char **d_bases, const uint64_t 
  * behind every reader.  Handles on different devices: DBGK_ERR_ARG; no compact batch, or h finalized: DBGK_ERR_STATE.       */
 int dbgk_push_corrected(dbgk_handle *h, dbgk_corr *c);
 
+/* The annotation of the headers, composed on the device (additions to ABI 7).  For record i of the compact batch the suffix is what
+ * bin/correct_error_reads appends to header i, without the final "\n":
+ *   "\tModifiedBaseNum: " M "\tFinalReadLength: " F "\tLeftEndTrim: " Lt "\tRightEndTrim: " Rt "\tIsDeleted: " D
+ * M = (uint32)(one_base + tree), F = the record's length in the compact batch, Lt / Rt = left_trim / right_trim as stored, D =
+ * deleted as an unsigned number, all in decimal without padding.  The plane has the layout of every other plane: from a 16-byte
+ * boundary in whole 16-byte vectors, the pad of the last one 0, 64 readable bytes behind it, n + 1 64-bit offsets from 0 -- what
+ * dbgk_fmt_records_device_suffix reads where it lies.  A suffix has at most DBGK_CORR_ANNOT_MAX bytes: the 77 bytes of the literals,
+ * four numbers of 10 digits and one of 3.                                                                                  */
+#define DBGK_CORR_ANNOT_MAX 120
+typedef struct dbgk_corr_annot_info {
+	uint64_t n;                 /* records                                                                              */
+	uint64_t suffix_bytes;      /* bytes of the plane (without the pad)                                                 */
+	double ms_scan;             /* device time of the length kernel + the scan, and of the write kernel                 */
+	double ms_write;
+} dbgk_corr_annot_info;
+/* the plane of the handle's compact batch (dbgk_corr_compact, dbgk_corr_compact_from); before one: DBGK_ERR_STATE.  Returns when it
+ * is complete.                                                                                                             */
+int dbgk_corr_annot(dbgk_corr *c, dbgk_corr_annot_info *out);
+/* the plane where it lies; valid until the next dbgk_corr_reads*, dbgk_corr_compact*, dbgk_corr_annot or dbgk_corr_destroy on c.
+ * Before a dbgk_corr_annot of the current compact batch: DBGK_ERR_STATE (also for dbgk_corr_annot_results).                 */
+int dbgk_corr_annot_device(dbgk_corr *c, const char **d_suffix, const uint64_t **d_suffix_offsets, uint64_t *n, uint64_t *n_bytes);
+/* host copy: suffix_bytes bytes (without the pad) and n + 1 offsets; either pointer may be null                            */
+int dbgk_corr_annot_results(dbgk_corr *c, char *suffix, uint64_t *suffix_offsets);
+
 /* ---- MAP: map_reads / map_pair of the link_scaffold module on the GPU (additions to ABI 7) ----------------------------------
  * The reference maps every read onto the contigs with a seed search over the contig k-mer index (get_align_seed,
  * link_scaffold/map_func.cpp:181-237) and a gap-free extension with a mismatch count (extend_align_region, :241-299).  A mapper
@@ -1094,6 +1118,7 @@ int dbgk_inf_timing_get(dbgk_inf_t z, dbgk_inf_timing *t);
  *     quality plane (format 1 only), n + 1 64-bit offsets;
  *   - an optional suffix plane ON THE HOST, uploaded by the call: bytes and n + 1 offsets that start at 0 and do not decrease, below
  *     2^32, or null for all empty.  It is what a program appends to the header, composed by the caller.
+ *     dbgk_fmt_records_device_suffix takes the same plane in device memory (dbgk_corr_annot composes one there).
  * Output, record after record in input order, with H the header's bytes (a '\r' included), S the suffix, B / Q the record's bytes
  * of the two planes and L their length:
  *   format 1 (FASTQ)  H S "\n" B "\n+\n" Q "\n"        head_len + suf_len + 2 L + 5 bytes
@@ -1129,6 +1154,15 @@ int dbgk_fmt_destroy(dbgk_fmt *f);
 int dbgk_fmt_records_device(dbgk_fmt *f, const char *d_text, uint64_t n_text, const dbgk_parse_rec *d_recs, const char *d_bases,
                             const char *d_quals, const uint64_t *d_offsets, uint64_t n, const char *suffix, const uint64_t *suffix_offsets,
                             dbgk_fmt_info *out);
+/* dbgk_fmt_records_device with the suffix plane in device memory of f's GPU too, read in place and never written -- what
+ * dbgk_corr_annot_device returns: d_suffix 16-byte aligned with its last dword readable, d_suffix_offsets n + 1 64-bit values, both
+ * null for all empty.  What dbgk_fmt_records_device checks of a suffix plane on the host is found on the device here and answered
+ * with DBGK_ERR_ARG and no output (dbgk_fmt_results then gives DBGK_ERR_STATE): offsets that do not start at 0, that decrease, a total
+ * of 2^32 or more -- the plane's bytes are not read before the offsets have passed.  A misaligned plane, offsets without a plane
+ * that hold bytes, or the stage's own output as the plane: DBGK_ERR_ARG before any device work, as for the other inputs.      */
+int dbgk_fmt_records_device_suffix(dbgk_fmt *f, const char *d_text, uint64_t n_text, const dbgk_parse_rec *d_recs, const char *d_bases,
+                                   const char *d_quals, const uint64_t *d_offsets, uint64_t n, const char *d_suffix,
+                                   const uint64_t *d_suffix_offsets, dbgk_fmt_info *out);
 /* the same with everything on the host, uploaded by the call: offsets[n] bytes of each plane                               */
 int dbgk_fmt_records(dbgk_fmt *f, const char *text, uint64_t n_text, const dbgk_parse_rec *recs, const char *bases, const char *quals,
                      const uint64_t *offsets, uint64_t n, const char *suffix, const uint64_t *suffix_offsets, dbgk_fmt_info *out);
