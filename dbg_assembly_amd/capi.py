@@ -176,6 +176,21 @@ class FmtInfo(C.Structure):
                [("ms_scan", C.c_double), ("ms_gather", C.c_double)]
 
 
+MAPROW_READS, MAPROW_PAIR = 1, 2  # DBGK_MAPROW_*
+MAPROW_STREAMS = 3                # DBGK_MAPROW_STREAMS
+MAPROW_TILE = 4096                # DBGK_MAPROW_TILE
+
+
+class MapRowSide(C.Structure):    # dbgk_maprow_side
+    _fields_ = [("text", C.c_void_p), ("n_text", C.c_uint64), ("recs", C.c_void_p), ("bases", C.c_void_p), ("offsets", C.c_void_p),
+                ("hits", C.c_void_p)]
+
+
+class MapRowInfo(C.Structure):    # dbgk_maprow_info
+    _fields_ = [("n", C.c_uint64), ("counters", C.c_uint64 * 5), ("stream_bytes", C.c_uint64 * MAPROW_STREAMS), ("unprintable", C.c_uint64),
+                ("ms_scan", C.c_double), ("ms_write", C.c_double)]
+
+
 GZ_PIECE = 65280   # DBGK_GZ_PIECE
 GZ_MAX_LEVEL = 2   # DBGK_GZ_MAX_LEVEL
 
@@ -456,6 +471,8 @@ SYMBOLS = [
     ("dbgk_map_reads", _i, [_vp, _vp, _vp, _u64, _vp]),
     ("dbgk_map_batch_stats", _i, [_vp, C.POINTER(MapStats)]),
     ("dbgk_map_reads_device", _i, [_vp, _vp, _vp, _u64, _u64, _u64, _vp]),
+    ("dbgk_map_reads_device_keep", _i, [_vp, _vp, _vp, _u64, _u64, _u64]),
+    ("dbgk_map_hits_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("dbgk_clean_create", _i, [_i, C.POINTER(_vp)]),
     ("dbgk_clean_destroy", _i, [_vp]),
     ("dbgk_clean_set_adapters", _i, [_vp, _vp, _vp, _u64, C.c_int32]),
@@ -492,6 +509,14 @@ SYMBOLS = [
     ("dbgk_fmt_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
     ("dbgk_parse_recs_device", _i, [_vp, C.POINTER(_vp)]),
     ("dbgk_parse_text_device", _i, [_vp, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("dbgk_maprow_create", _i, [C.c_int32, C.c_char_p, C.c_int32, _i, C.POINTER(_vp)]),
+    ("dbgk_maprow_destroy", _i, [_vp]),
+    ("dbgk_maprow_set_contigs", _i, [_vp, _vp, _vp, _vp, _u64]),
+    ("dbgk_maprow_take_hits", _i, [_vp, C.c_int32, _vp]),
+    ("dbgk_maprow_rows_device", _i, [_vp, C.POINTER(MapRowSide), _u64, C.POINTER(MapRowInfo)]),
+    ("dbgk_maprow_rows", _i, [_vp, C.POINTER(MapRowSide), _u64, C.POINTER(MapRowInfo)]),
+    ("dbgk_maprow_device", _i, [_vp, C.c_int32, C.POINTER(_vp), C.POINTER(_u64)]),
+    ("dbgk_maprow_results", _i, [_vp, C.c_int32, _vp, _u64]),
     ("dbgk_gz_create", _i, [_i, C.POINTER(_vp)]),
     ("dbgk_gz_destroy", _i, [_vp]),
     ("dbgk_gz_deflate", _i, [_vp, _vp, _u64, _i, C.POINTER(GzInfo)]),
@@ -1466,12 +1491,22 @@ class Mapper(_Handle):
              "dbgk_map_reads")
         return hits[:n]
 
-    def map_device(self, d_bases, d_offsets, n_reads, n_bases, max_len):
+    def map_device(self, d_bases, d_offsets, n_reads, n_bases, max_len, keep=False):
         """map() for a batch on the device, offsets included (pointers; Pairer.device, Corrector / Cleaner.compact_device); max_len
-        is at least the longest read (PairInfo.max_len) -> MAP_HIT_DTYPE[n, 2]"""
+        is at least the longest read (PairInfo.max_len) -> MAP_HIT_DTYPE[n, 2].  keep: the hits stay on the device (hits_device,
+        RowWriter.take_hits) and None is returned"""
+        if keep:
+            _chk(lib().dbgk_map_reads_device_keep(self._h, d_bases, d_offsets, n_reads, n_bases, max_len), "dbgk_map_reads_device_keep")
+            return None
         hits = np.zeros((max(n_reads, 1), 2), dtype=MAP_HIT_DTYPE)
         _chk(lib().dbgk_map_reads_device(self._h, d_bases, d_offsets, n_reads, n_bases, max_len, hits.ctypes.data), "dbgk_map_reads_device")
         return hits[:n_reads]
+
+    def hits_device(self):
+        """-> (device pointer of the 2 n hits of the last batch, or None for an empty one; n)"""
+        p, n = _vp(), _u64()
+        _chk(lib().dbgk_map_hits_device(self._h, C.byref(p), C.byref(n)), "dbgk_map_hits_device")
+        return p.value, int(n.value)
 
     def map_sequences(self, reads):
         return self.map(*concat_sequences(reads))
@@ -1697,6 +1732,96 @@ class Formatter(_Handle):
         _, n = self.device()
         out = np.empty(max(n, 1), dtype=np.uint8)
         _chk(lib().dbgk_fmt_results(self._h, out.ctypes.data, n), "dbgk_fmt_results")
+        return out[:n].tobytes()
+
+
+class RowWriter(_Handle):
+    """The lines of map_reads' / map_pair's output files composed on the GPU (ROWS section of include/dbgk.h).  mode MAPROW_READS: one
+    side, hits 2 i and 2 i + 1 the two alignments of read i; MAPROW_PAIR: two sides, read i of each a pair.  delims: the delimiter set of
+    the read id.  set_contigs gives the table the rows print from; rows (everything on the host) and rows_device (a Parser's batch and
+    hits taken from a Mapper with take_hits) return the info as a dict, also kept in `info`; results(stream) / device(stream) give the
+    text of stream 0 .. 2."""
+    _destroy = "dbgk_maprow_destroy"
+
+    def __init__(self, mode, delims, min_read_len=0, device=0):
+        self._h = C.c_void_p()
+        self.info = None
+        if isinstance(delims, str):
+            delims = delims.encode("latin-1")
+        self.n_sides = 2 if mode == MAPROW_PAIR else 1
+        _chk(lib().dbgk_maprow_create(mode, delims, min_read_len, device, C.byref(self._h)), "dbgk_maprow_create")
+
+    def set_contigs(self, names, lengths):
+        """names: a list of bytes / str, the id of every contig; lengths: the length every row of that contig prints"""
+        data, off = concat_sequences(names)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+        if len(lengths) != len(off) - 1:
+            raise ValueError("one length per contig")
+        _chk(lib().dbgk_maprow_set_contigs(self._h, data.ctypes.data if data.size else None, off.ctypes.data,
+                                           lengths.ctypes.data if lengths.size else None, len(lengths)), "dbgk_maprow_set_contigs")
+
+    def take_hits(self, side, mapper):
+        """the hits of the Mapper's last batch, device to device, as side 0 or 1 of the next rows_device"""
+        _chk(lib().dbgk_maprow_take_hits(self._h, side, mapper._h), "dbgk_maprow_take_hits")
+
+    def _done(self, info):
+        self.info = {"n": int(info.n), "counters": [int(v) for v in info.counters], "stream_bytes": [int(v) for v in info.stream_bytes],
+                     "unprintable": int(info.unprintable), "ms_scan": info.ms_scan, "ms_write": info.ms_write}
+        return self.info
+
+    def rows(self, sides, n=None):
+        """sides: per side (text, recs PARSE_REC_DTYPE[n], bases, offsets uint64[n + 1], hits MAP_HIT_DTYPE[n, 2]), all on the host"""
+        if len(sides) != self.n_sides:
+            raise ValueError("one side for READS, two for PAIR")
+        keep, arr = [], (MapRowSide * self.n_sides)()
+        pad = np.zeros(16, dtype=np.uint8)
+        for s, (text, recs, bases, offsets, hits) in enumerate(sides):
+            t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+            recs = np.ascontiguousarray(recs, dtype=PARSE_REC_DTYPE)
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+            hits = np.ascontiguousarray(hits, dtype=MAP_HIT_DTYPE).reshape(-1)
+            m = len(offsets) - 1
+            if n is None:
+                n = m
+            if m != n or len(recs) != n or hits.size != 2 * n:
+                raise ValueError("n records, n + 1 offsets and 2 n hits per side")
+            keep.append((t, recs, bases, offsets, hits))
+            arr[s] = MapRowSide(t.ctypes.data if t.size else None, t.size, (recs if n else pad).ctypes.data, (bases if bases.size else pad).ctypes.data,
+                                offsets.ctypes.data, (hits if n else pad).ctypes.data)
+        info = MapRowInfo()
+        _chk(lib().dbgk_maprow_rows(self._h, arr, n, C.byref(info)), "dbgk_maprow_rows")
+        return self._done(info)
+
+    def rows_device(self, sides, n):
+        """sides: per side a Parser after a chunk, or the pointers (d_text, n_text, d_recs, d_bases, d_offsets); the hits are those of
+        take_hits"""
+        if len(sides) != self.n_sides:
+            raise ValueError("one side for READS, two for PAIR")
+        arr = (MapRowSide * self.n_sides)()
+        for s, side in enumerate(sides):
+            if isinstance(side, Parser):
+                d_text, nt, d_recs = _vp(), _u64(), _vp()
+                _chk(lib().dbgk_parse_text_device(side._h, C.byref(d_text), C.byref(nt)), "dbgk_parse_text_device")
+                _chk(lib().dbgk_parse_recs_device(side._h, C.byref(d_recs)), "dbgk_parse_recs_device")
+                d_bases, _, d_off, _, _ = side.device()
+                side = (d_text.value, int(nt.value), d_recs.value, d_bases, d_off)
+            arr[s] = MapRowSide(side[0], side[1], side[2], side[3], side[4], None)
+        info = MapRowInfo()
+        _chk(lib().dbgk_maprow_rows_device(self._h, arr, n, C.byref(info)), "dbgk_maprow_rows_device")
+        return self._done(info)
+
+    def device(self, stream):
+        """-> (device pointer of the text of a stream of the last call, its bytes)"""
+        p, n = _vp(), _u64()
+        _chk(lib().dbgk_maprow_device(self._h, stream, C.byref(p), C.byref(n)), "dbgk_maprow_device")
+        return p.value, int(n.value)
+
+    def results(self, stream):
+        """-> the text of a stream of the last call as bytes"""
+        _, n = self.device(stream)
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        _chk(lib().dbgk_maprow_results(self._h, stream, out.ctypes.data, n), "dbgk_maprow_results")
         return out[:n].tobytes()
 
 

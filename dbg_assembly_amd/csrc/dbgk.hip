@@ -34,6 +34,7 @@
 #include "dbgk_parse.h"
 #include "dbgk_format.h"
 #include "dbgk_annot.h"
+#include "dbgk_maprow.h"
 #include "dbgk_gz.h"
 #include "dbgk_inflate.h"
 #include "dbgk_link.h"
@@ -484,6 +485,7 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_pair.h"
 #include "dbgk_host_parse.h"
 #include "dbgk_host_format.h"
+#include "dbgk_host_maprow.h"
 #include "dbgk_host_gz.h"
 #include "dbgk_host_inflate.h"
 #include "dbgk_host_link.h"

@@ -20,6 +20,7 @@ struct dbgk_map : StageDev {
 	uint64_t cap_bytes = 0, cap_reads = 0;
 	StageEvents<4> ev;
 	dbgk_map_stats last{};
+	bool have_hits = false; // d_hits holds the 2 * last.reads hits of a batch that succeeded (dbgk_map_hits_device)
 };
 
 static_assert(sizeof(dbgk_map_hit) == 32 && sizeof(mapk::Hit) == 32, "dbgk_map_hit is eight int32");
@@ -105,6 +106,7 @@ extern "C" int dbgk_map_set_contigs(dbgk_map *m, const char *bases, const uint64
 	const uint64_t total = offsets[n_contigs];
 	if ((total && !bases) || longest >= (1ull << 30)) return DBGK_ERR_ARG; // pos is a 30-bit field of the index
 	map_free_contigs(m);
+	m->have_hits = false;
 	// the index: init_kmerset(total * 3) of map_pair.cpp:122-124 -- find_next_prime unless below 3
 	dbgk_config cfg{};
 	cfg.kmer_size = m->p.k;
@@ -169,8 +171,8 @@ static int map_ensure_batch(dbgk_map *m, uint64_t n_bytes, uint64_t n_reads)
 	return DBGK_OK;
 }
 
-// The n_reads > 0 reads of d_seq / d_off (on the device, or on their way there on the mapper's stream) -> out.  The accept table
-// covers the longest read and the batch buffers hold n_reads reads.
+// The n_reads > 0 reads of d_seq / d_off (on the device, or on their way there on the mapper's stream) -> out, or with a null `out`
+// left in d_hits alone.  The accept table covers the longest read and the batch buffers hold n_reads reads.
 static int map_run(dbgk_map *m, const uint8_t *d_seq, const uint64_t *d_off, uint64_t n_reads, dbgk_map_hit *out)
 {
 	HIPCHK(hipMemsetAsync(m->d_ctr, 0, sizeof(mapk::MapCounters), m->stream));
@@ -196,8 +198,9 @@ static int map_run(dbgk_map *m, const uint8_t *d_seq, const uint64_t *d_off, uin
 		HIPCHK(hipEventRecord(m->ev[3], m->stream));
 		HIPCHK(hipMemcpyAsync(&hc, m->d_ctr, sizeof hc, hipMemcpyDeviceToHost, m->stream));
 	}
-	HIPCHK(hipMemcpyAsync(out, m->d_hits, n_reads * 2 * sizeof(mapk::Hit), hipMemcpyDeviceToHost, m->stream));
+	if (out) HIPCHK(hipMemcpyAsync(out, m->d_hits, n_reads * 2 * sizeof(mapk::Hit), hipMemcpyDeviceToHost, m->stream));
 	HIPCHK(hipStreamSynchronize(m->stream));
+	m->have_hits = true;
 	float ms = 0;
 	HIPCHK(hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
 	m->last.ms_map = ms;
@@ -225,6 +228,7 @@ extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *of
 	if (!m->index) return DBGK_ERR_STATE;
 	m->last = dbgk_map_stats{};
 	m->last.reads = n_reads;
+	m->have_hits = !n_reads;
 	if (!n_reads) return DBGK_OK;
 	HIPCHK(hipSetDevice(m->device));
 	int rc = map_ensure_accept(m, max_len);
@@ -238,14 +242,16 @@ extern "C" int dbgk_map_reads(dbgk_map *m, const char *bases, const uint64_t *of
 	return map_run(m, m->d_seq, m->d_off, n_reads, out);
 }
 
-extern "C" int dbgk_map_reads_device(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len,
-                                     dbgk_map_hit *out)
+// both device entries; keep: the hits stay on the device and `out` is not looked at
+static int map_reads_device(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len, dbgk_map_hit *out,
+                            bool keep)
 {
-	if (!m || (n_reads && (!out || !d_offsets)) || n_reads >= (1ull << 31) || max_len >= (1ull << 31)) return DBGK_ERR_ARG;
+	if (!m || (n_reads && ((!keep && !out) || !d_offsets)) || n_reads >= (1ull << 31) || max_len >= (1ull << 31)) return DBGK_ERR_ARG;
 	if (((uintptr_t)d_bases & 15u) || ((uintptr_t)d_offsets & 7u) || (n_bases && !d_bases)) return DBGK_ERR_ARG;
 	if (!m->index) return DBGK_ERR_STATE;
 	m->last = dbgk_map_stats{};
 	m->last.reads = n_reads;
+	m->have_hits = !n_reads;
 	if (!n_reads) return DBGK_OK;
 	HIPCHK(hipSetDevice(m->device));
 	// what dbgk_map_reads learns from its host loop over the offsets, learned on the device, before any read is mapped
@@ -262,7 +268,27 @@ extern "C" int dbgk_map_reads_device(dbgk_map *m, const char *d_bases, const uin
 	if (rc) return rc;
 	rc = map_ensure_batch(m, 0, n_reads);
 	if (rc) return rc;
-	return map_run(m, (const uint8_t *)d_bases, d_offsets, n_reads, out);
+	return map_run(m, (const uint8_t *)d_bases, d_offsets, n_reads, keep ? nullptr : out);
+}
+
+extern "C" int dbgk_map_reads_device(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len,
+                                     dbgk_map_hit *out)
+{
+	return map_reads_device(m, d_bases, d_offsets, n_reads, n_bases, max_len, out, false);
+}
+
+extern "C" int dbgk_map_reads_device_keep(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len)
+{
+	return map_reads_device(m, d_bases, d_offsets, n_reads, n_bases, max_len, nullptr, true);
+}
+
+extern "C" int dbgk_map_hits_device(dbgk_map *m, const dbgk_map_hit **d_hits, uint64_t *n_reads)
+{
+	if (!m || !d_hits || !n_reads) return DBGK_ERR_ARG;
+	if (!m->have_hits) return DBGK_ERR_STATE;
+	*d_hits = m->last.reads ? reinterpret_cast<const dbgk_map_hit *>(m->d_hits.p) : nullptr;
+	*n_reads = m->last.reads;
+	return DBGK_OK;
 }
 
 extern "C" int dbgk_map_batch_stats(dbgk_map *m, dbgk_map_stats *out)

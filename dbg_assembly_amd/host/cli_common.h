@@ -264,20 +264,17 @@ struct GzWriter {
 		for (size_t at = 0; f && at < n; at += 1u << 30) gzwrite(f, p + at, (unsigned)min<size_t>(n - at, 1u << 30));
 	}
 	void write(const string &s) { write(s.data(), s.size()); }
-	// The text of a formatter's last call (FORMAT section of dbgk.h), behind everything written so far.  With DBGK_GZ=device what
-	// the writer still holds on the host is deflated first (a short member in mid-file is valid), then the text where it lies, in
-	// slices of whole pieces below 2^31 bytes; the end marker stays close()'s.  Otherwise the text comes back to the host for zlib.
-	void write_device(dbgk_fmt *text)
+	// n bytes of text in device memory, behind everything written so far: 16-byte aligned, in whole 16-byte vectors with 64 readable
+	// bytes behind them, as the FORMAT and ROWS stages of dbgk.h leave theirs.  With DBGK_GZ=device what the writer still holds on the
+	// host is deflated first (a short member in mid-file is valid), then the text where it lies, in slices of whole pieces below 2^31
+	// bytes; the end marker stays close()'s.  Otherwise host_copy(dst, n) brings the same bytes to the host for zlib.
+	template <class HostCopy>
+	void write_device(const void *d_text, uint64_t n, HostCopy host_copy)
 	{
-		const void *d_text = nullptr;
-		uint64_t n = 0;
-		int rc = dbgk_fmt_device(text, &d_text, &n);
-		if (rc) die("dbgk_fmt_device", rc);
 		if (!n) return;
 		if (!z) {
 			vector<char> host(n);
-			rc = dbgk_fmt_results(text, host.data(), host.size());
-			if (rc) die("dbgk_fmt_results", rc);
+			host_copy(host.data(), host.size());
 			write(host.data(), host.size());
 			return;
 		}
@@ -286,13 +283,37 @@ struct GzWriter {
 		static_assert((uint64_t)32768 * DBGK_GZ_PIECE < (1ull << 31) && DBGK_GZ_PIECE % 16 == 0, "a slice is one call on aligned text");
 		for (uint64_t at = 0; at < n; at += slice) {
 			dbgk_gz_info info;
-			rc = dbgk_gz_deflate_device(z, (const char *)d_text + at, min<uint64_t>(slice, n - at), 0, &info);
+			int rc = dbgk_gz_deflate_device(z, (const char *)d_text + at, min<uint64_t>(slice, n - at), 0, &info);
 			if (rc) die("dbgk_gz_deflate_device", rc);
 			members.resize(info.out_bytes);
 			rc = dbgk_gz_results(z, members.data(), members.size());
 			if (rc) die("dbgk_gz_results", rc);
 			if (!members.empty() && fwrite(members.data(), 1, members.size(), raw) != members.size()) write_failed();
 		}
+	}
+	// the text of a formatter's last call (FORMAT section of dbgk.h)
+	void write_device(dbgk_fmt *text)
+	{
+		const void *d_text = nullptr;
+		uint64_t n = 0;
+		int rc = dbgk_fmt_device(text, &d_text, &n);
+		if (rc) die("dbgk_fmt_device", rc);
+		write_device(d_text, n, [&](char *dst, size_t cap) {
+			rc = dbgk_fmt_results(text, dst, cap);
+			if (rc) die("dbgk_fmt_results", rc);
+		});
+	}
+	// stream 0 .. 2 of a row writer's last call (ROWS section of dbgk.h)
+	void write_device(dbgk_maprow *rows, int stream)
+	{
+		const void *d_text = nullptr;
+		uint64_t n = 0;
+		int rc = dbgk_maprow_device(rows, stream, &d_text, &n);
+		if (rc) die("dbgk_maprow_device", rc);
+		write_device(d_text, n, [&](char *dst, size_t cap) {
+			rc = dbgk_maprow_results(rows, stream, dst, cap);
+			if (rc) die("dbgk_maprow_results", rc);
+		});
 	}
 };
 

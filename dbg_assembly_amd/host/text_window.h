@@ -1,4 +1,4 @@
-// text_window.h -- what the DBGK_TEXT=device routes of the programs share (clean_common.h, correct_error_reads.cpp, kmerfreq.cpp): the
+// text_window.h -- what the DBGK_TEXT=device routes of the programs share (clean_common.h, correct_error_reads.cpp, kmerfreq.cpp, map_common.h): the
 // switch itself, and the decompressed bytes of an input file window by window for dbgk_parse_chunk -- zlib's gzread (plain and
 // ordinary gzip alike; DBGK_GUNZIP is not looked at), what the window before left unconsumed in front of the new bytes, the refusal
 // of a record that does not end within 2 GiB of text, and the text_window test hook.
@@ -68,9 +68,11 @@ struct TextWindows {
 	}
 
 	// the parser used up `consumed` bytes of the text: the rest goes in front of the next window; a window without a whole record
-	// only makes the text longer
-	void keep_from(uint64_t consumed)
+	// only makes the text longer.  hand_back: the caller itself used less than the parser delivered (map_pair, whose other file gave
+	// fewer records): the rest of a text that ended the file is then handed out once more, as the text that ends the file.
+	void keep_from(uint64_t consumed, bool hand_back = false)
 	{
+		if (hand_back && last && consumed < n_text) last = false; // (the next gzread returns 0 again)
 		have = last ? 0 : n_text - (size_t)consumed;
 		if (have && consumed) memmove(chunk.data(), chunk.data() + consumed, have);
 	}

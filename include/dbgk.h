@@ -760,6 +760,12 @@ int dbgk_map_batch_stats(dbgk_map *m, dbgk_map_stats *out);
  * the batch has to be synchronised; the call returns when the hits are in `out`.                                           */
 int dbgk_map_reads_device(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len,
                           dbgk_map_hit *out);
+/* dbgk_map_reads_device without the copy to the host: the hits stay in the mapper's buffer for dbgk_map_hits_device and
+ * dbgk_maprow_take_hits.  Same checks, same statistics.                                                                    */
+int dbgk_map_reads_device_keep(dbgk_map *m, const char *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t max_len);
+/* the 2 n_reads hits of the last batch (any of the three calls) where they lie; valid until the next batch, dbgk_map_set_contigs or
+ * dbgk_map_destroy.  Before a successful batch: DBGK_ERR_STATE.  *d_hits is null when n_reads is 0.                          */
+int dbgk_map_hits_device(dbgk_map *m, const dbgk_map_hit **d_hits, uint64_t *n_reads);
 
 /* ---- CLEAN: clean_adapter / clean_lowqual of the clean_illumina module on the GPU (additions to ABI 7) -------------------------
  * clean_adapter aligns every read against every contaminant sequence with an ungapped local dynamic programme (match +1,
@@ -1177,6 +1183,80 @@ int dbgk_parse_recs_device(dbgk_parse *p, const dbgk_parse_rec **d_recs);
 /* ... and the text of that chunk where it lies: the copy dbgk_parse_chunk uploaded (16-byte aligned, readable up to n_bytes
  * rounded up to 16, valid until the next chunk), or the caller's own buffer of dbgk_parse_chunk_device                     */
 int dbgk_parse_text_device(dbgk_parse *p, const char **d_text, uint64_t *n_bytes);
+
+/* ---- ROWS: from the mapper's hits to the lines of map_reads' and map_pair's output files (additions to ABI 7) ----------------------------
+ * The stage behind the mapper: a batch of reads as the parser left it (the text with its records for the header lines, the bases
+ * plane with its n + 1 offsets), two dbgk_map_hit per read, and a contig table of the caller's become the text the host loops of
+ * bin/map_reads and bin/map_pair write for that batch, byte for byte, in up to three streams:
+ *   DBGK_MAPROW_READS (map_reads.cpp; one side; hits 2 i and 2 i + 1 are alignments a and b of read i)
+ *     stream 0  the 2ctg lines   row(a) "\t" row(b) "\n"        a and b on two different contigs
+ *     stream 1  the 1ctg lines   row(a) "\n"                    a alone
+ *     stream 2  the .reads.fa records of stream 0's reads, ">" id "\n" bases "\n"
+ *     counters: total_read_num, map_ctg_diff_num, map_ctg_same_num, map_no_no_num, error_map_num (a and b on one contig: no text).
+ *     A read shorter than min_read_len is neither written nor counted.
+ *   DBGK_MAPROW_PAIR (map_pair.cpp; two sides; read i of side 0 and read i of side 1 are pair i, hit 2 i of each side its alignment)
+ *     stream 0  the 2ctg lines   row(mate 1) "\t" row(mate 2) "\n"    two different contigs
+ *     stream 1  the 1ctg lines   the same line, one contig
+ *     stream 2  the gap lines    row "\n" of the one mate that is mapped
+ *     counters: total_read_pair_num, map_ctg_diff_num, map_ctg_same_num, map_ctg_gap_num, map_no_no_num.  A pair with a mate shorter
+ *     than min_read_len is neither written nor counted.
+ * A hit is mapped when its contig is not -1.  A row is
+ *   id "\t" read_len "\t" read_start "\t" read_end "\t" contig_id "\t" contig_len "\t" contig_start "\t" contig_end "\t" direct "\t" identity "%"
+ * with id the first token of the header line under the handle's delimiter set, followed by "-" and the second token if there is one (a
+ * header of delimiters only: empty; a '\r' the parser left in the line is a token byte), direct the low byte of the hit's field, and
+ * identity the host's `ostream << (float)(1.0 - (float)mismatches / align_len) * 100`, reproduced digit for digit while it prints
+ * without an exponent.  An identity below 10^-4 % (align_len near 2^24 and more) would print in exponent form: it is counted in
+ * `unprintable`, and a batch that holds one writes NO text -- the counters are valid, the streams are empty and DBGK_OK is returned;
+ * the caller formats that batch on the host.
+ * Each stream starts on a 16-byte boundary, is written in whole 16-byte vectors with the pad of the last one 0, and 64 readable bytes
+ * follow it, so dbgk_gz_deflate_device reads it where it lies.  n < 2^31, n_text < 2^31, a read below 2^31 bytes, a line below 2^32. */
+typedef struct dbgk_maprow dbgk_maprow;
+#define DBGK_MAPROW_READS 1
+#define DBGK_MAPROW_PAIR  2
+#define DBGK_MAPROW_STREAMS 3
+#define DBGK_MAPROW_TILE 4096       /* bytes of output per workgroup round of the write kernel                             */
+typedef struct dbgk_maprow_side {   /* one side of a batch: what the parser delivered for one file                          */
+	const char *text;               /* the chunk the parser parsed, n_text bytes                                            */
+	uint64_t n_text;
+	const dbgk_parse_rec *recs;     /* n records, of which head_pos and head_len are used                                   */
+	const char *bases;              /* the bases plane and its n + 1 offsets; PAIR prints the lengths alone and never reads */
+	const uint64_t *offsets;        /* (or uploads) the plane: it may be null there                                         */
+	const dbgk_map_hit *hits;       /* dbgk_maprow_rows: 2 n hits on the host; dbgk_maprow_rows_device: unused, the side's  */
+} dbgk_maprow_side;                 /* hits are the ones dbgk_maprow_take_hits took                                         */
+typedef struct dbgk_maprow_info {
+	uint64_t n;                     /* items: reads (READS) or pairs (PAIR)                                                 */
+	uint64_t counters[5];           /* the five numbers of the program's .stat file, in the order given above               */
+	uint64_t stream_bytes[DBGK_MAPROW_STREAMS]; /* bytes of each stream (without the pad)                                   */
+	uint64_t unprintable;           /* rows whose identity needs an exponent; not 0: no text, stream_bytes all 0            */
+	double ms_scan;                 /* device time: token spans + lengths + scans; segments + the write kernels             */
+	double ms_write;
+} dbgk_maprow_info;
+/* mode: DBGK_MAPROW_READS or DBGK_MAPROW_PAIR.  format_delims: the delimiter set of the id, 1 to 16 bytes of 1..127 (map_reads:
+ * ">@ \t\n"; map_pair: "@ \t" for FASTQ, "> \t" for FASTA).  min_read_len >= 0.  Anything else: DBGK_ERR_ARG before any device work.
+ * DBGK_ERR_HIP without a usable gfx950 device: there is no host fall-back                                                    */
+int dbgk_maprow_create(int32_t mode, const char *format_delims, int32_t min_read_len, int device, dbgk_maprow **out);
+int dbgk_maprow_destroy(dbgk_maprow *r);
+/* the contig table: n ids back to back, id c = names[name_offsets[c], name_offsets[c + 1]) (name_offsets[0] == 0, non-decreasing),
+ * and the length every row of contig c prints (bin/map_*: the contig's size after the short ones were emptied).  The handle is not
+ * tied to a mapper's contigs.  Replaces the earlier table; n < 2^31                                                            */
+int dbgk_maprow_set_contigs(dbgk_maprow *r, const char *names, const uint64_t *name_offsets, const uint32_t *lengths, uint64_t n);
+/* the hits of the mapper's last batch, copied device to device into side 0 or 1 of r and ordered by events on the two streams: the
+ * mapper may map its next batch at once.  Handles on different devices: DBGK_ERR_ARG; no batch mapped: DBGK_ERR_STATE          */
+int dbgk_maprow_take_hits(dbgk_maprow *r, int32_t side, dbgk_map *m);
+/* the rows of n items.  sides: one dbgk_maprow_side for READS, two for PAIR, every pointer in device memory of r's GPU, read in place
+ * and never written; text and bases 16-byte aligned, the text readable up to n_text rounded up to 16, the plane up to offsets[n]
+ * rounded up to 4.  The hits are those of dbgk_maprow_take_hits, n reads' per side (else DBGK_ERR_STATE; no contig table:
+ * DBGK_ERR_STATE).  Found on the device and answered with DBGK_ERR_ARG and no output: a mapped hit whose contig is outside the table,
+ * with a negative coordinate, align_len <= 0 or mismatches outside [0, align_len]; a header that leaves the text; offsets that
+ * decrease.  n == 0 is valid.  Work of the caller's own on the inputs has to be synchronised.  Returns when the text is complete.  */
+int dbgk_maprow_rows_device(dbgk_maprow *r, const dbgk_maprow_side *sides, uint64_t n, dbgk_maprow_info *out);
+/* the same with everything on the host, the 2 n hits of each side included, uploaded by the call                            */
+int dbgk_maprow_rows(dbgk_maprow *r, const dbgk_maprow_side *sides, uint64_t n, dbgk_maprow_info *out);
+/* stream 0 .. 2 of the last call where it lies; valid until the next call or dbgk_maprow_destroy.  Before a successful call:
+ * DBGK_ERR_STATE (also for dbgk_maprow_results)                                                                               */
+int dbgk_maprow_device(dbgk_maprow *r, int32_t stream, const void **d_text, uint64_t *n_bytes);
+/* host copy of a stream: stream_bytes bytes; a capacity below that: DBGK_ERR_ARG                                            */
+int dbgk_maprow_results(dbgk_maprow *r, int32_t stream, void *out, uint64_t capacity);
 
 /* ---- LINK: link_scaffold of the link_scaffold module on the GPU (additions to ABI 7) -------------------------------------------
  * link_scaffold turns the read pairs whose mates map_pair placed on two different contigs (the lines of *.map_pair.2ctg.gz) into
