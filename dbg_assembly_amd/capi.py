@@ -591,6 +591,7 @@ SYMBOLS = [
     ("dbgk_align_pairs", _i, [_vp, _vp, _vp, _u64, C.POINTER(AlignSummary)]),
     ("dbgk_align_results", _i, [_vp, _vp, _vp, _vp, _vp]),
     ("dbgk_align_timing_get", _i, [_vp, C.POINTER(AlignTiming)]),
+    ("dbgk_l1_forms_text", _i, [_vp, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     ("dbgk_device_count", _i, []),
     ("dbgk_abi_version", _i, []),
     ("dbgk_strerror", C.c_char_p, [_i]),
@@ -1089,6 +1090,14 @@ class Graph:
 
     def reset_timings(self):
         _chk(lib().dbgk_reset_timings(self._h), "dbgk_reset_timings")
+
+    def l1_forms(self):
+        """the level-1 kernel forms launched since the last reset / reset_timings, in launch order: a list of the forms' texts
+        (dbgk_l1_forms_text; the first 16 launches -- `l1_launches` gets the number of all of them)"""
+        buf, n = C.create_string_buffer(4096), C.c_uint32()
+        _chk(lib().dbgk_l1_forms_text(self._h, buf, len(buf), C.byref(n)), "dbgk_l1_forms_text")
+        self.l1_launches = n.value
+        return buf.value.decode().splitlines()
 
     def copy_bandwidth(self, nbytes=1 << 30, iters=10):
         g = C.c_double()

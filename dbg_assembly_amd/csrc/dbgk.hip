@@ -45,6 +45,7 @@
 #include "dbgk_simplify.h"
 #include "dbgk_wide_simplify.h"
 #include "dbgk_align.h"
+#include "dbgk_l1_form.h"
 
 // dbgk_sort.hip
 extern "C" int dbgk_internal_sort_pairs(uint64_t *d_keys, uint64_t *d_vals, uint64_t n, hipStream_t stream);
@@ -236,6 +237,10 @@ struct dbgk_handle {
 	uint64_t insert_launches = 0;
 	uint32_t partition_launches = 0;
 	uint32_t uniform_launches = 0;
+	// the level-1 forms launched since the last dbgk_reset / dbgk_reset_timings (dbgk_l1_forms_text): the first kL1FormLog of them, and how many there were
+	static constexpr uint32_t kL1FormLog = 16;
+	L1Form l1_forms[kL1FormLog] = {};
+	uint32_t l1_forms_total = 0;
 
 	TableRef tref() const { return TableRef{table, size, magic}; }
 	WTable wref() const { return WTable{wnodes, size, magic, wside}; }

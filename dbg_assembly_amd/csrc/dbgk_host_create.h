@@ -169,6 +169,7 @@ extern "C" int dbgk_reset(dbgk_handle *h)
 	HIPCHK(hipStreamSynchronize(h->stream));
 	rc = collect_spans(h);
 	if (rc) return rc;
+	h->l1_forms_total = 0;
 	return reset_state(h);
 }
 

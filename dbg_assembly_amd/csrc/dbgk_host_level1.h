@@ -188,6 +188,8 @@ static int launch_l1(dbgk_handle *h, const L1Plan &plan, const ReadBatch &rb, co
 			break;
 		}
 		if (rc) return rc;
+		if (h->l1_forms_total < dbgk_handle::kL1FormLog) h->l1_forms[h->l1_forms_total] = l.form; // what dbgk_l1_forms_text reports
+		h->l1_forms_total++;
 	}
 	return DBGK_OK;
 }

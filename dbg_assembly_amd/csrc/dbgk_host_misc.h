@@ -125,6 +125,28 @@ extern "C" int dbgk_reset_timings(dbgk_handle *h)
 	h->partition_launches = 0;
 	h->uniform_launches = 0;
 	h->prefix_launches = 0;
+	h->l1_forms_total = 0;
+	return DBGK_OK;
+}
+
+// the level-1 launches since the last dbgk_reset / dbgk_reset_timings, one line of l1_form_text() each
+extern "C" int dbgk_l1_forms_text(dbgk_handle *h, char *buf, size_t cap, uint32_t *n_launches)
+{
+	if (!h || (!buf && cap)) return DBGK_ERR_ARG;
+	if (n_launches) *n_launches = h->l1_forms_total;
+	const uint32_t n = std::min(h->l1_forms_total, dbgk_handle::kL1FormLog);
+	size_t used = 0;
+	if (cap) buf[0] = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		char text[192];
+		l1_form_text(h->l1_forms[i], text, sizeof text);
+		const size_t len = strlen(text);
+		if (used + len + 2 > cap) return DBGK_ERR_ARG; // (the line, its newline, the terminator)
+		memcpy(buf + used, text, len);
+		buf[used + len] = '\n';
+		buf[used + len + 1] = 0;
+		used += len + 1;
+	}
 	return DBGK_OK;
 }
 

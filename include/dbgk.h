@@ -1780,6 +1780,13 @@ int dbgk_align_pairs(dbgk_contig *c, const char *seqs, const uint64_t *offsets, 
 int dbgk_align_results(dbgk_contig *c, dbgk_align_row *rows, uint64_t *aligned_offsets, char *aligned_i, char *aligned_j);
 int dbgk_align_timing_get(dbgk_contig *c, dbgk_align_timing *out);
 
+/* ---- which level-1 kernels ran (additions to ABI 7) ---------------------------------------------
+ * The level-1 kernel forms that the batches of a PARTITION / WIDE record handle launched since the last dbgk_reset or
+ * dbgk_reset_timings, in launch order: one line per launch, "family=... wide_d=... ... dbg=0\n", the text the library's
+ * own error messages use for a form.  The handle keeps the first 16 launches; *n_launches (may be NULL) gets the number
+ * of all of them.  buf gets a terminated string; DBGK_ERR_ARG if cap is too small for it (4096 bytes always suffice).  */
+int dbgk_l1_forms_text(dbgk_handle *h, char *buf, size_t cap, uint32_t *n_launches);
+
 int dbgk_device_count(void);
 int dbgk_abi_version(void);
 const char *dbgk_strerror(int status);

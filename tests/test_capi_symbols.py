@@ -36,6 +36,14 @@ def test_abi_version_and_errors():
     assert L.dbgk_create(ctypes.byref(cfg), ctypes.byref(h)) == capi.ERR_ARG
 
 
+def test_l1_forms_text_checks_its_arguments():
+    """appended to ABI 7 as the align and trace calls were; argument validation needs no handle and no device"""
+    L = capi.lib()
+    n = ctypes.c_uint32(7)
+    assert L.dbgk_l1_forms_text(None, ctypes.create_string_buffer(64), 64, ctypes.byref(n)) == capi.ERR_ARG and n.value == 7
+    assert L.dbgk_abi_version() == 7
+
+
 def test_struct_layouts_match_header():
     assert ctypes.sizeof(capi.Config) == 4 + 4 + 8 + 4 + 4 + 8 + 8 + 32
     assert ctypes.sizeof(capi.Stats) == 6 * 8 + 8 + 8  # + other_bytes (ABI 5)

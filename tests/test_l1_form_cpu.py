@@ -6,7 +6,10 @@ alone: nothing is loaded into Python.
                  power of two, k < 17, many level-1 buckets, the three table widths, mixed lengths with and without the hooks, KFREQ
                  direct blocks, the WIDE record engine.  Every form of every plan must have a row in its family's list.
   the lists      74 / 12 / 6 / 6 / 6 / 6 rows, no two equal, and as many kernels of each family in the built library's code object.
+  the cases      tests/l1_form_cases.py, which tests/test_l1_forms_gpu.py runs on the GPU: one case per row, and the plan of every case on
+                 the facts of the handle the library creates for it and of its actual reads is the launch list the case expects.
 """
+import collections
 import os
 import re
 import subprocess
@@ -187,6 +190,81 @@ def test_lists_have_the_rows_of_the_library_and_no_row_twice(program):
     rows, counts = list_rows(program)
     assert counts == ROWS
     assert len(rows) == sum(ROWS.values()) == 110 and len(set(rows)) == len(rows)
+
+
+# ---- the table of cases that tests/test_l1_forms_gpu.py runs on the GPU (tests/l1_form_cases.py) -------------------------------------
+
+def handle_facts(case):
+    """the facts of the handle the case creates, without a device: the level-1 bucket count the planner gives the real table size
+    (dbgk_plan_partition), `kf` and the direct-block geometry as dbgk_host_create.h / dbgk_host_partition.h set them"""
+    from dbg_assembly_amd import capi
+    import l1_form_cases as LC
+    if case.engine == "kfreq":       # expected_kmers > 0 and k >= 13: direct blocks, size = 4^k, level-1 bucket = slot >> r
+        bits = 2 * case.k
+        r = max(20, min(26, bits - 8))
+        return dict(part=1, kfreq=1, kf=2, kmer_size=case.k, max_read_len=case.max_read_len, n1=(1 << bits) >> r, geom_size=1 << bits, size=1 << bits)
+    size = capi.find_next_prime_ref(LC.SLOTS[case.width])
+    if case.engine == "wide":
+        return dict(wide=1, wrec=1, kmer_size=case.k, max_read_len=case.max_read_len, size=size)
+    info = capi.plan_partition(size, LC.EXPECTED_KMERS)
+    assert info.table_slots == size
+    return dict(part=1, kmer_size=case.k, max_read_len=case.max_read_len, n1=info.level1_buckets, geom_size=size, size=size)
+
+
+def batch_facts(case):
+    import l1_form_cases as LC
+    lens = [len(r) for r in LC.reads(case)]
+    assert sorted(lens) == sorted(LC.lengths(case))
+    return dict(n_reads=len(lens), n_bases=sum(lens), uniform_len=lens[0] if len(set(lens)) == 1 else 0, len_max=max(lens),
+                has_long=int(max(lens) > case.max_read_len), packed=int(case.entry != "push_reads"))
+
+
+def test_cases_are_the_rows_of_the_lists(program):
+    """one case per row: 110 keys, none missing, none extra; every case is filed under its own row"""
+    import l1_form_cases as LC
+    rows, _ = list_rows(program)
+    cases = LC.cases()
+    assert sorted(cases) == sorted(r[len("row "):] for r in rows) and len(cases) == 110
+    assert all(c.row == row and row in c.launches for row, c in cases.items())
+    assert len(LC.UNSELECTABLE) <= 4 and set(LC.UNSELECTABLE) <= set(cases)
+    for row, reason in LC.UNSELECTABLE.items():
+        assert " and " in reason and any(w in reason for w in ("slots", "buckets", "k <", "k >=")), (row, reason)
+
+
+def test_every_case_plans_its_row_on_the_real_handle_facts(program):
+    """l1_plan on the facts of the handle the library creates for the case and of the recipe's actual reads gives exactly the
+    launches the case expects (times the passes); the named row is among them.  Rows in UNSELECTABLE are the only exceptions."""
+    import l1_form_cases as LC
+    seen = collections.Counter()
+    for row, case in sorted(LC.cases().items()):
+        if row in LC.UNSELECTABLE:
+            continue
+        assert case.entry != "push_reads_packed_uniform" or case.recipe[0] == "equal", row
+        launches = plan(program, handle_facts(case), batch_facts(case), case.hooks)
+        got = ["family=%s wide_d=%d c=%d ragged=%d lin=%d reg=%d packed=%d full=%d k17=%d has_dead=%d pipe=%d dbg=%d" % tuple(
+            l[f] for f in "family wide_d c ragged lin reg packed full k17 has_dead pipe dbg".split()) for l in launches]
+        assert got * case.passes == case.launches and row in got, (row, case, got)
+        if "reg=1" in row:           # two whole regular tiles of 128 reads, then the 44 reads behind them
+            assert [(l["first_read"], l["n_reads"], l["Q"]) for l in launches] == [(0, 256, 8), (256, 44, 8)], launches
+        seen[(case.engine, case.width)] += 1
+    # the tiers: small tables / tables of 2^31 and of 2^32 slots and more
+    assert seen == {("graph", 0): 32, ("kfreq", 0): 14, ("wide", 0): 4, ("graph", 1): 32, ("wide", 1): 4, ("graph", 2): 20, ("wide", 2): 4}, seen
+
+
+def test_case_reads_hold_what_makes_rows_go_wrong():
+    """every read set: both strands of a small genome, a read some tens of times, poly-A and poly-T, N, lower case, one other byte;
+    mixed lengths: a read whose last lane holds a single window"""
+    import l1_form_cases as LC
+    for row, case in LC.cases().items():
+        reads = LC.reads(case)
+        assert reads == LC.reads(case) and len(reads) == LC.N_READS, row
+        count = collections.Counter(reads)
+        assert 20 <= max(v for r, v in count.items() if set(r) - set(b"AT")) <= 40, row
+        assert any(set(r) == set(b"A") for r in reads) and any(set(r) == set(b"T") for r in reads), row
+        assert sum(r.count(b"N") for r in reads) == 1 and sum(r.count(b"*") for r in reads) == 1, row
+        assert sum(len(bytes(b for b in r if b not in b"ACGTNacgtn")) for r in reads) == 1 and any(r != r.upper() for r in reads), row
+        if case.recipe[0] in ("mixed", "trimmed"):
+            assert any((len(r) - case.k + 1) % case.recipe[2] == 1 for r in reads), row
 
 
 def test_built_library_has_one_kernel_per_row(program, tmp_path):
