@@ -73,6 +73,8 @@ static int hip_fail(hipError_t e, const char *what, int line)
 		if (e__ != hipSuccess) return hip_fail(e__, #expr, __LINE__);  \
 	} while (0)
 
+#include "dbgk_host_stage.h"
+
 // ---------------------------------------------------------------------------------------------
 // handle
 // ---------------------------------------------------------------------------------------------
@@ -84,39 +86,67 @@ constexpr uint64_t kHeavyHitterSlots = 4194301; // side table for the surplus of
 enum Phase { PH_MARK = 0, PH_INSERT, PH_PARTITION, PH_BUILD, PH_FIXUP, PH_FINALIZE, PH_L2_BUILD_WALL, PH_COUNT };
 
 struct TimedSpan {
-	hipEvent_t a, b;
-	int phase;
+	StageEvent a, b;
+	int phase = 0;
 };
 
 struct StageSlot {
-	char *h_bases = nullptr;
-	uint64_t *h_offsets = nullptr;
-	char *d_bases = nullptr;
-	uint64_t *d_offsets = nullptr;
-	uint32_t *d_start = nullptr;
-	uint32_t *d_dead = nullptr;
-	hipEvent_t done = nullptr;      // the kernels that read the device buffers have run
-	hipEvent_t copied = nullptr;    // the host-to-device copies of the batch have run (copy stream)
+	PinBuf<char> h_bases;
+	PinBuf<uint64_t> h_offsets;
+	DevBuf<char> d_bases;
+	DevBuf<uint64_t> d_offsets;
+	DevBuf<uint32_t> d_start;
+	DevBuf<uint32_t> d_dead;
+	StageEvent done;                // the kernels that read the device buffers have run
+	StageEvent copied;              // the host-to-device copies of the batch have run (copy stream)
 	bool busy = false;
 	bool acquired = false;          // handed out by dbgk_push_acquire and not committed yet
 };
 
+// What owns the memory behind the PartStore / WPartStore views that the kernels take (setup_partition, setup_wide_partition fill
+// the views).  A resize re-makes the stores: it assigns a fresh one.
+struct PartBufs {
+	DevBuf<uint64_t> l1, l2, inbox, mid;
+	DevBuf<uint32_t> cnt1, cnt2, inbox_cnt, cnt_mid;
+	DevBuf<Node> ovf, spill, hh, outgoing;
+	DevBuf<unsigned long long> ovf_n, outgoing_n;
+	DevBuf<uint32_t> tile_prefix;    // [n_ranks * B + 1] level-2 tile plan
+	DevBuf<uint32_t> tile_prefix2;   // [nb_own * fan_mid + 1]
+	DevBuf<uint32_t> l2_done;        // EARLY level 2 (early_l2): records per level-1 bucket that level 2 has taken already; null = not in use
+	DevBuf<unsigned int> region_cursor; // [kMaxBuildLaunches] work cursors of the persistent build launches
+};
+
+struct WPartBufs {
+	DevBuf<ull2> l1, l2, inbox;      // inbox, sharded: [n_l1][cap1] records of my buckets from every rank
+	DevBuf<uint32_t> cnt1, cnt2, inbox_cnt, tile_prefix;
+	DevBuf<dbgk_node32> ovf, spill, outgoing;
+	DevBuf<unsigned long long> ovf_n, outgoing_n;
+	DevBuf<unsigned int> cursor;
+	DevBuf<dbgk_node32> side_out;    // [kWideSideSlots + 1] dbgk_shard_side_export
+	DevBuf<unsigned long long> side_n;
+};
+
+// what plan_partition decides for a configuration and a modulus: engine, shard, and the geometry of its record stores
+struct PartPlan {
+	bool part = false, sharded = false, three = false;
+	uint32_t fan_mid = 0, shard_rank = 0;
+	uint64_t tslots = 0;
+	PartGeom geom, g_mid, g_fin;
+};
+
 } // namespace
 
-struct dbgk_handle {
+struct dbgk_handle : StageDev {
 	dbgk_config cfg;
-	int device = 0;
-	int n_cu = 256;
 	int grid = 2048;
-	hipStream_t stream = nullptr;
 
-	Node *table = nullptr;
+	DevBuf<Node> table;
 	uint64_t size = 0;            // hash modulus: slot = hash_code(key) % size (the GLOBAL table when sharded)
 	uint64_t tslots = 0;          // slots held by `table` (== size unless sharded)
 	ModMagic magic;
 
-	Counters *d_ctr = nullptr;
-	Counters *h_ctr = nullptr; // pinned
+	DevBuf<Counters> d_ctr;
+	PinBuf<Counters> h_ctr;
 
 	// host-buffer staging
 	StageSlot slots[2];
@@ -124,20 +154,16 @@ struct dbgk_handle {
 	int next_slot = 0;
 
 	// bitmaps for the device-pointer path
-	uint32_t *dev_start = nullptr, *dev_dead = nullptr;
-	uint64_t dev_bits_words = 0;
+	DevBuf<uint32_t> dev_start, dev_dead;
 	// level 1 for reads of any lengths (k_extract_scatter_prefix): the per-read lane prefix of the current batch, and the
 	// 2-bit form of a batch that came as ASCII.  One set per handle: batches follow each other on one stream.
-	ReadLanes *pf_ent = nullptr;
-	uint32_t *pf_tile_first = nullptr;
-	PrefixTile *pf_tiles = nullptr;
-	unsigned long long *pf_bsum = nullptr;
-	PrefixTotals *pf_tot = nullptr;
-	uint64_t pf_cap_reads = 0, pf_cap_tiles = 0;
-	uint32_t *pf_packed = nullptr;
-	uint64_t pf_packed_words = 0;
-	uint64_t *uni_offsets = nullptr; // offsets made on the device for a batch that came without (dbgk_push_reads_packed_uniform*) and needs them
-	uint64_t uni_cap = 0;
+	DevBuf<ReadLanes> pf_ent;
+	DevBuf<uint32_t> pf_tile_first;
+	DevBuf<PrefixTile> pf_tiles;
+	DevBuf<unsigned long long> pf_bsum;
+	DevBuf<PrefixTotals> pf_tot;
+	DevBuf<uint32_t> pf_packed;
+	DevBuf<uint64_t> uni_offsets; // offsets made on the device for a batch that came without (dbgk_push_reads_packed_uniform*) and needs them
 	uint32_t prefix_launches = 0;
 
 	bool finalized = false;
@@ -146,20 +172,19 @@ struct dbgk_handle {
 
 	// first-seen tracking (DBGK_FLAG_TRACK_FIRST_SEEN, DIRECT engine)
 	bool track = false;
-	unsigned long long *first_pos = nullptr; // [tslots]
+	DevBuf<unsigned long long> first_pos;    // [tslots]
 	uint64_t pos_base = 0;                   // bases pushed so far
 
 	bool wide = false;            // WIDE engine: 128-bit keys, 32-byte nodes (dbgk_wide_kernels.h)
-	WNode *wnodes = nullptr;      // [size]
-	WNode *wside = nullptr;       // [kWideSideSlots]
+	DevBuf<WNode> wnodes;         // [size]
+	DevBuf<WNode> wside;          // [kWideSideSlots]
 	// WIDE through radix-partitioned records (dbgk_wide_partition.h): expected_kmers > 0 and a feasible geometry
 	bool wpart = false;
 	bool wbuilt = false;          // the records have been turned into the table: later batches use the atomic kernels
 	bool wzero_pending = false;   // the main table is stale (reset without memset): the build overwrites every slot
 	WPartGeom wgeom;
-	WPartStore wstore;
-	uint32_t *w_tile_prefix = nullptr;
-	unsigned int *w_cursor = nullptr;
+	WPartStore wstore = {};       // the kernels' view of `wbuf`
+	WPartBufs wbuf;
 	// shards and passes of the wide record path (WPartGeom): `wmulti` handles follow the strict protocol
 	// begin_pass -> pushes -> [exchange] -> end_pass, ..., finalize; nothing streams through the atomic kernels
 	bool wmulti = false;          // sharded and / or several passes
@@ -167,10 +192,6 @@ struct dbgk_handle {
 	bool wplanned = false;        // level-2 tile plan of the current pass made
 	uint32_t wnext = 0;           // own-bucket indices [0, wnext) of the current pass have been built
 	uint32_t wpasses_done = 0;
-	ull2 *winbox = nullptr;       // sharded: [n_l1][cap1] records of my buckets from every rank
-	uint32_t *winbox_cnt = nullptr;
-	dbgk_node32 *w_side_out = nullptr;      // [kWideSideSlots + 1] dbgk_shard_side_export
-	unsigned long long *w_side_n = nullptr;
 	unsigned long long wsaved_totals[2] = {0, 0}; // total_kmers, stored_kmers before a repeated pass over the input
 	uint64_t wsaved_reads = 0;
 	unsigned long long wsaved_other = 0;          // ... and Counters::other_bytes
@@ -180,11 +201,11 @@ struct dbgk_handle {
 	// KFREQ engine: counts[4^k] instead of a node table
 	bool kfreq = false;
 	bool kf_blocks = false;       // KFREQ through the PARTITION engine in its direct-block form (geom.kf == 2, dbgk_partition.h)
-	uint8_t *counts = nullptr;
+	DevBuf<uint8_t> counts;
 	uint64_t n_counts = 0;
 	uint64_t kf_distinct = 0, kf_sum = 0;
-	unsigned long long *kf_bins = nullptr; // the 256 device bins of dbgk_kfreq_spectrum, made at its first call
-	hipEvent_t kf_ev[2] = {nullptr, nullptr};
+	DevBuf<unsigned long long> kf_bins;    // the 256 device bins of dbgk_kfreq_spectrum, made at its first call
+	StageEvent kf_ev[2];
 	double kf_spectrum_ms = 0;             // device time of the last k_kf_spectrum
 
 	// PARTITION engine
@@ -193,7 +214,6 @@ struct dbgk_handle {
 	bool part_planned = false;    // level-2 tile plan made for this step (part_plan)
 	uint32_t next_bucket = 0;     // own level-1 buckets [0, next_bucket) have been handed to level 2 + build
 	uint32_t chunks_used = 0;     // chunk events consumed this step
-	unsigned int *region_cursor = nullptr; // [kMaxBuildLaunches] work cursors of the persistent build launches
 	uint32_t cursors_used = 0;
 	TimedSpan wall_span;
 	bool zero_pending = false;    // table content is stale and must be zeroed before a direct-path write
@@ -201,9 +221,8 @@ struct dbgk_handle {
 	uint64_t pending_kmers = 0;   // upper bound of the k-mer occurrences sitting in the record store
 	uint64_t store_capacity = 0;  // occurrences the record store is sized for (expected_kmers)
 	PartGeom geom;
-	PartStore store;
-	uint32_t *tile_prefix = nullptr; // [n_ranks * B + 1] level-2 tile plan
-	uint32_t *l2_done = nullptr;     // EARLY level 2 (early_l2): records per level-1 bucket that level 2 has taken already; null = not in use
+	PartStore store = {};         // the kernels' view of `pbuf`
+	PartBufs pbuf;
 	uint64_t l2_seen_kmers = 0;      // pending_kmers when the last early level-2 round was launched
 	// THREE-LEVEL partition for tables whose level-1 buckets hold 4096 regions (2^33 slots and more): level 2
 	// runs as two passes of the same kernel -- MID: every level-1 bucket into fan_mid = n2 / 64 mid buckets (store `mid`,
@@ -213,24 +232,19 @@ struct dbgk_handle {
 	bool three = false;
 	uint32_t fan_mid = 0;
 	PartGeom g_mid, g_fin;
-	PartStore s_mid, s_fin;
-	uint64_t *mid = nullptr;
-	uint32_t *cnt_mid = nullptr;
-	uint32_t *tile_prefix2 = nullptr; // [nb_own * fan_mid + 1]
-	hipStream_t stream2 = nullptr;   // finalize: region build of bucket chunk c runs here while level 2 of chunk c+1 runs on `stream`
-	std::vector<hipEvent_t> chunk_ev; // level 2 of chunk c finished
-	hipEvent_t join_ev = nullptr;
+	PartStore s_mid = {}, s_fin = {};
+	StageStream stream2;             // finalize: region build of bucket chunk c runs here while level 2 of chunk c+1 runs on `stream`
+	std::vector<StageEvent> chunk_ev; // level 2 of chunk c finished
+	StageEvent join_ev;
 	// sharding: the handle owns slots [geom.slot_lo, geom.slot_hi) of a GLOBAL table of `size` slots
 	bool sharded = false;         // shard_count > 1
 	bool exchanged = false;       // the caller has filled the inbox (all-to-all) for this step
-	uint64_t *inbox = nullptr;    // [n_ranks][B][cap1]
-	uint32_t *inbox_cnt = nullptr;
 
 	// large device-to-host copies (the host KmerSet): slices through pinned buffers, host threads moving them on
-	std::vector<void *> d2h_stage;
-	std::vector<hipEvent_t> d2h_ev;
-	hipEvent_t source_read = nullptr; // dbgk_push_reads from a pinned caller buffer: the last host-to-device copy out of it
-	hipStream_t copy_stream = nullptr; // host-to-device copies of the batches: batch i+1 travels while the kernels of batch i run
+	std::vector<PinBuf<char>> d2h_stage;
+	std::vector<StageEvent> d2h_ev;
+	StageEvent source_read;       // dbgk_push_reads from a pinned caller buffer: the last host-to-device copy out of it
+	StageStream copy_stream;      // host-to-device copies of the batches: batch i+1 travels while the kernels of batch i run
 
 	std::vector<TimedSpan> spans, free_spans;
 	float phase_ms[PH_COUNT] = {0};
@@ -255,11 +269,10 @@ static int use_device(dbgk_handle *h)
 static int span_begin(dbgk_handle *h, int phase, TimedSpan &s, hipStream_t stream = nullptr)
 {
 	if (!h->free_spans.empty()) {
-		s = h->free_spans.back();
+		s = std::move(h->free_spans.back());
 		h->free_spans.pop_back();
 	} else {
-		HIPCHK(hipEventCreate(&s.a));
-		HIPCHK(hipEventCreate(&s.b));
+		if (s.a.create() || s.b.create()) return DBGK_ERR_HIP;
 	}
 	s.phase = phase;
 	HIPCHK(hipEventRecord(s.a, stream ? stream : h->stream));
@@ -269,7 +282,7 @@ static int span_begin(dbgk_handle *h, int phase, TimedSpan &s, hipStream_t strea
 static int span_end(dbgk_handle *h, TimedSpan &s, hipStream_t stream = nullptr)
 {
 	HIPCHK(hipEventRecord(s.b, stream ? stream : h->stream));
-	h->spans.push_back(s);
+	h->spans.push_back(std::move(s));
 	return DBGK_OK;
 }
 
@@ -284,7 +297,7 @@ static int collect_spans(dbgk_handle *h)
 		h->phase_ms[s.phase] += ms;
 		if (s.phase == PH_INSERT) h->insert_launches++;
 		if (s.phase == PH_PARTITION) h->partition_launches++;
-		h->free_spans.push_back(s);
+		h->free_spans.push_back(std::move(s));
 	}
 	h->spans.clear();
 	return DBGK_OK;
@@ -335,93 +348,14 @@ extern "C" const char *dbgk_strerror(int status)
 	}
 }
 
-// record stores of the PARTITION engine (re-allocated when the table is resized: the geometry changes)
-static void free_partition_stores(dbgk_handle *h)
-{
-	for (void *p : {(void *)h->store.l1, (void *)h->store.l2, (void *)h->store.cnt1, (void *)h->store.cnt2, (void *)h->store.ovf,
-	                (void *)h->store.spill, (void *)h->store.ovf_n, (void *)h->tile_prefix, (void *)h->store.hh, (void *)h->region_cursor, (void *)h->l2_done,
-	                (void *)h->mid, (void *)h->cnt_mid, (void *)h->tile_prefix2,
-	                (void *)h->inbox, (void *)h->inbox_cnt, (void *)h->store.outgoing, (void *)h->store.outgoing_n})
-		if (p) (void)hipFree(p);
-	memset(&h->store, 0, sizeof h->store);
-	h->tile_prefix = nullptr;
-	h->l2_done = nullptr;
-	h->region_cursor = nullptr;
-	h->inbox = nullptr;
-	h->inbox_cnt = nullptr;
-	h->mid = nullptr;
-	h->cnt_mid = nullptr;
-	h->tile_prefix2 = nullptr;
-}
-
-static void free_wide_partition(dbgk_handle *h)
-{
-	WPartStore &P = h->wstore;
-	for (void *p : {(void *)P.l1, (void *)P.cnt1, (void *)P.l2, (void *)P.cnt2, (void *)P.ovf, (void *)P.spill, (void *)P.ovf_n, (void *)h->w_tile_prefix,
-	                (void *)h->w_cursor, (void *)h->winbox, (void *)h->winbox_cnt, (void *)P.outgoing, (void *)P.outgoing_n, (void *)h->w_side_out,
-	                (void *)h->w_side_n})
-		if (p) (void)hipFree(p);
-	memset(&P, 0, sizeof P);
-	h->w_tile_prefix = nullptr;
-	h->w_cursor = nullptr;
-	h->winbox = nullptr;
-	h->winbox_cnt = nullptr;
-	h->w_side_out = nullptr;
-	h->w_side_n = nullptr;
-}
-
-static void free_handle(dbgk_handle *h)
+// what dbgk_destroy does behind its null check: every stream of the handle idle with its device current, then the owners free
+static void close_handle(dbgk_handle *h)
 {
 	if (!h) return;
 	(void)hipSetDevice(h->device);
 	if (h->stream2) (void)hipStreamSynchronize(h->stream2); // region builds of an unfinished ranged finalize
 	if (h->stream) (void)hipStreamSynchronize(h->stream);
-	for (void *q : {(void *)h->pf_ent, (void *)h->pf_tile_first, (void *)h->pf_tiles, (void *)h->pf_bsum, (void *)h->pf_tot, (void *)h->pf_packed, (void *)h->uni_offsets})
-		if (q) (void)hipFree(q);
-	for (void *p : h->d2h_stage)
-		if (p) (void)hipHostFree(p);
-	for (hipEvent_t e : h->d2h_ev)
-		if (e) (void)hipEventDestroy(e);
-	if (h->source_read) (void)hipEventDestroy(h->source_read);
-	if (h->copy_stream) {
-		(void)hipStreamSynchronize(h->copy_stream);
-		(void)hipStreamDestroy(h->copy_stream);
-	}
-	for (auto &s : h->slots) {
-		if (s.h_bases) (void)hipHostFree(s.h_bases);
-		if (s.h_offsets) (void)hipHostFree(s.h_offsets);
-		if (s.d_bases) (void)hipFree(s.d_bases);
-		if (s.d_offsets) (void)hipFree(s.d_offsets);
-		if (s.d_start) (void)hipFree(s.d_start);
-		if (s.d_dead) (void)hipFree(s.d_dead);
-		if (s.done) (void)hipEventDestroy(s.done);
-		if (s.copied) (void)hipEventDestroy(s.copied);
-	}
-	for (auto &v : {&h->spans, &h->free_spans})
-		for (auto &s : *v) {
-			(void)hipEventDestroy(s.a);
-			(void)hipEventDestroy(s.b);
-		}
-	if (h->dev_start) (void)hipFree(h->dev_start);
-	if (h->dev_dead) (void)hipFree(h->dev_dead);
-	if (h->part) {
-		free_partition_stores(h);
-		for (hipEvent_t e : h->chunk_ev) (void)hipEventDestroy(e);
-		if (h->join_ev) (void)hipEventDestroy(h->join_ev);
-		if (h->stream2) (void)hipStreamDestroy(h->stream2);
-	}
-	if (h->wpart) free_wide_partition(h);
-	if (h->wnodes) (void)hipFree(h->wnodes);
-	if (h->wside) (void)hipFree(h->wside);
-	if (h->table) (void)hipFree(h->table);
-	if (h->counts) (void)hipFree(h->counts);
-	if (h->kf_bins) (void)hipFree(h->kf_bins);
-	for (hipEvent_t e : h->kf_ev)
-		if (e) (void)hipEventDestroy(e);
-	if (h->first_pos) (void)hipFree(h->first_pos);
-	if (h->d_ctr) (void)hipFree(h->d_ctr);
-	if (h->h_ctr) (void)hipHostFree(h->h_ctr);
-	if (h->stream) (void)hipStreamDestroy(h->stream);
+	if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
 	delete h;
 }
 
@@ -448,11 +382,11 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 	auto add = [&](void *q, size_t bytes) { z.p[ne] = q; z.dwords[ne] = (uint32_t)(bytes / 4); ne++; };
 	add(h->store.cnt1, (size_t)h->geom.n_ranks * h->geom.B * h->geom.n_sub * 4);
 	add(h->store.cnt2, (size_t)h->geom.nb_own * h->geom.n2 * 4);
-	if (h->three) add(h->cnt_mid, (size_t)h->geom.nb_own * h->fan_mid * 4);
+	if (h->three) add(h->pbuf.cnt_mid, (size_t)h->geom.nb_own * h->fan_mid * 4);
 	add(h->store.ovf_n, 16);
 	add(h->store.outgoing_n, 8);
-	if (h->l2_done) add(h->l2_done, (size_t)h->geom.n_ranks * h->geom.B * h->geom.n_sub * 8); // done[] and upto[]
-	add(h->region_cursor, (kMaxBuildLaunches + 2) * sizeof(unsigned int)); // one work cursor per build launch of the next build, + the exact pass's cursor and count
+	if (h->pbuf.l2_done) add(h->pbuf.l2_done, (size_t)h->geom.n_ranks * h->geom.B * h->geom.n_sub * 8); // done[] and upto[]
+	add(h->pbuf.region_cursor, (kMaxBuildLaunches + 2) * sizeof(unsigned int)); // one work cursor per build launch of the next build, + the exact pass's cursor and count
 	hipLaunchKernelGGL(k_zero_list, dim3(64), dim3(kBlock), 0, h->stream, z, with_counters ? h->d_ctr : (Counters *)nullptr);
 	HIPCHK(hipGetLastError());
 	h->part_built = false;
@@ -480,7 +414,6 @@ static int clear_record_store(dbgk_handle *h, bool with_counters = false /* also
 #include "dbgk_host_misc.h"
 #include "dbgk_comm.h"
 #include "dbgk_host_wide_links.h"
-#include "dbgk_host_stage.h"
 #include "dbgk_host_emit.h"
 #include "dbgk_host_annot.h"
 #include "dbgk_host_correct.h"

@@ -84,7 +84,7 @@ extern "C" int dbgk_comm_destroy(dbgk_comm *c)
 		if (i < c->ev.size())
 			for (hipEvent_t e : c->ev[i]) (void)hipEventDestroy(e);
 		if (i < c->cnt_ev.size() && c->cnt_ev[i]) (void)hipEventDestroy(c->cnt_ev[i]);
-		free_handle(c->h[i]);
+		close_handle(c->h[i]);
 	}
 	if (c->stage) (void)hipHostFree(c->stage);
 	delete c;
@@ -181,7 +181,7 @@ static int comm_exchange_and_build(dbgk_comm *c)
 		if (rc) return rc;
 		for (uint32_t s = 0; s < n; s++) {
 			dbgk_handle *S = c->h[s];
-			rc = comm_copy(D, reinterpret_cast<char *>(D->inbox_cnt) + s * cnt_chunk_bytes, S,
+			rc = comm_copy(D, reinterpret_cast<char *>(D->pbuf.inbox_cnt.p) + s * cnt_chunk_bytes, S,
 			               reinterpret_cast<const char *>(S->store.cnt1) + d * cnt_chunk_bytes, cnt_chunk_bytes, c->copy_stream[d]);
 			if (rc) return rc;
 		}
@@ -205,7 +205,7 @@ static int comm_exchange_and_build(dbgk_comm *c)
 			const uint64_t off = (uint64_t)ranges[p].first * bucket_bytes, len = (uint64_t)(ranges[p].second - ranges[p].first) * bucket_bytes;
 			for (uint32_t s = 0; s < n; s++) {
 				dbgk_handle *S = c->h[s];
-				rc = comm_copy(D, reinterpret_cast<char *>(D->inbox) + s * chunk_bytes + off, S,
+				rc = comm_copy(D, reinterpret_cast<char *>(D->pbuf.inbox.p) + s * chunk_bytes + off, S,
 				               reinterpret_cast<const char *>(S->store.l1) + d * chunk_bytes + off, len, c->copy_stream[d]);
 				if (rc) return rc;
 			}
@@ -254,7 +254,7 @@ static int comm_exchange_and_build(dbgk_comm *c)
 			if (rc) return rc;
 			HIPCHK(hipMemcpy(buf.data(), c->h[d]->store.cnt1, buf.size() * 4, hipMemcpyDeviceToHost));
 			for (uint32_t v : buf) sent += v;
-			HIPCHK(hipMemcpy(buf.data(), c->h[d]->inbox_cnt, buf.size() * 4, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(buf.data(), c->h[d]->pbuf.inbox_cnt, buf.size() * 4, hipMemcpyDeviceToHost));
 			for (uint32_t v : buf) received += v;
 		}
 		if (sent != received) {
@@ -362,7 +362,7 @@ static int comm_wide_finalize(dbgk_comm *c)
 			if (rc) return rc;
 			for (uint32_t s = 0; s < n; s++) {
 				dbgk_handle *S = c->h[s];
-				rc = comm_copy(D, reinterpret_cast<char *>(D->winbox_cnt) + s * cnt_chunk_bytes, S,
+				rc = comm_copy(D, reinterpret_cast<char *>(D->wbuf.inbox_cnt.p) + s * cnt_chunk_bytes, S,
 				               reinterpret_cast<const char *>(S->wstore.cnt1) + d * cnt_chunk_bytes, cnt_chunk_bytes, c->copy_stream[d]);
 				if (rc) return rc;
 			}
@@ -388,7 +388,7 @@ static int comm_wide_finalize(dbgk_comm *c)
 			if (n > 1)
 				for (uint32_t s = 0; s < n; s++) {
 					dbgk_handle *S = c->h[s];
-					rc = comm_copy(D, reinterpret_cast<char *>(D->winbox) + s * chunk_bytes + off, S,
+					rc = comm_copy(D, reinterpret_cast<char *>(D->wbuf.inbox.p) + s * chunk_bytes + off, S,
 					               reinterpret_cast<const char *>(S->wstore.l1) + d * chunk_bytes + off, len, c->copy_stream[d]);
 					if (rc) return rc;
 				}
@@ -435,7 +435,7 @@ static int comm_wide_finalize(dbgk_comm *c)
 			if (rc) return rc;
 			HIPCHK(hipMemcpy(buf.data(), c->h[d]->wstore.cnt1, buf.size() * 4, hipMemcpyDeviceToHost));
 			for (uint32_t v : buf) sent += v;
-			HIPCHK(hipMemcpy(buf.data(), c->h[d]->winbox_cnt, buf.size() * 4, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(buf.data(), c->h[d]->wbuf.inbox_cnt, buf.size() * 4, hipMemcpyDeviceToHost));
 			for (uint32_t v : buf) received += v;
 		}
 		if (sent != received) {
@@ -572,7 +572,7 @@ extern "C" int dbgk_comm_resize(dbgk_comm *c, uint64_t new_slots)
 	std::vector<dbgk_handle *> fresh(n, nullptr);
 	auto drop_fresh = [&]() {
 		for (dbgk_handle *f : fresh)
-			if (f) free_handle(f);
+			if (f) close_handle(f);
 	};
 	for (uint32_t i = 0; i < n && rc == DBGK_OK; i++) {
 		dbgk_config one = c->cfg;
@@ -680,7 +680,7 @@ extern "C" int dbgk_comm_resize(dbgk_comm *c, uint64_t new_slots)
 		return rc;
 	}
 	for (uint32_t i = 0; i < n; i++) {
-		free_handle(c->h[i]);
+		close_handle(c->h[i]);
 		c->h[i] = fresh[i];
 	}
 	c->cfg.table_slots = new_slots;

@@ -31,25 +31,25 @@ template <int DBG>
 static void launch_l2(dbgk_handle *h, int grid, uint32_t j0, uint32_t j1)
 {
 	if (h->three) { // mid pass, plan of the mid buckets filled so far, final pass (see the handle's comment)
-		hipLaunchKernelGGL(k_scatter_l2<0>, dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->g_mid, h->s_mid, h->tile_prefix, h->d_ctr, j0, j1);
-		hipLaunchKernelGGL(k_plan_l2, dim3(1), dim3(kMaxBuckets), 0, h->stream, h->g_fin, h->s_fin, h->tile_prefix2);
-		hipLaunchKernelGGL(k_scatter_l2<0>, dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->g_fin, h->s_fin, h->tile_prefix2, h->d_ctr,
+		hipLaunchKernelGGL(k_scatter_l2<0>, dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->g_mid, h->s_mid, h->pbuf.tile_prefix, h->d_ctr, j0, j1);
+		hipLaunchKernelGGL(k_plan_l2, dim3(1), dim3(kMaxBuckets), 0, h->stream, h->g_fin, h->s_fin, h->pbuf.tile_prefix2);
+		hipLaunchKernelGGL(k_scatter_l2<0>, dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->g_fin, h->s_fin, h->pbuf.tile_prefix2, h->d_ctr,
 		                   j0 * h->fan_mid, j1 * h->fan_mid);
 		return;
 	}
 	if (h->geom.n2 > 2048u) // tables of 2^33 slots and more
-		hipLaunchKernelGGL((k_scatter_l2<0, 4096>), dim3(grid), dim3(l2_threads(4096)), sizeof(ScatterLdsL2T<4096>), h->stream, h->geom, h->store, h->tile_prefix, h->d_ctr, j0, j1);
+		hipLaunchKernelGGL((k_scatter_l2<0, 4096>), dim3(grid), dim3(l2_threads(4096)), sizeof(ScatterLdsL2T<4096>), h->stream, h->geom, h->store, h->pbuf.tile_prefix, h->d_ctr, j0, j1);
 	else if (h->geom.n2 > (uint32_t)kMaxBuckets) // 2^32 .. 2^33 slots
-		hipLaunchKernelGGL((k_scatter_l2<0, 2048>), dim3(grid), dim3(l2_threads(2048)), sizeof(ScatterLdsL2T<2048>), h->stream, h->geom, h->store, h->tile_prefix, h->d_ctr, j0, j1);
+		hipLaunchKernelGGL((k_scatter_l2<0, 2048>), dim3(grid), dim3(l2_threads(2048)), sizeof(ScatterLdsL2T<2048>), h->stream, h->geom, h->store, h->pbuf.tile_prefix, h->d_ctr, j0, j1);
 	else if (h->geom.kf == 2u) // KFREQ, direct blocks: 32-bit level-1 records (n2 <= 1024 always)
-		hipLaunchKernelGGL((k_scatter_l2<0, kMaxBuckets, true>), dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->geom, h->store, h->tile_prefix, h->d_ctr, j0, j1);
+		hipLaunchKernelGGL((k_scatter_l2<0, kMaxBuckets, true>), dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->geom, h->store, h->pbuf.tile_prefix, h->d_ctr, j0, j1);
 	else
-		hipLaunchKernelGGL(k_scatter_l2<DBG>, dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->geom, h->store, h->tile_prefix, h->d_ctr, j0, j1);
+		hipLaunchKernelGGL(k_scatter_l2<DBG>, dim3(grid), dim3(l2_threads(kMaxBuckets)), sizeof(ScatterLdsL2), h->stream, h->geom, h->store, h->pbuf.tile_prefix, h->d_ctr, j0, j1);
 }
 
 static RedoList redo_list(dbgk_handle *h)
 {
-	return RedoList{h->region_cursor + kMaxBuildLaunches + 2, h->region_cursor + kMaxBuildLaunches + 1, h->geom.n_regions_own};
+	return RedoList{h->pbuf.region_cursor + kMaxBuildLaunches + 2, h->pbuf.region_cursor + kMaxBuildLaunches + 1, h->geom.n_regions_own};
 }
 
 // FAST form of the insert (four records per thread in flight, plain adds on the link words, regions whose counters pass 255
@@ -75,7 +75,7 @@ static void launch_build(dbgk_handle *h, hipStream_t stream, uint32_t first_regi
 #undef DBGK_KFB
 		return;
 	}
-	Node *counts = reinterpret_cast<Node *>(h->counts);
+	Node *counts = reinterpret_cast<Node *>(h->counts.p);
 #define DBGK_BUILD(D, KF, INCR, FAST, TABLE) \
 	hipLaunchKernelGGL((k_build_regions<D, KF, INCR, FAST>), dim3(grid), dim3(kBuildThreads), sizeof(BuildLds), stream, h->geom, h->store, TABLE, h->d_ctr, \
 	                   first_region, n_regions, cursor, redo)
@@ -98,7 +98,7 @@ static void launch_build_redo(dbgk_handle *h, hipStream_t stream)
 {
 	const uint32_t grid = (uint32_t)h->n_cu * 2u;
 	const RedoList redo = redo_list(h);
-	unsigned int *cursor = h->region_cursor + kMaxBuildLaunches;
+	unsigned int *cursor = h->pbuf.region_cursor + kMaxBuildLaunches;
 	if (h->geom.kf == 2u) {
 		if (h->incr)
 			hipLaunchKernelGGL((k_kf_build_blocks<true, false, true>), dim3(grid), dim3(kBuildThreads), sizeof(KfBlockLds), stream, h->geom, h->store,
@@ -108,7 +108,7 @@ static void launch_build_redo(dbgk_handle *h, hipStream_t stream)
 			                   h->counts, h->d_ctr, 0u, 0u, cursor, redo);
 		return;
 	}
-	Node *counts = reinterpret_cast<Node *>(h->counts);
+	Node *counts = reinterpret_cast<Node *>(h->counts.p);
 #define DBGK_REDO(KF, INCR, TABLE) \
 	hipLaunchKernelGGL((k_build_regions<0, KF, INCR, false, true>), dim3(grid), dim3(kBuildThreads), sizeof(BuildLds), stream, h->geom, h->store, TABLE, \
 	                   h->d_ctr, 0u, 0u, cursor, redo)
@@ -137,7 +137,7 @@ static void launch_build_redo(dbgk_handle *h, hipStream_t stream)
 constexpr uint64_t kEarlyL2Min = 8ull << 20;
 static int early_l2(dbgk_handle *h)
 {
-	if (!h->part || !h->l2_done || h->part_planned || h->part_built) return DBGK_OK;
+	if (!h->part || !h->pbuf.l2_done || h->part_planned || h->part_built) return DBGK_OK;
 	const char *e_min = dbgk_hook("early_l2_min"); // (read per call: the tests ask for a round after every small batch)
 	const uint64_t min_kmers = e_min ? strtoull(e_min, nullptr, 10) : kEarlyL2Min;
 	if (h->pending_kmers < h->l2_seen_kmers + std::max<uint64_t>(min_kmers, 1)) return DBGK_OK;
@@ -147,7 +147,7 @@ static int early_l2(dbgk_handle *h)
 	TimedSpan sp;
 	int rc = span_begin(h, PH_PARTITION, sp);
 	if (rc) return rc;
-	hipLaunchKernelGGL(k_plan_l2, dim3(1), dim3(kMaxBuckets), 0, h->stream, h->geom, h->store, h->tile_prefix);
+	hipLaunchKernelGGL(k_plan_l2, dim3(1), dim3(kMaxBuckets), 0, h->stream, h->geom, h->store, h->pbuf.tile_prefix);
 	launch_l2<0>(h, l2_grid, 0, G.nb_own);
 	HIPCHK(hipGetLastError());
 	h->l2_seen_kmers = h->pending_kmers;
@@ -157,11 +157,8 @@ static int early_l2(dbgk_handle *h)
 static int part_plan(dbgk_handle *h)
 {
 	if (h->part_planned) return DBGK_OK;
-	if (!h->stream2) {
-		HIPCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-		HIPCHK(hipEventCreateWithFlags(&h->join_ev, hipEventDisableTiming));
-	}
-	hipLaunchKernelGGL(k_plan_l2, dim3(1), dim3(kMaxBuckets), 0, h->stream, h->geom, h->store, h->tile_prefix);
+	if (h->stream2.create() || h->join_ev.create(hipEventDisableTiming)) return DBGK_ERR_HIP;
+	hipLaunchKernelGGL(k_plan_l2, dim3(1), dim3(kMaxBuckets), 0, h->stream, h->geom, h->store, h->pbuf.tile_prefix);
 	HIPCHK(hipGetLastError());
 	h->cursors_used = 0; // (the work cursors were zeroed with the record stores' control arrays: clear_record_store)
 	int rc = span_begin(h, PH_L2_BUILD_WALL, h->wall_span);
@@ -199,9 +196,9 @@ static int part_build_range(dbgk_handle *h, uint32_t j0, uint32_t j1, bool two_s
 	if (dbg_l2) return DBGK_OK; // never build regions from the garbage a timing experiment leaves behind
 	if (two_streams) {
 		if (h->chunk_ev.size() <= h->chunks_used) {
-			hipEvent_t e;
-			HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-			h->chunk_ev.push_back(e);
+			StageEvent e;
+			if (e.create(hipEventDisableTiming)) return DBGK_ERR_HIP;
+			h->chunk_ev.push_back(std::move(e));
 		}
 		hipEvent_t ev = h->chunk_ev[h->chunks_used++];
 		HIPCHK(hipEventRecord(ev, h->stream));
@@ -215,7 +212,7 @@ static int part_build_range(dbgk_handle *h, uint32_t j0, uint32_t j1, bool two_s
 		g_last_error = "too many build ranges in one step";
 		return DBGK_ERR_STATE;
 	}
-	unsigned int *cursor = h->region_cursor + h->cursors_used++;
+	unsigned int *cursor = h->pbuf.region_cursor + h->cursors_used++;
 	switch (dbg_build) {
 #ifdef DBGK_EXPERIMENTS
 		case 1: launch_build<1>(h, bstream, r0, r1 - r0, cursor); break;
@@ -273,11 +270,11 @@ static int build_from_records(dbgk_handle *h)
 	if (h->kfreq) {
 		Counters *track = h->kf_blocks ? h->d_ctr : nullptr; // direct blocks: the table summary is kept as the table is written
 		hipLaunchKernelGGL(k_kf_apply, dim3(h->n_cu), dim3(kBlock), 0, h->stream, h->store.spill, &h->store.ovf_n[1], h->store.spill_cap, 0,
-		                   reinterpret_cast<uint32_t *>(h->counts), track);
+		                   reinterpret_cast<uint32_t *>(h->counts.p), track);
 		hipLaunchKernelGGL(k_kf_apply, dim3(h->n_cu), dim3(kBlock), 0, h->stream, h->store.ovf, &h->store.ovf_n[0], h->store.ovf_cap, 1,
-		                   reinterpret_cast<uint32_t *>(h->counts), track);
+		                   reinterpret_cast<uint32_t *>(h->counts.p), track);
 		hipLaunchKernelGGL(k_kf_apply_table, dim3(grid_for(h, h->store.hh_size)), dim3(kBlock), 0, h->stream, h->store.hh, h->store.hh_size,
-		                   reinterpret_cast<uint32_t *>(h->counts), track);
+		                   reinterpret_cast<uint32_t *>(h->counts.p), track);
 		hipLaunchKernelGGL(k_kf_key0, dim3(1), dim3(64), 0, h->stream, h->d_ctr, h->counts, h->kf_blocks ? 1 : 0);
 	} else if (!h->sharded) {
 		hipLaunchKernelGGL(k_merge_spill, dim3(h->n_cu), dim3(kBlock), 0, h->stream, h->store.spill, &h->store.ovf_n[1], h->store.spill_cap,

@@ -61,11 +61,13 @@ extern "C" int dbgk_create(const dbgk_config *cfg, dbgk_handle **out)
 	h->magic = make_mod_magic(h->size);
 	h->tslots = h->size;
 	if ((!kfreq || kf_part) && !wide) {
-		const int prc = plan_partition(h); // geometry first: a sharded handle holds only its slot range
+		PartPlan plan;
+		const int prc = plan_partition(h->cfg, h->size, kfreq, h->kf_blocks, plan); // geometry first: a sharded handle holds only its slot range
 		if (prc != DBGK_OK) {
 			delete h;
 			return prc;
 		}
+		apply_plan(h, plan);
 		if (kfreq) {
 			if (!h->part) { // infeasible geometry: fall back to the direct table
 				h->size = 3;
@@ -78,25 +80,19 @@ extern "C" int dbgk_create(const dbgk_config *cfg, dbgk_handle **out)
 	}
 
 	auto fail = [&](int rc) {
-		free_handle(h);
+		close_handle(h);
 		return rc;
 	};
-	if (hipSetDevice(h->device) != hipSuccess) return fail(DBGK_ERR_HIP);
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, h->device) != hipSuccess) return fail(DBGK_ERR_HIP);
-	if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-		g_last_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-		return fail(DBGK_ERR_HIP);
+	{
+		const int orc = stage_open(*h, cfg->device_id); // the device current and a gfx950, its CU count, the first stream
+		if (orc != DBGK_OK) return fail(orc);
 	}
-	h->n_cu = prop.multiProcessorCount;
 	h->grid = h->n_cu * 8; // 8 x 256-thread blocks per CU = 32 waves/CU, the residency limit
-
-	if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(DBGK_ERR_HIP);
 	lap(1);
 	if (kfreq) {
 		h->n_counts = 1ull << (2 * cfg->kmer_size);
 		if (h->n_counts < 64) h->n_counts = 64; // whole dwords / 8-byte groups for the scan kernels (k < 3)
-		if (hipMalloc(&h->counts, h->n_counts) != hipSuccess) {
+		if (h->counts.reserve(h->n_counts)) {
 			g_last_error = "hipMalloc of the 4^k count table failed";
 			return fail(DBGK_ERR_NOMEM);
 		}
@@ -104,7 +100,7 @@ extern "C" int dbgk_create(const dbgk_config *cfg, dbgk_handle **out)
 		bool werr = false;
 		h->wpart = plan_wide_partition(h, &werr); // input size known: records first, the table region by region (a shard: its slot range only)
 		if (werr) return fail(DBGK_ERR_ARG);
-		if (hipMalloc(&h->wnodes, h->tslots * sizeof(WNode)) != hipSuccess || hipMalloc(&h->wside, kWideSideSlots * sizeof(WNode)) != hipSuccess) {
+		if (h->wnodes.reserve(h->tslots * sizeof(WNode)) || h->wside.reserve(kWideSideSlots * sizeof(WNode))) {
 			g_last_error = "hipMalloc of the wide k-mer table failed";
 			return fail(DBGK_ERR_NOMEM);
 		}
@@ -112,7 +108,7 @@ extern "C" int dbgk_create(const dbgk_config *cfg, dbgk_handle **out)
 			const int wrc = setup_wide_partition(h);
 			if (wrc != DBGK_OK) return fail(wrc);
 		}
-	} else if (hipMalloc(&h->table, h->tslots * sizeof(Node)) != hipSuccess) {
+	} else if (h->table.reserve(h->tslots * sizeof(Node))) {
 		g_last_error = "hipMalloc of the k-mer table failed";
 		return fail(DBGK_ERR_NOMEM);
 	}
@@ -121,11 +117,10 @@ extern "C" int dbgk_create(const dbgk_config *cfg, dbgk_handle **out)
 			g_last_error = "DBGK_FLAG_TRACK_FIRST_SEEN needs the DIRECT engine";
 			return fail(DBGK_ERR_ARG);
 		}
-		if (hipMalloc(&h->first_pos, h->tslots * 8) != hipSuccess) return fail(DBGK_ERR_NOMEM);
+		if (h->first_pos.reserve(h->tslots * 8)) return fail(DBGK_ERR_NOMEM);
 		h->track = true;
 	}
-	if (hipMalloc(&h->d_ctr, sizeof(Counters)) != hipSuccess) return fail(DBGK_ERR_NOMEM);
-	if (hipHostMalloc(&h->h_ctr, sizeof(Counters), hipHostMallocDefault) != hipSuccess) return fail(DBGK_ERR_NOMEM);
+	if (h->d_ctr.reserve(sizeof(Counters)) || h->h_ctr.alloc(sizeof(Counters))) return fail(DBGK_ERR_NOMEM);
 	h->cap_bases = cfg->max_batch_bases ? cfg->max_batch_bases : (256ull << 20);
 	h->cap_reads = h->cap_bases / 16 + 1024;
 	lap(2);
@@ -157,7 +152,7 @@ extern "C" int dbgk_create(const dbgk_config *cfg, dbgk_handle **out)
 extern "C" int dbgk_destroy(dbgk_handle *h)
 {
 	if (!h) return DBGK_ERR_ARG;
-	free_handle(h);
+	close_handle(h);
 	return DBGK_OK;
 }
 
@@ -186,7 +181,6 @@ extern "C" int dbgk_sync(dbgk_handle *h)
 extern "C" void *dbgk_stream(dbgk_handle *h) { return h ? (void *)h->stream : nullptr; }
 
 static int build_from_records(dbgk_handle *h);
-static int plan_partition(dbgk_handle *h);
 static int setup_partition(dbgk_handle *h);
 
 // PARTITION engine, streaming use: records -> table now (regions that already hold nodes are loaded back
@@ -216,34 +210,24 @@ static int resize_partition_table(dbgk_handle *h, uint64_t new_slots)
 	}
 	int rc = flush_records(h);
 	if (rc) return rc;
-	dbgk_handle probe_cfg;           // feasibility first: nothing is touched if the new size does not fit the engine
-	probe_cfg.cfg = h->cfg;
-	probe_cfg.size = new_slots;
-	probe_cfg.magic = make_mod_magic(new_slots);
-	rc = plan_partition(&probe_cfg);
+	PartPlan plan;                   // feasibility first: nothing is touched if the new size does not fit the engine
+	rc = plan_partition(h->cfg, new_slots, h->kfreq, h->kf_blocks, plan);
 	if (rc) return rc;
-	if (!probe_cfg.part) {
+	if (!plan.part) {
 		g_last_error = "dbgk_resize_table: the new size does not fit the PARTITION engine's geometry";
 		return DBGK_ERR_ARG;
 	}
-	Node *fresh = nullptr;
-	if (hipMalloc(&fresh, new_slots * sizeof(Node)) != hipSuccess) return DBGK_ERR_NOMEM;
+	DevBuf<Node> fresh;
+	if (fresh.reserve(new_slots * sizeof(Node))) return DBGK_ERR_NOMEM;
 	const TableRef dst{fresh, new_slots, make_mod_magic(new_slots)};
 	if (h->incr) { // the old table holds nodes
-		hipError_t e = hipMemsetAsync(fresh, 0, new_slots * sizeof(Node), h->stream);
-		if (e == hipSuccess) {
-			hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, h->size)), dim3(kBlock), 0, h->stream, h->table, h->size, dst, h->d_ctr,
-			                   (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
-			e = hipGetLastError();
-		}
-		if (e == hipSuccess) e = hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, h->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-		if (e != hipSuccess) {
-			(void)hipFree(fresh);
-			return hip_fail(e, "resize_table(partition)", __LINE__);
-		}
+		HIPCHK(hipMemsetAsync(fresh, 0, new_slots * sizeof(Node), h->stream));
+		hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, h->size)), dim3(kBlock), 0, h->stream, h->table, h->size, dst, h->d_ctr,
+		                   (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
 		if (h->h_ctr->error & 1u) {
-			(void)hipFree(fresh);
 			HIPCHK(hipMemsetAsync(&h->d_ctr->error, 0, sizeof(unsigned int), h->stream));
 			HIPCHK(hipStreamSynchronize(h->stream));
 			return DBGK_ERR_TABLE_FULL;
@@ -251,15 +235,13 @@ static int resize_partition_table(dbgk_handle *h, uint64_t new_slots)
 	}
 	HIPCHK(hipStreamSynchronize(h->stream));
 	if (h->stream2) HIPCHK(hipStreamSynchronize(h->stream2));
-	(void)hipFree(h->table);
-	h->table = fresh;
+	h->table.take(fresh);
 	h->size = new_slots;
 	h->magic = dst.magic;
 	h->cfg.table_slots = new_slots;
-	free_partition_stores(h);
-	rc = plan_partition(h);
-	if (rc == DBGK_OK && !h->part) rc = DBGK_ERR_STATE;
-	if (rc == DBGK_OK) rc = setup_partition(h);
+	h->pbuf = PartBufs(); // the geometry changes: the record stores are made again
+	apply_plan(h, plan);
+	rc = setup_partition(h);
 	if (rc) return rc;
 	h->zero_pending = !h->incr; // nothing built yet: the first region build writes every slot
 	return clear_record_store(h);
@@ -276,47 +258,27 @@ extern "C" int dbgk_resize_table(dbgk_handle *h, uint64_t new_slots)
 	if (rc) return rc;
 	if (new_slots == h->size) return DBGK_OK;
 	if (h->part) return resize_partition_table(h, new_slots);
-	Node *fresh = nullptr;
-	unsigned long long *fresh_first = nullptr;
-	if (hipMalloc(&fresh, new_slots * sizeof(Node)) != hipSuccess) return DBGK_ERR_NOMEM;
+	DevBuf<Node> fresh;
+	DevBuf<unsigned long long> fresh_first;
+	if (fresh.reserve(new_slots * sizeof(Node))) return DBGK_ERR_NOMEM;
 	if (h->track) {
-		if (hipMalloc(&fresh_first, new_slots * 8) != hipSuccess) {
-			(void)hipFree(fresh);
-			return DBGK_ERR_NOMEM;
-		}
-		if (hipMemsetAsync(fresh_first, 0xFF, new_slots * 8, h->stream) != hipSuccess) {
-			(void)hipFree(fresh);
-			(void)hipFree(fresh_first);
-			return DBGK_ERR_HIP;
-		}
+		if (fresh_first.reserve(new_slots * 8)) return DBGK_ERR_NOMEM;
+		if (hipMemsetAsync(fresh_first, 0xFF, new_slots * 8, h->stream) != hipSuccess) return DBGK_ERR_HIP;
 	}
 	TableRef dst{fresh, new_slots, make_mod_magic(new_slots)};
-	hipError_t e = hipMemsetAsync(fresh, 0, new_slots * sizeof(Node), h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, h->size)), dim3(kBlock), 0, h->stream, h->table, h->size, dst, h->d_ctr,
-		                   (const unsigned long long *)h->first_pos, fresh_first);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e != hipSuccess) {
-		(void)hipFree(fresh);
-		if (fresh_first) (void)hipFree(fresh_first);
-		return hip_fail(e, "resize_table", __LINE__);
-	}
+	HIPCHK(hipMemsetAsync(fresh, 0, new_slots * sizeof(Node), h->stream));
+	hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, h->size)), dim3(kBlock), 0, h->stream, h->table, h->size, dst, h->d_ctr,
+	                   (const unsigned long long *)h->first_pos, fresh_first);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	if (h->h_ctr->error & 1u) { // new table too small for the existing nodes: keep the old one
-		(void)hipFree(fresh);
-		if (fresh_first) (void)hipFree(fresh_first);
 		HIPCHK(hipMemsetAsync(&h->d_ctr->error, 0, sizeof(unsigned int), h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
 		return DBGK_ERR_TABLE_FULL;
 	}
-	(void)hipFree(h->table);
-	if (h->track) {
-		(void)hipFree(h->first_pos);
-		h->first_pos = fresh_first;
-	}
-	h->table = fresh;
+	h->table.take(fresh);
+	if (h->track) h->first_pos.take(fresh_first);
 	h->size = new_slots;
 	h->tslots = new_slots;
 	h->magic = dst.magic;

@@ -22,31 +22,19 @@ extern "C" int dbgk_seed_export_sorted(dbgk_handle *h, dbgk_node *out, uint64_t 
 		out[0].r_link = (uint32_t)(w >> 32);
 	}
 	if (n == 0) return DBGK_OK;
-	uint64_t *d_keys = nullptr, *d_links = nullptr;
-	unsigned long long *d_cursor = nullptr;
-	auto cleanup = [&]() {
-		for (void *p : {(void *)d_keys, (void *)d_links, (void *)d_cursor})
-			if (p) (void)hipFree(p);
-	};
-	if (hipMalloc(&d_keys, n * 8) != hipSuccess || hipMalloc(&d_links, n * 8) != hipSuccess || hipMalloc(&d_cursor, 8) != hipSuccess) {
-		cleanup();
-		return DBGK_ERR_NOMEM;
-	}
-	hipError_t e = hipMemsetAsync(d_cursor, 0, 8, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_compact, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, d_keys, d_links, d_cursor, n);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e != hipSuccess) { cleanup(); return hip_fail(e, "seed_export_sorted/compact", __LINE__); }
+	DevBuf<uint64_t> d_keys, d_links;
+	DevBuf<unsigned long long> d_cursor;
+	if (d_keys.reserve(n * 8) || d_links.reserve(n * 8) || d_cursor.reserve(8)) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemsetAsync(d_cursor, 0, 8, h->stream));
+	hipLaunchKernelGGL(k_compact, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, d_keys, d_links, d_cursor, n);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream));
 	rc = dbgk_internal_sort_pairs(d_keys, d_links, n, h->stream);
-	if (rc != DBGK_OK) { cleanup(); return rc; }
+	if (rc != DBGK_OK) return rc;
 	std::vector<uint64_t> hk(n), hl(n);
-	e = hipMemcpyAsync(hk.data(), d_keys, n * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(hl.data(), d_links, n * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	cleanup();
-	if (e != hipSuccess) return hip_fail(e, "seed_export_sorted/copy", __LINE__);
+	HIPCHK(hipMemcpyAsync(hk.data(), d_keys, n * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(hl.data(), d_links, n * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	for (uint64_t i = 0; i < n; i++) {
 		const uint64_t w = seed_payload_out(hl[i]);
 		out[i + z].kmer = hk[i];
@@ -63,31 +51,22 @@ extern "C" int dbgk_seed_export_host_table(dbgk_handle *h, uint64_t host_size, d
 	int rc = use_device(h);
 	if (rc) return rc;
 	if (h->h_ctr->n_new + 1 > host_size) return DBGK_ERR_TABLE_FULL;
-	Node *tmp = nullptr;
-	uint8_t *d_flags = nullptr;
-	if (hipMalloc(&tmp, host_size * sizeof(Node)) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&d_flags, host_size / 8 + 1) != hipSuccess) {
-		(void)hipFree(tmp);
-		return DBGK_ERR_NOMEM;
-	}
+	DevBuf<Node> tmp;
+	DevBuf<uint8_t> d_flags;
+	if (tmp.reserve(host_size * sizeof(Node)) || d_flags.reserve(host_size / 8 + 1)) return DBGK_ERR_NOMEM;
 	TableRef T{tmp, host_size, make_mod_magic(host_size)};
-	hipError_t e = hipMemsetAsync(tmp, 0, host_size * sizeof(Node), h->stream);
-	if (e == hipSuccess) {
-		// always through a copy: the payload words are converted in place to the reference's bit-field
-		hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, T, h->d_ctr,
-		                   (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
-		hipLaunchKernelGGL(k_seed_convert, dim3(grid_for(h, host_size)), dim3(kBlock), 0, h->stream, tmp, host_size);
-		hipLaunchKernelGGL(k_seed_place_key0, dim3(1), dim3(64), 0, h->stream, T, h->d_ctr);
-		hipLaunchKernelGGL(k_build_flags_ctr, dim3(grid_for(h, host_size / 8 + 1)), dim3(kBlock), 0, h->stream, tmp, host_size, h->d_ctr, d_flags);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(array, tmp, host_size * sizeof(Node), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(nul_flag, d_flags, host_size / 8 + 1, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(tmp);
-	(void)hipFree(d_flags);
-	if (e != hipSuccess) return hip_fail(e, "seed_export_host_table", __LINE__);
+	HIPCHK(hipMemsetAsync(tmp, 0, host_size * sizeof(Node), h->stream));
+	// always through a copy: the payload words are converted in place to the reference's bit-field
+	hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, T, h->d_ctr,
+	                   (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
+	hipLaunchKernelGGL(k_seed_convert, dim3(grid_for(h, host_size)), dim3(kBlock), 0, h->stream, tmp, host_size);
+	hipLaunchKernelGGL(k_seed_place_key0, dim3(1), dim3(64), 0, h->stream, T, h->d_ctr);
+	hipLaunchKernelGGL(k_build_flags_ctr, dim3(grid_for(h, host_size / 8 + 1)), dim3(kBlock), 0, h->stream, tmp, host_size, h->d_ctr, d_flags);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(array, tmp, host_size * sizeof(Node), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(nul_flag, d_flags, host_size / 8 + 1, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return (h->h_ctr->error & 1u) ? DBGK_ERR_TABLE_FULL : DBGK_OK;
 }
 
@@ -107,25 +86,16 @@ extern "C" int dbgk_wide_export_sorted(dbgk_handle *h, dbgk_node32 *out, uint64_
 	if (z) out[0] = dbgk_node32{0, 0, (uint32_t)(h->h_ctr->polyA_links & 0xFFFFFFFFu), (uint32_t)(h->h_ctr->polyA_links >> 32), 0}; // key 0 sorts first
 	dbgk_node32 *dst = out + z; // the non-zero keys follow the key-0 node (if this shard reports one)
 	if (n == 0) return DBGK_OK;
-	dbgk_node32 *d_out = nullptr;
-	unsigned long long *d_cursor = nullptr;
-	if (hipMalloc(&d_out, n * sizeof(dbgk_node32)) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&d_cursor, 8) != hipSuccess) {
-		(void)hipFree(d_out);
-		return DBGK_ERR_NOMEM;
-	}
+	DevBuf<dbgk_node32> d_out;
+	DevBuf<unsigned long long> d_cursor;
+	if (d_out.reserve(n * sizeof(dbgk_node32)) || d_cursor.reserve(8)) return DBGK_ERR_NOMEM;
 	unsigned long long found = 0;
-	hipError_t e = hipMemsetAsync(d_cursor, 0, 8, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_wide_compact, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, d_out, d_cursor, n);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(&found, d_cursor, 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(dst, d_out, n * sizeof(dbgk_node32), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_out);
-	(void)hipFree(d_cursor);
-	if (e != hipSuccess) return hip_fail(e, "wide_export_sorted", __LINE__);
+	HIPCHK(hipMemsetAsync(d_cursor, 0, 8, h->stream));
+	hipLaunchKernelGGL(k_wide_compact, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, d_out, d_cursor, n);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(&found, d_cursor, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(dst, d_out, n * sizeof(dbgk_node32), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	if (found != n) {
 		g_last_error = "wide_export_sorted: occupied slots != counted keys";
 		return DBGK_ERR_STATE;
@@ -167,23 +137,16 @@ static int wide_export_host_table_impl(dbgk_handle *h, uint64_t host_size, dbgk_
 	if (!h->sharded && h->h_ctr->n_new + 1 > host_size) return DBGK_ERR_TABLE_FULL;
 	int rc = use_device(h);
 	if (rc) return rc;
-	dbgk_node32 *d_img = nullptr;
-	uint8_t *d_flags = nullptr;
+	DevBuf<dbgk_node32> d_img;
+	DevBuf<uint8_t> d_flags;
 	std::vector<WNode> side(kWideSideSlots);
-	if (hipMalloc(&d_img, host_size * sizeof(dbgk_node32)) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&d_flags, host_size / 8 + 1) != hipSuccess) {
-		(void)hipFree(d_img);
-		return DBGK_ERR_NOMEM;
-	}
+	if (d_img.reserve(host_size * sizeof(dbgk_node32)) || d_flags.reserve(host_size / 8 + 1)) return DBGK_ERR_NOMEM;
 	hipLaunchKernelGGL(k_wide_image, dim3(grid_for(h, host_size / 8 + 1)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, d_img, d_flags);
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpyAsync(array, d_img, host_size * sizeof(dbgk_node32), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(nul_flag, d_flags, host_size / 8 + 1, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(side.data(), h->wside, kWideSideSlots * sizeof(WNode), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_img);
-	(void)hipFree(d_flags);
-	if (e != hipSuccess) return hip_fail(e, "wide_export_host_table", __LINE__);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(array, d_img, host_size * sizeof(dbgk_node32), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(nul_flag, d_flags, host_size / 8 + 1, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(side.data(), h->wside, kWideSideSlots * sizeof(WNode), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	if (h->sharded) return DBGK_OK; // a shard's slice as it is: side-table nodes and the key-0 node are placed over the WHOLE table by the caller
 	wide_place_outside_nodes(side, (uint32_t)(h->h_ctr->polyA_links & 0xFFFFFFFFu), (uint32_t)(h->h_ctr->polyA_links >> 32), host_size, array, nul_flag, placed);
 	return DBGK_OK;
@@ -202,21 +165,15 @@ extern "C" int dbgk_wide_partition_export(dbgk_handle *h, uint32_t n_parts, dbgk
 	if (!h->wide || !h->finalized) return DBGK_ERR_STATE;
 	int rc = use_device(h);
 	if (rc) return rc;
-	unsigned long long *d_counts = nullptr;
-	if (hipMalloc(&d_counts, n_parts * 8) != hipSuccess) return DBGK_ERR_NOMEM;
+	DevBuf<unsigned long long> d_counts;
+	if (d_counts.reserve(n_parts * 8)) return DBGK_ERR_NOMEM;
 	std::vector<unsigned long long> hc(n_parts, 0);
-	hipError_t e = hipMemsetAsync(d_counts, 0, n_parts * 8, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_wide_partition, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, n_parts, d_counts,
-		                   (unsigned long long *)nullptr, (dbgk_node32 *)nullptr, (uint64_t)0);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(hc.data(), d_counts, n_parts * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e != hipSuccess) {
-		(void)hipFree(d_counts);
-		return hip_fail(e, "wide_partition_export/count", __LINE__);
-	}
+	HIPCHK(hipMemsetAsync(d_counts, 0, n_parts * 8, h->stream));
+	hipLaunchKernelGGL(k_wide_partition, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, n_parts, d_counts,
+	                   (unsigned long long *)nullptr, (dbgk_node32 *)nullptr, (uint64_t)0);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(hc.data(), d_counts, n_parts * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	hc[0] += 1; // the key-0 node travels with part 0
 	uint64_t total = 0;
 	std::vector<unsigned long long> cursors(n_parts);
@@ -225,25 +182,15 @@ extern "C" int dbgk_wide_partition_export(dbgk_handle *h, uint32_t n_parts, dbgk
 		cursors[p] = total + (p == 0 ? 1 : 0);
 		total += hc[p];
 	}
-	if (!d_nodes) { // counts only
-		(void)hipFree(d_counts);
-		return DBGK_OK;
-	}
-	if (total > capacity) {
-		(void)hipFree(d_counts);
-		return DBGK_ERR_CAPACITY;
-	}
+	if (!d_nodes) return DBGK_OK; // counts only
+	if (total > capacity) return DBGK_ERR_CAPACITY;
 	const dbgk_node32 zero = {0, 0, (uint32_t)(h->h_ctr->polyA_links & 0xFFFFFFFFu), (uint32_t)(h->h_ctr->polyA_links >> 32), 0};
-	e = hipMemcpyAsync(d_counts, cursors.data(), n_parts * 8, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_nodes, &zero, sizeof zero, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_wide_partition, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, n_parts,
-		                   (unsigned long long *)nullptr, d_counts, d_nodes, capacity);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_counts);
-	if (e != hipSuccess) return hip_fail(e, "wide_partition_export", __LINE__);
+	HIPCHK(hipMemcpyAsync(d_counts, cursors.data(), n_parts * 8, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(d_nodes, &zero, sizeof zero, hipMemcpyHostToDevice, h->stream));
+	hipLaunchKernelGGL(k_wide_partition, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, n_parts,
+	                   (unsigned long long *)nullptr, d_counts, d_nodes, capacity);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return DBGK_OK;
 }
 
@@ -294,14 +241,12 @@ extern "C" int dbgk_kfreq_export_bits(dbgk_handle *h, uint32_t cutoff, uint64_t 
 	int rc = use_device(h);
 	if (rc) return rc;
 	if (n_bytes == 0) return DBGK_OK;
-	uint8_t *d_bits = nullptr;
-	if (hipMalloc(&d_bits, n_bytes) != hipSuccess) return DBGK_ERR_NOMEM;
+	DevBuf<uint8_t> d_bits;
+	if (d_bits.reserve(n_bytes)) return DBGK_ERR_NOMEM;
 	hipLaunchKernelGGL(k_counts_to_bits, dim3(grid_for(h, n_bytes)), dim3(kBlock), 0, h->stream, h->counts, first_byte, n_bytes, cutoff, d_bits);
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpyAsync(host_out, d_bits, n_bytes, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_bits);
-	if (e != hipSuccess) return hip_fail(e, "kfreq_export_bits", __LINE__);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(host_out, d_bits, n_bytes, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return DBGK_OK;
 }
 
@@ -309,18 +254,16 @@ extern "C" int dbgk_kfreq_export_bits(dbgk_handle *h, uint32_t cutoff, uint64_t 
 // (saturating).  The distinct-k-mer count of the handle is recomputed.
 static int kfreq_summary(dbgk_handle *h, uint64_t first, uint64_t n, unsigned long long res[2])
 {
-	unsigned long long *d_sum = nullptr;
+	DevBuf<unsigned long long> d_sum;
 	res[0] = res[1] = 0;
-	if (hipMalloc(&d_sum, 16) != hipSuccess) return DBGK_ERR_NOMEM;
-	hipError_t e = hipMemsetAsync(d_sum, 0, 16, h->stream);
-	if (e == hipSuccess && n) {
+	if (d_sum.reserve(16)) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemsetAsync(d_sum, 0, 16, h->stream));
+	if (n) {
 		hipLaunchKernelGGL(k_counts_summary, dim3(grid_for(h, n >> 3)), dim3(kBlock), 0, h->stream, h->counts + first, n, d_sum);
-		e = hipGetLastError();
+		HIPCHK(hipGetLastError());
 	}
-	if (e == hipSuccess) e = hipMemcpyAsync(res, d_sum, 16, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_sum);
-	if (e != hipSuccess) return hip_fail(e, "kfreq summary", __LINE__);
+	HIPCHK(hipMemcpyAsync(res, d_sum, 16, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return DBGK_OK;
 }
 
@@ -370,46 +313,30 @@ extern "C" int dbgk_extract_kmers(dbgk_handle *h, const char *bases, const uint6
 	const uint64_t nb = offsets[n_reads];
 	if (nb == 0) return DBGK_OK;
 	const uint64_t words = bitmap_words(nb);
-	char *d_bases = nullptr;
-	uint64_t *d_off = nullptr, *d_kmer = nullptr;
-	uint32_t *d_start = nullptr, *d_dead = nullptr;
-	uint8_t *d_l = nullptr, *d_r = nullptr, *d_v = nullptr;
-	Counters *d_ctr = nullptr;
-	auto cleanup = [&]() {
-		for (void *p : {(void *)d_bases, (void *)d_off, (void *)d_kmer, (void *)d_start, (void *)d_dead, (void *)d_l, (void *)d_r,
-		                (void *)d_v, (void *)d_ctr})
-			if (p) (void)hipFree(p);
-	};
-	hipError_t e = hipMalloc(&d_bases, nb + 64);
-	if (e == hipSuccess) e = hipMalloc(&d_off, (n_reads + 1) * 8);
-	if (e == hipSuccess) e = hipMalloc(&d_kmer, nb * 8);
-	if (e == hipSuccess) e = hipMalloc(&d_start, words * 4);
-	if (e == hipSuccess) e = hipMalloc(&d_dead, words * 4);
-	if (e == hipSuccess) e = hipMalloc(&d_l, nb);
-	if (e == hipSuccess) e = hipMalloc(&d_r, nb);
-	if (e == hipSuccess) e = hipMalloc(&d_v, nb);
-	if (e == hipSuccess) e = hipMalloc(&d_ctr, sizeof(Counters));
-	if (e != hipSuccess) { cleanup(); return DBGK_ERR_NOMEM; }
-	e = hipMemcpyAsync(d_bases, bases, nb, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(d_start, 0, words * 4, h->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(d_dead, 0, words * 4, h->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(d_ctr, 0, sizeof(Counters), h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_mark, dim3(grid_for(h, n_reads)), dim3(kBlock), 0, h->stream, d_off, n_reads, nb, h->cfg.kmer_size,
-		                   h->cfg.max_read_len, d_start, d_dead, d_ctr);
-		ReadBatch rb{d_bases, nb, d_start, d_dead, h->cfg.kmer_size, nullptr, &d_ctr->other_seen};
-		hipLaunchKernelGGL(k_extract_store<true>, dim3(grid_for(h, (nb + 15) >> 4)), dim3(kBlock), 0, h->stream, rb, d_kmer, d_l,
-		                   d_r, d_v);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(kmer, d_kmer, nb * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(left, d_l, nb, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(right, d_r, nb, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(valid, d_v, nb, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	cleanup();
-	if (e != hipSuccess) return hip_fail(e, "extract_kmers", __LINE__);
+	DevBuf<char> d_bases;
+	DevBuf<uint64_t> d_off, d_kmer;
+	DevBuf<uint32_t> d_start, d_dead;
+	DevBuf<uint8_t> d_l, d_r, d_v;
+	DevBuf<Counters> d_ctr;
+	if (d_bases.reserve(nb + 64) || d_off.reserve((n_reads + 1) * 8) || d_kmer.reserve(nb * 8) || d_start.reserve(words * 4) || d_dead.reserve(words * 4) ||
+	    d_l.reserve(nb) || d_r.reserve(nb) || d_v.reserve(nb) || d_ctr.reserve(sizeof(Counters)))
+		return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemcpyAsync(d_bases, bases, nb, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(d_off, offsets, (n_reads + 1) * 8, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemsetAsync(d_start, 0, words * 4, h->stream));
+	HIPCHK(hipMemsetAsync(d_dead, 0, words * 4, h->stream));
+	HIPCHK(hipMemsetAsync(d_ctr, 0, sizeof(Counters), h->stream));
+	hipLaunchKernelGGL(k_mark, dim3(grid_for(h, n_reads)), dim3(kBlock), 0, h->stream, d_off, n_reads, nb, h->cfg.kmer_size,
+	                   h->cfg.max_read_len, d_start, d_dead, d_ctr);
+	ReadBatch rb{d_bases, nb, d_start, d_dead, h->cfg.kmer_size, nullptr, &d_ctr->other_seen};
+	hipLaunchKernelGGL(k_extract_store<true>, dim3(grid_for(h, (nb + 15) >> 4)), dim3(kBlock), 0, h->stream, rb, d_kmer, d_l,
+	                   d_r, d_v);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(kmer, d_kmer, nb * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(left, d_l, nb, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(right, d_r, nb, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(valid, d_v, nb, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return DBGK_OK;
 }
 
@@ -425,18 +352,14 @@ extern "C" int dbgk_partition_counts(dbgk_handle *h, uint32_t n_parts, uint64_t 
 	if (!h->finalized || h->sharded) return DBGK_ERR_STATE; // a sharded table is already owned by slot range
 	int rc = use_device(h);
 	if (rc) return rc;
-	unsigned long long *d_counts = nullptr;
-	if (hipMalloc(&d_counts, n_parts * 8) != hipSuccess) return DBGK_ERR_NOMEM;
-	hipError_t e = hipMemsetAsync(d_counts, 0, n_parts * 8, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_partition_count, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, n_parts,
-		                   d_counts);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, n_parts * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_counts);
-	if (e != hipSuccess) return hip_fail(e, "partition_counts", __LINE__);
+	DevBuf<unsigned long long> d_counts;
+	if (d_counts.reserve(n_parts * 8)) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemsetAsync(d_counts, 0, n_parts * 8, h->stream));
+	hipLaunchKernelGGL(k_partition_count, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, n_parts,
+	                   d_counts);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(counts, d_counts, n_parts * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	counts[0] += 1; // the key-0 node travels with part 0
 	return DBGK_OK;
 }
@@ -466,19 +389,15 @@ extern "C" int dbgk_partition_export(dbgk_handle *h, uint32_t n_parts, dbgk_node
 		total += counts[p];
 	}
 	if (total > capacity) return DBGK_ERR_CAPACITY;
-	unsigned long long *d_cursors = nullptr;
-	if (hipMalloc(&d_cursors, n_parts * 8) != hipSuccess) return DBGK_ERR_NOMEM;
-	hipError_t e = hipMemcpyAsync(d_cursors, cursors.data(), n_parts * 8, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_write_polyA_node, dim3(1), dim3(64), 0, h->stream, reinterpret_cast<Node *>(d_nodes), (uint64_t)0,
-		                   h->d_ctr);
-		hipLaunchKernelGGL(k_partition_scatter, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, n_parts,
-		                   d_cursors, reinterpret_cast<Node *>(d_nodes), capacity);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_cursors);
-	if (e != hipSuccess) return hip_fail(e, "partition_export", __LINE__);
+	DevBuf<unsigned long long> d_cursors;
+	if (d_cursors.reserve(n_parts * 8)) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemcpyAsync(d_cursors, cursors.data(), n_parts * 8, hipMemcpyHostToDevice, h->stream));
+	hipLaunchKernelGGL(k_write_polyA_node, dim3(1), dim3(64), 0, h->stream, reinterpret_cast<Node *>(d_nodes), (uint64_t)0,
+	                   h->d_ctr);
+	hipLaunchKernelGGL(k_partition_scatter, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, n_parts,
+	                   d_cursors, reinterpret_cast<Node *>(d_nodes), capacity);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return DBGK_OK;
 }
 
@@ -525,27 +444,25 @@ extern "C" int dbgk_copy_nodes_peer(dbgk_handle *dst, dbgk_node *d_dst, dbgk_han
 extern "C" int dbgk_plan_partition(uint64_t table_slots, uint64_t expected_kmers, uint32_t shard_count, uint32_t shard_index, dbgk_plan_info *out)
 {
 	if (!out || table_slots == 0) return DBGK_ERR_ARG;
-	dbgk_handle *h = new (std::nothrow) dbgk_handle();   // never touches a device: plan_partition is host arithmetic
-	if (!h) return DBGK_ERR_NOMEM;
-	memset(&h->cfg, 0, sizeof h->cfg);
-	h->cfg.kmer_size = 31;
-	h->cfg.engine = DBGK_ENGINE_PARTITION;
-	h->cfg.table_slots = table_slots;
-	h->cfg.expected_kmers = expected_kmers;
-	h->cfg.shard_count = shard_count;
-	h->cfg.shard_index = shard_index;
-	h->size = table_slots;
-	h->magic = make_mod_magic(table_slots);
-	int rc = plan_partition(h);
-	if (rc == DBGK_OK && !h->part) rc = DBGK_ERR_ARG;
+	dbgk_config cfg; // (no handle, no device: plan_partition is host arithmetic)
+	memset(&cfg, 0, sizeof cfg);
+	cfg.kmer_size = 31;
+	cfg.engine = DBGK_ENGINE_PARTITION;
+	cfg.table_slots = table_slots;
+	cfg.expected_kmers = expected_kmers;
+	cfg.shard_count = shard_count;
+	cfg.shard_index = shard_index;
+	PartPlan plan;
+	int rc = plan_partition(cfg, table_slots, false, false, plan);
+	if (rc == DBGK_OK && !plan.part) rc = DBGK_ERR_ARG;
 	if (rc == DBGK_OK) {
-		const PartGeom &G = h->geom;
+		const PartGeom &G = plan.geom;
 		memset(out, 0, sizeof *out);
 		out->table_slots = G.size;
 		out->r = G.r;
 		out->level1_buckets = G.n1;
 		out->final_per_level1 = G.n2;
-		out->three_level = h->three ? 1u : 0u;
+		out->three_level = plan.three ? 1u : 0u;
 		out->buckets_per_rank = G.B;
 		out->own_buckets = G.nb_own;
 		out->first_bucket = G.b_lo;
@@ -556,10 +473,9 @@ extern "C" int dbgk_plan_partition(uint64_t table_slots, uint64_t expected_kmers
 		const uint64_t n_entries = (uint64_t)G.n_ranks * G.B * G.n_sub;
 		out->table_bytes = (G.slot_hi - G.slot_lo) * sizeof(Node);
 		out->level1_store_bytes = n_entries * G.cap1 * 8;
-		out->inbox_bytes = h->sharded ? n_entries * G.cap1 * 8 : 0;
-		out->final_store_bytes = (uint64_t)G.nb_own * G.n2 * G.cap2 * 8 + (h->three ? (uint64_t)G.nb_own * h->fan_mid * h->g_mid.cap2 * 8 : 0);
+		out->inbox_bytes = plan.sharded ? n_entries * G.cap1 * 8 : 0;
+		out->final_store_bytes = (uint64_t)G.nb_own * G.n2 * G.cap2 * 8 + (plan.three ? (uint64_t)G.nb_own * plan.fan_mid * plan.g_mid.cap2 * 8 : 0);
 	}
-	delete h;
 	return rc;
 }
 
@@ -584,8 +500,8 @@ extern "C" int dbgk_shard_buffers(dbgk_handle *h, dbgk_shard_info *out)
 		out->cnt_chunk_bytes = (uint64_t)G.Bp * 4;
 		out->d_send = h->wstore.l1;
 		out->d_send_cnt = h->wstore.cnt1;
-		out->d_recv = h->sharded ? (void *)h->winbox : (void *)h->wstore.l1;
-		out->d_recv_cnt = h->sharded ? (void *)h->winbox_cnt : (void *)h->wstore.cnt1;
+		out->d_recv = h->sharded ? (void *)h->wbuf.inbox : (void *)h->wstore.l1;
+		out->d_recv_cnt = h->sharded ? (void *)h->wbuf.inbox_cnt : (void *)h->wstore.cnt1;
 		return DBGK_OK;
 	}
 	if (!h->part) return DBGK_ERR_STATE;
@@ -604,8 +520,8 @@ extern "C" int dbgk_shard_buffers(dbgk_handle *h, dbgk_shard_info *out)
 	out->cnt_chunk_bytes = (uint64_t)G.B * G.n_sub * 4;
 	out->d_send = h->store.l1;
 	out->d_send_cnt = h->store.cnt1;
-	out->d_recv = h->sharded ? (void *)h->inbox : (void *)h->store.l1;
-	out->d_recv_cnt = h->sharded ? (void *)h->inbox_cnt : (void *)h->store.cnt1;
+	out->d_recv = h->sharded ? (void *)h->pbuf.inbox : (void *)h->store.l1;
+	out->d_recv_cnt = h->sharded ? (void *)h->pbuf.inbox_cnt : (void *)h->store.cnt1;
 	return DBGK_OK;
 }
 
@@ -754,13 +670,13 @@ extern "C" int dbgk_shard_side_export(dbgk_handle *h, dbgk_node32 **d_nodes, uin
 	if (!h->wide || !h->wmulti || !h->finalized) return DBGK_ERR_STATE;
 	int rc = use_device(h);
 	if (rc) return rc;
-	HIPCHK(hipMemsetAsync(h->w_side_n, 0, 8, h->stream));
-	hipLaunchKernelGGL(k_wide_side_export, dim3(16), dim3(kBlock), 0, h->stream, h->wside, h->d_ctr, h->w_side_out, h->w_side_n, (uint64_t)kWideSideSlots + 1);
+	HIPCHK(hipMemsetAsync(h->wbuf.side_n, 0, 8, h->stream));
+	hipLaunchKernelGGL(k_wide_side_export, dim3(16), dim3(kBlock), 0, h->stream, h->wside, h->d_ctr, h->wbuf.side_out, h->wbuf.side_n, (uint64_t)kWideSideSlots + 1);
 	HIPCHK(hipGetLastError());
 	unsigned long long v = 0;
-	HIPCHK(hipMemcpyAsync(&v, h->w_side_n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(&v, h->wbuf.side_n, 8, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));
-	*d_nodes = h->w_side_out;
+	*d_nodes = h->wbuf.side_out;
 	*n = v + 1; // + the key-0 node in front
 	return DBGK_OK;
 }
@@ -772,11 +688,11 @@ extern "C" int dbgk_shard_side_clear(dbgk_handle *h)
 	int rc = use_device(h);
 	if (rc) return rc;
 	// the claims in the side table were counted as new keys of this handle: take them back with the table
-	HIPCHK(hipMemsetAsync(h->w_side_n, 0, 8, h->stream));
-	hipLaunchKernelGGL(k_wide_side_export, dim3(16), dim3(kBlock), 0, h->stream, h->wside, h->d_ctr, h->w_side_out, h->w_side_n, (uint64_t)kWideSideSlots + 1);
+	HIPCHK(hipMemsetAsync(h->wbuf.side_n, 0, 8, h->stream));
+	hipLaunchKernelGGL(k_wide_side_export, dim3(16), dim3(kBlock), 0, h->stream, h->wside, h->d_ctr, h->wbuf.side_out, h->wbuf.side_n, (uint64_t)kWideSideSlots + 1);
 	HIPCHK(hipGetLastError());
 	unsigned long long v = 0;
-	HIPCHK(hipMemcpyAsync(&v, h->w_side_n, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(&v, h->wbuf.side_n, 8, hipMemcpyDeviceToHost, h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));
 	Counters c;
 	HIPCHK(hipMemcpyAsync(&c, h->d_ctr, sizeof c, hipMemcpyDeviceToHost, h->stream));

@@ -121,12 +121,12 @@ static int d2h_pipelined(dbgk_handle *h, void *dst, const void *d_src, size_t by
 		return DBGK_OK;
 	}
 	while (h->d2h_stage.size() < (size_t)kBuffers) {
-		void *p = nullptr;
-		hipEvent_t e = nullptr;
-		if (hipHostMalloc(&p, kSlice, hipHostMallocDefault) != hipSuccess) return DBGK_ERR_NOMEM;
-		h->d2h_stage.push_back(p);
-		HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-		h->d2h_ev.push_back(e);
+		PinBuf<char> p;
+		StageEvent e;
+		if (p.alloc(kSlice)) return DBGK_ERR_NOMEM;
+		h->d2h_stage.push_back(std::move(p));
+		if (e.create(hipEventDisableTiming)) return DBGK_ERR_HIP;
+		h->d2h_ev.push_back(std::move(e));
 	}
 	const size_t n_slices = (bytes + kSlice - 1) / kSlice;
 	std::vector<std::atomic<int>> issued(n_slices), done(n_slices);
@@ -236,17 +236,11 @@ static int d2h_compact(dbgk_handle *h, dbgk_node *array, uint8_t *nul_flag, cons
 	double laps[5] = {0, 0, 0, 0, 0}, lap_t = clock_s();
 	auto lap = [&](int i) { const double t = clock_s(); laps[i] += t - lap_t; lap_t = t; };
 	std::atomic<uint64_t> wait_link_us{0}, wait_host_us{0};
-	Node *d_stream = nullptr;
-	uint32_t *d_counts = nullptr;
-	uint64_t *d_first = nullptr;
-	auto cleanup = [&]() {
-		for (void *p : {(void *)d_stream, (void *)d_counts, (void *)d_first})
-			if (p) (void)hipFree(p);
-	};
-	if (hipMalloc(&d_stream, (n_occ + 1) * sizeof(Node)) != hipSuccess || hipMalloc(&d_counts, n_spans * 4) != hipSuccess ||
-	    hipMalloc(&d_first, n_spans * 8) != hipSuccess) {
+	DevBuf<Node> d_stream;
+	DevBuf<uint32_t> d_counts;
+	DevBuf<uint64_t> d_first;
+	if (d_stream.reserve((n_occ + 1) * sizeof(Node)) || d_counts.reserve(n_spans * 4) || d_first.reserve(n_spans * 8)) {
 		(void)hipGetLastError();
-		cleanup();
 		return DBGK_ERR_STATE;
 	}
 	// page-locked pieces: [the occupancy bits] + the slices the stream passes through
@@ -258,24 +252,24 @@ static int d2h_compact(dbgk_handle *h, dbgk_node *array, uint8_t *nul_flag, cons
 		if (sl.busy && hipEventQuery(sl.done) != hipSuccess) continue; // (a batch still on its way: not after dbgk_finalize)
 		size_t off = 0;
 		if (!bits_pinned && h->cap_bases >= flag_room + kSlice) {
-			bits_pinned = reinterpret_cast<uint8_t *>(sl.h_bases);
+			bits_pinned = reinterpret_cast<uint8_t *>(sl.h_bases.p);
 			off = flag_room;
 		}
 		for (; off + kSlice <= h->cap_bases && bufs.size() < kMaxBuffers; off += kSlice) bufs.push_back(sl.h_bases + off);
 	}
 	if (bufs.size() < kMinBuffers) {
 		while (h->d2h_stage.size() < kOwnBuffers) {
-			void *p = nullptr;
-			if (hipHostMalloc(&p, kOwnSlice, hipHostMallocDefault) != hipSuccess) { cleanup(); return DBGK_ERR_NOMEM; }
-			h->d2h_stage.push_back(p);
+			PinBuf<char> p;
+			if (p.alloc(kOwnSlice)) return DBGK_ERR_NOMEM;
+			h->d2h_stage.push_back(std::move(p));
 		}
-		for (void *p : h->d2h_stage)
-			for (size_t off = 0; off + kSlice <= kOwnSlice && bufs.size() < kMaxBuffers; off += kSlice) bufs.push_back(static_cast<char *>(p) + off);
+		for (const PinBuf<char> &p : h->d2h_stage)
+			for (size_t off = 0; off + kSlice <= kOwnSlice && bufs.size() < kMaxBuffers; off += kSlice) bufs.push_back(p + off);
 	}
 	while (h->d2h_ev.size() < bufs.size()) {
-		hipEvent_t ev = nullptr;
-		if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { cleanup(); return DBGK_ERR_HIP; }
-		h->d2h_ev.push_back(ev);
+		StageEvent ev;
+		if (ev.create(hipEventDisableTiming)) return DBGK_ERR_HIP;
+		h->d2h_ev.push_back(std::move(ev));
 	}
 	const size_t n_bufs = bufs.size();
 	lap(0);
@@ -284,25 +278,18 @@ static int d2h_compact(dbgk_handle *h, dbgk_node *array, uint8_t *nul_flag, cons
 	                   (n_flag_bytes + 3) / 4, n_spans, d_counts);
 	std::vector<uint32_t> counts(n_spans);
 	std::vector<uint64_t> first(n_spans + 1);
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts, n_spans * 4, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e != hipSuccess) { cleanup(); return hip_fail(e, "d2h_compact(counts)", __LINE__); }
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(counts.data(), d_counts, n_spans * 4, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	first[0] = 0;
 	for (uint64_t b = 0; b < n_spans; b++) first[b + 1] = first[b] + counts[b];
-	if (first[n_spans] != n_occ) { // (never: the counters and the bits describe the same table)
-		cleanup();
-		return DBGK_ERR_STATE;
-	}
+	if (first[n_spans] != n_occ) return DBGK_ERR_STATE; // (never: the counters and the bits describe the same table)
 	lap(1);
-	e = hipMemcpyAsync(d_first, first.data(), n_spans * 8, hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(bits_pinned ? bits_pinned : nul_flag, d_flags, n_flag_bytes, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_compact_nodes, dim3(span_grid), dim3(256), 0, h->stream, T.nodes, size, h->d_ctr, d_first, n_spans, d_stream);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // the bits are on the host: the threads below read them
-	if (e != hipSuccess) { cleanup(); return hip_fail(e, "d2h_compact(bits)", __LINE__); }
+	HIPCHK(hipMemcpyAsync(d_first, first.data(), n_spans * 8, hipMemcpyHostToDevice, h->stream));
+	HIPCHK(hipMemcpyAsync(bits_pinned ? bits_pinned : nul_flag, d_flags, n_flag_bytes, hipMemcpyDeviceToHost, h->stream));
+	hipLaunchKernelGGL(k_compact_nodes, dim3(span_grid), dim3(256), 0, h->stream, T.nodes, size, h->d_ctr, d_first, n_spans, d_stream);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream)); // the bits are on the host: the threads below read them
 	lap(2);
 	// slices of the stream small enough that every thread gets several (the zeros between the nodes are written by the thread
 	// whose nodes come next, so the slot ranges follow the ranks)
@@ -412,7 +399,7 @@ static int d2h_compact(dbgk_handle *h, dbgk_node *array, uint8_t *nul_flag, cons
 	if (failed.load() && rc == DBGK_OK) rc = DBGK_ERR_HIP;
 	if (rc == DBGK_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = DBGK_ERR_HIP;
 	lap(3);
-	cleanup();
+	d_stream.release(); // (the large one: its release is what the last lap times)
 	lap(4);
 	if (rc) return hip_fail(hipGetLastError(), "d2h_compact", __LINE__);
 	if (lap_wanted)
@@ -466,38 +453,25 @@ extern "C" int dbgk_export_host_table_links(dbgk_handle *h, uint64_t host_size, 
 static int run_link_pass(dbgk_handle *h, const TableRef &T, const LinkOutputs &LO)
 {
 	const uint64_t n_blocks = (T.size + kLinkChunk - 1) / kLinkChunk;
-	uint16_t *d_klink = nullptr;
-	uint8_t *d_del = nullptr;
-	unsigned long long *d_stats = nullptr, *d_base = nullptr, *d_tips = nullptr, *d_branches = nullptr;
-	uint32_t *d_counts = nullptr;
-	auto cleanup = [&]() {
-		for (void *p : {(void *)d_klink, (void *)d_del, (void *)d_stats, (void *)d_base, (void *)d_tips, (void *)d_branches, (void *)d_counts})
-			if (p) (void)hipFree(p);
-	};
-	if (hipMalloc(&d_klink, T.size * 2) != hipSuccess || hipMalloc(&d_del, T.size / 8 + 1) != hipSuccess || hipMalloc(&d_stats, 261 * 8) != hipSuccess ||
-	    hipMalloc(&d_counts, n_blocks * 8) != hipSuccess || hipMalloc(&d_base, n_blocks * 16) != hipSuccess) {
-		cleanup();
+	DevBuf<uint16_t> d_klink;
+	DevBuf<uint8_t> d_del;
+	DevBuf<unsigned long long> d_stats, d_base, d_tips, d_branches;
+	DevBuf<uint32_t> d_counts;
+	if (d_klink.reserve(T.size * 2) || d_del.reserve(T.size / 8 + 1) || d_stats.reserve(261 * 8) || d_counts.reserve(n_blocks * 8) || d_base.reserve(n_blocks * 16))
 		return DBGK_ERR_NOMEM;
-	}
-	hipError_t e = hipMemsetAsync(d_stats, 0, 261 * 8, h->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(d_del, 0, T.size / 8 + 1, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_kmer_links<0>, dim3((unsigned)n_blocks), dim3(kBlock), 0, h->stream, T.nodes, T.size, h->d_ctr, (int)LO.cutoff, d_klink, d_del, d_stats,
-		                   d_counts, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
-		e = hipGetLastError();
-	}
+	HIPCHK(hipMemsetAsync(d_stats, 0, 261 * 8, h->stream));
+	HIPCHK(hipMemsetAsync(d_del, 0, T.size / 8 + 1, h->stream));
+	hipLaunchKernelGGL(k_kmer_links<0>, dim3((unsigned)n_blocks), dim3(kBlock), 0, h->stream, T.nodes, T.size, h->d_ctr, (int)LO.cutoff, d_klink, d_del, d_stats,
+	                   d_counts, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+	HIPCHK(hipGetLastError());
 	std::vector<uint32_t> counts(n_blocks * 2);
 	std::vector<unsigned long long> base(n_blocks * 2);
 	unsigned long long res[261];
-	if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts, n_blocks * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(res, d_stats, sizeof res, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(LO.klink, d_klink, T.size * 2, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(LO.del_flag, d_del, T.size / 8 + 1, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e != hipSuccess) {
-		cleanup();
-		return hip_fail(e, "export_host_table_links", __LINE__);
-	}
+	HIPCHK(hipMemcpyAsync(counts.data(), d_counts, n_blocks * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(res, d_stats, sizeof res, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(LO.klink, d_klink, T.size * 2, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(LO.del_flag, d_del, T.size / 8 + 1, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	unsigned long long nt = 0, nb = 0;
 	for (uint64_t b = 0; b < n_blocks; b++) {
 		base[2 * b] = nt;
@@ -515,27 +489,18 @@ static int run_link_pass(dbgk_handle *h, const TableRef &T, const LinkOutputs &L
 		LO.stats->tip_nodes = (int64_t)res[259];
 		LO.stats->branch_nodes = (int64_t)res[260];
 	}
-	int rc = DBGK_OK;
 	if ((LO.tips || LO.branches) && (nt || nb)) {
-		if ((LO.tips && nt > LO.tip_cap) || (LO.branches && nb > LO.branch_cap)) {
-			rc = DBGK_ERR_CAPACITY; // *n_tips / *n_branches say what is needed
-		} else if (hipMalloc(&d_tips, (nt ? nt : 1) * 8) != hipSuccess || hipMalloc(&d_branches, (nb ? nb : 1) * 8) != hipSuccess) {
-			rc = DBGK_ERR_NOMEM;
-		} else {
-			e = hipMemcpyAsync(d_base, base.data(), n_blocks * 16, hipMemcpyHostToDevice, h->stream);
-			if (e == hipSuccess) {
-				hipLaunchKernelGGL(k_kmer_links<1>, dim3((unsigned)n_blocks), dim3(kBlock), 0, h->stream, T.nodes, T.size, h->d_ctr, (int)LO.cutoff, d_klink, d_del,
-				                   d_stats, d_counts, d_base, d_tips, d_branches);
-				e = hipGetLastError();
-			}
-			if (e == hipSuccess && LO.tips && nt) e = hipMemcpyAsync(LO.tips, d_tips, nt * 8, hipMemcpyDeviceToHost, h->stream);
-			if (e == hipSuccess && LO.branches && nb) e = hipMemcpyAsync(LO.branches, d_branches, nb * 8, hipMemcpyDeviceToHost, h->stream);
-			if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-			if (e != hipSuccess) rc = hip_fail(e, "export_host_table_links(lists)", __LINE__);
-		}
+		if ((LO.tips && nt > LO.tip_cap) || (LO.branches && nb > LO.branch_cap)) return DBGK_ERR_CAPACITY; // *n_tips / *n_branches say what is needed
+		if (d_tips.reserve((nt ? nt : 1) * 8) || d_branches.reserve((nb ? nb : 1) * 8)) return DBGK_ERR_NOMEM;
+		HIPCHK(hipMemcpyAsync(d_base, base.data(), n_blocks * 16, hipMemcpyHostToDevice, h->stream));
+		hipLaunchKernelGGL(k_kmer_links<1>, dim3((unsigned)n_blocks), dim3(kBlock), 0, h->stream, T.nodes, T.size, h->d_ctr, (int)LO.cutoff, d_klink, d_del,
+		                   d_stats, d_counts, d_base, d_tips, d_branches);
+		HIPCHK(hipGetLastError());
+		if (LO.tips && nt) HIPCHK(hipMemcpyAsync(LO.tips, d_tips, nt * 8, hipMemcpyDeviceToHost, h->stream));
+		if (LO.branches && nb) HIPCHK(hipMemcpyAsync(LO.branches, d_branches, nb * 8, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
 	}
-	cleanup();
-	return rc;
+	return DBGK_OK;
 }
 
 static int export_host_table_impl(dbgk_handle *h, uint64_t host_size, dbgk_node *array, uint8_t *nul_flag, const LinkOutputs *LO)
@@ -549,36 +514,30 @@ static int export_host_table_impl(dbgk_handle *h, uint64_t host_size, dbgk_node 
 	if (rc) return rc;
 	if (h->sharded) { // the shard's slice of the global table: slots [slot_lo, slot_hi), key-0 node not placed
 		if (host_size != h->tslots) return DBGK_ERR_ARG;
-		uint8_t *d_fl = nullptr;
-		if (hipMalloc(&d_fl, host_size / 8 + 1) != hipSuccess) return DBGK_ERR_NOMEM;
+		DevBuf<uint8_t> d_fl;
+		if (d_fl.reserve(host_size / 8 + 1)) return DBGK_ERR_NOMEM;
 		hipLaunchKernelGGL(k_build_flags_ctr, dim3(grid_for(h, host_size / 8 + 1)), dim3(kBlock), 0, h->stream, h->table, h->tslots,
 		                   h->d_ctr, d_fl);
-		hipError_t es = hipGetLastError();
-		if (es == hipSuccess) es = hipMemcpyAsync(array, h->table, host_size * sizeof(Node), hipMemcpyDeviceToHost, h->stream);
-		if (es == hipSuccess) es = hipMemcpyAsync(nul_flag, d_fl, host_size / 8 + 1, hipMemcpyDeviceToHost, h->stream);
-		if (es == hipSuccess) es = hipStreamSynchronize(h->stream);
-		(void)hipFree(d_fl);
-		if (es != hipSuccess) return hip_fail(es, "export_host_table(shard)", __LINE__);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(array, h->table, host_size * sizeof(Node), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipMemcpyAsync(nul_flag, d_fl, host_size / 8 + 1, hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
 		return DBGK_OK;
 	}
 	if (h->h_ctr->n_new + 1 > host_size) return DBGK_ERR_TABLE_FULL;
 
 	TableRef T = h->tref();
-	Node *tmp = nullptr;
-	uint8_t *d_flags = nullptr;
-	auto cleanup = [&]() {
-		if (tmp) (void)hipFree(tmp);
-		if (d_flags) (void)hipFree(d_flags);
-	};
+	DevBuf<Node> tmp;
+	DevBuf<uint8_t> d_flags;
 	if (host_size != h->size) {
-		if (hipMalloc(&tmp, host_size * sizeof(Node)) != hipSuccess) return DBGK_ERR_NOMEM;
+		if (tmp.reserve(host_size * sizeof(Node))) return DBGK_ERR_NOMEM;
 		T = TableRef{tmp, host_size, make_mod_magic(host_size)};
-		if (hipMemsetAsync(tmp, 0, host_size * sizeof(Node), h->stream) != hipSuccess) { cleanup(); return DBGK_ERR_HIP; }
+		if (hipMemsetAsync(tmp, 0, host_size * sizeof(Node), h->stream) != hipSuccess) return DBGK_ERR_HIP;
 		hipLaunchKernelGGL(k_rehash, dim3(grid_for(h, h->size)), dim3(kBlock), 0, h->stream, h->table, h->size, T, h->d_ctr);
 	}
 	const uint64_t flag_bytes = host_size / 8 + 1, flag_alloc = (flag_bytes + 11) & ~7ull; // whole dwords for k_flag_block_counts
-	if (hipMalloc(&d_flags, flag_alloc) != hipSuccess) { cleanup(); return DBGK_ERR_NOMEM; }
-	if (hipMemsetAsync(d_flags, 0, flag_alloc, h->stream) != hipSuccess) { cleanup(); return DBGK_ERR_HIP; }
+	if (d_flags.reserve(flag_alloc)) return DBGK_ERR_NOMEM;
+	if (hipMemsetAsync(d_flags, 0, flag_alloc, h->stream) != hipSuccess) return DBGK_ERR_HIP;
 	hipLaunchKernelGGL(k_place_polyA, dim3(1), dim3(64), 0, h->stream, T, h->d_ctr);
 	hipLaunchKernelGGL(k_build_flags_ctr, dim3(grid_for(h, host_size / 8 + 1)), dim3(kBlock), 0, h->stream, T.nodes, T.size,
 	                   h->d_ctr, d_flags);
@@ -609,7 +568,6 @@ static int export_host_table_impl(dbgk_handle *h, uint64_t host_size, dbgk_node 
 	}
 	if (e == hipSuccess) e = hipMemcpyAsync(h->h_ctr, h->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, h->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	cleanup();
 	if (e != hipSuccess) return hip_fail(e, "export_host_table", __LINE__);
 	if (h->h_ctr->error & 1u) return DBGK_ERR_TABLE_FULL;
 	return link_rc;
@@ -635,41 +593,26 @@ extern "C" int dbgk_export_sorted(dbgk_handle *h, dbgk_node *out, uint64_t capac
 	}
 	if (n == 0) return DBGK_OK;
 
-	uint64_t *d_keys = nullptr, *d_links = nullptr;
-	unsigned long long *d_cursor = nullptr;
-	auto cleanup = [&]() {
-		if (d_keys) (void)hipFree(d_keys);
-		if (d_links) (void)hipFree(d_links);
-		if (d_cursor) (void)hipFree(d_cursor);
-	};
-	if (hipMalloc(&d_keys, n * 8) != hipSuccess || hipMalloc(&d_links, n * 8) != hipSuccess ||
-	    hipMalloc(&d_cursor, 8) != hipSuccess) {
-		cleanup();
-		return DBGK_ERR_NOMEM;
-	}
-	hipError_t e = hipMemsetAsync(d_cursor, 0, 8, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_compact, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, d_keys, d_links,
-		                   d_cursor, n);
-		e = hipGetLastError();
-	}
+	DevBuf<uint64_t> d_keys, d_links;
+	DevBuf<unsigned long long> d_cursor;
+	if (d_keys.reserve(n * 8) || d_links.reserve(n * 8) || d_cursor.reserve(8)) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemsetAsync(d_cursor, 0, 8, h->stream));
+	hipLaunchKernelGGL(k_compact, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, d_keys, d_links,
+	                   d_cursor, n);
+	HIPCHK(hipGetLastError());
 	unsigned long long found = 0;
-	if (e == hipSuccess) e = hipMemcpyAsync(&found, d_cursor, 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e != hipSuccess) { cleanup(); return hip_fail(e, "export_sorted/compact", __LINE__); }
+	HIPCHK(hipMemcpyAsync(&found, d_cursor, 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	if (found != n) {
-		cleanup();
 		g_last_error = "export_sorted: occupied slots != counted keys";
 		return DBGK_ERR_STATE;
 	}
 	rc = dbgk_internal_sort_pairs(d_keys, d_links, n, h->stream);
-	if (rc != DBGK_OK) { cleanup(); return rc; }
+	if (rc != DBGK_OK) return rc;
 	std::vector<uint64_t> hk(n), hl(n);
-	e = hipMemcpyAsync(hk.data(), d_keys, n * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(hl.data(), d_links, n * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	cleanup();
-	if (e != hipSuccess) return hip_fail(e, "export_sorted/copy", __LINE__);
+	HIPCHK(hipMemcpyAsync(hk.data(), d_keys, n * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(hl.data(), d_links, n * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	for (uint64_t i = 0; i < n; i++) {
 		out[i + z].kmer = hk[i];
 		out[i + z].l_link = (uint32_t)(hl[i] & 0xFFFFFFFFu);
@@ -688,35 +631,22 @@ extern "C" int dbgk_export_first_seen_order(dbgk_handle *h, dbgk_node *out, uint
 	*n_out = n;
 	if (capacity < n) return DBGK_ERR_CAPACITY;
 	if (n == 0) return DBGK_OK;
-	uint64_t *d_pos = nullptr, *d_slot = nullptr;
-	unsigned long long *d_cursor = nullptr;
-	Node *d_nodes = nullptr;
-	auto cleanup = [&]() {
-		for (void *p : {(void *)d_pos, (void *)d_slot, (void *)d_cursor, (void *)d_nodes})
-			if (p) (void)hipFree(p);
-	};
-	if (hipMalloc(&d_pos, n * 8) != hipSuccess || hipMalloc(&d_slot, n * 8) != hipSuccess || hipMalloc(&d_cursor, 8) != hipSuccess ||
-	    hipMalloc(&d_nodes, n * sizeof(Node)) != hipSuccess) {
-		cleanup();
-		return DBGK_ERR_NOMEM;
-	}
-	hipError_t e = hipMemsetAsync(d_cursor, 0, 8, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_compact_order, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->first_pos, h->tslots, d_pos,
-		                   d_slot, d_cursor, n);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	if (e != hipSuccess) { cleanup(); return hip_fail(e, "export_first_seen_order/compact", __LINE__); }
+	DevBuf<uint64_t> d_pos, d_slot;
+	DevBuf<unsigned long long> d_cursor;
+	DevBuf<Node> d_nodes;
+	if (d_pos.reserve(n * 8) || d_slot.reserve(n * 8) || d_cursor.reserve(8) || d_nodes.reserve(n * sizeof(Node))) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemsetAsync(d_cursor, 0, 8, h->stream));
+	hipLaunchKernelGGL(k_compact_order, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->first_pos, h->tslots, d_pos,
+	                   d_slot, d_cursor, n);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream));
 	rc = dbgk_internal_sort_pairs(d_pos, d_slot, n, h->stream); // positions are unique per key: a total order
-	if (rc != DBGK_OK) { cleanup(); return rc; }
+	if (rc != DBGK_OK) return rc;
 	hipLaunchKernelGGL(k_gather_nodes, dim3(grid_for(h, n)), dim3(kBlock), 0, h->stream, h->table, d_slot, n, d_nodes);
-	e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpyAsync(out, d_nodes, n * sizeof(Node), hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(first_pos, d_pos, n * 8, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	cleanup();
-	if (e != hipSuccess) return hip_fail(e, "export_first_seen_order", __LINE__);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(out, d_nodes, n * sizeof(Node), hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipMemcpyAsync(first_pos, d_pos, n * 8, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return DBGK_OK;
 }
 
@@ -728,21 +658,17 @@ extern "C" int dbgk_digest(dbgk_handle *h, uint64_t *digest)
 	if (!h->finalized) return DBGK_ERR_STATE;
 	int rc = use_device(h);
 	if (rc) return rc;
-	unsigned long long *d_out = nullptr;
-	if (hipMalloc(&d_out, 16) != hipSuccess) return DBGK_ERR_NOMEM;
+	DevBuf<unsigned long long> d_out;
+	if (d_out.reserve(16)) return DBGK_ERR_NOMEM;
 	unsigned long long res[2] = {0, 0};
-	hipError_t e = hipMemsetAsync(d_out, 0, 16, h->stream);
-	if (e == hipSuccess) {
-		if (h->wide)
-			hipLaunchKernelGGL(k_wide_digest, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, d_out);
-		else
-			hipLaunchKernelGGL(k_digest, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, d_out);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(res, d_out, 16, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_out);
-	if (e != hipSuccess) return hip_fail(e, "digest", __LINE__);
+	HIPCHK(hipMemsetAsync(d_out, 0, 16, h->stream));
+	if (h->wide)
+		hipLaunchKernelGGL(k_wide_digest, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, d_out);
+	else
+		hipLaunchKernelGGL(k_digest, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, d_out);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(res, d_out, 16, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	*digest = res[0] + ((h->sharded && h->shard_rank != 0) ? 0ull : node_digest(0ull, h->h_ctr->polyA_links));
 	return DBGK_OK;
 }
@@ -755,24 +681,20 @@ extern "C" int dbgk_link_stats_device(dbgk_handle *h, int32_t cutoff, dbgk_link_
 	if (!h->finalized) return DBGK_ERR_STATE;
 	int rc = use_device(h);
 	if (rc) return rc;
-	unsigned long long *d_out = nullptr;
+	DevBuf<unsigned long long> d_out;
 	const size_t bytes = 261 * sizeof(unsigned long long);
-	if (hipMalloc(&d_out, bytes) != hipSuccess) return DBGK_ERR_NOMEM;
+	if (d_out.reserve(bytes)) return DBGK_ERR_NOMEM;
 	unsigned long long res[261];
-	hipError_t e = hipMemsetAsync(d_out, 0, bytes, h->stream);
-	if (e == hipSuccess) {
-		if (h->wide)
-			hipLaunchKernelGGL(k_wide_link_stats, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, (int)cutoff,
-			                   (uint64_t)h->h_ctr->polyA_links, (h->sharded && h->shard_rank != 0) ? 0 : 1, d_out);
-		else
-			hipLaunchKernelGGL(k_link_stats, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, (int)cutoff,
-			                   (uint64_t)h->h_ctr->polyA_links, (h->sharded && h->shard_rank != 0) ? 0 : 1, d_out);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(res, d_out, bytes, hipMemcpyDeviceToHost, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d_out);
-	if (e != hipSuccess) return hip_fail(e, "link_stats", __LINE__);
+	HIPCHK(hipMemsetAsync(d_out, 0, bytes, h->stream));
+	if (h->wide)
+		hipLaunchKernelGGL(k_wide_link_stats, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, h->wside, (int)cutoff,
+		                   (uint64_t)h->h_ctr->polyA_links, (h->sharded && h->shard_rank != 0) ? 0 : 1, d_out);
+	else
+		hipLaunchKernelGGL(k_link_stats, dim3(grid_for(h, h->tslots)), dim3(kBlock), 0, h->stream, h->table, h->tslots, (int)cutoff,
+		                   (uint64_t)h->h_ctr->polyA_links, (h->sharded && h->shard_rank != 0) ? 0 : 1, d_out);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(res, d_out, bytes, hipMemcpyDeviceToHost, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	for (int i = 0; i < 256; i++) out->depth_stat[i] = (int64_t)res[i];
 	out->total_nodes = (int64_t)res[256];
 	out->deleted_lowfreq = (int64_t)res[257];

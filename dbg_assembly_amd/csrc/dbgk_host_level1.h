@@ -99,30 +99,19 @@ static L1Facts l1_facts(const dbgk_handle *h, bool wrec)
 static int ensure_prefix_scratch(dbgk_handle *h, uint64_t n_reads, uint64_t n_bases, bool need_packed)
 {
 	const uint64_t tiles = (n_bases / 15 + n_reads) / kL1Threads + 2; // a read of W windows has at most W / 15 + 1 lanes
-	if (n_reads > h->pf_cap_reads || tiles > h->pf_cap_tiles) {
+	const uint64_t cr = std::max(n_reads, h->cap_reads), ct = std::max(tiles, (h->cap_bases / 15 + h->cap_reads) / kL1Threads + 2);
+	if (cr * sizeof(ReadLanes) > h->pf_ent.cap || ct * sizeof(PrefixTile) > h->pf_tiles.cap) {
 		HIPCHK(hipStreamSynchronize(h->stream));
-		for (void *q : {(void *)h->pf_ent, (void *)h->pf_tile_first, (void *)h->pf_tiles, (void *)h->pf_bsum})
-			if (q) (void)hipFree(q);
-		h->pf_ent = nullptr; h->pf_tile_first = nullptr; h->pf_tiles = nullptr; h->pf_bsum = nullptr;
-		h->pf_cap_reads = h->pf_cap_tiles = 0;
-		const uint64_t cr = std::max(n_reads, h->cap_reads), ct = std::max(tiles, (h->cap_bases / 15 + h->cap_reads) / kL1Threads + 2);
 		const uint64_t blocks = (cr + kPrefixBlock * kPrefixItems - 1) / (kPrefixBlock * kPrefixItems) + 1;
-		if (hipMalloc(&h->pf_ent, cr * sizeof(ReadLanes)) != hipSuccess || hipMalloc(&h->pf_tile_first, (ct + 1) * 4) != hipSuccess ||
-		    hipMalloc(&h->pf_tiles, ct * sizeof(PrefixTile)) != hipSuccess || hipMalloc(&h->pf_bsum, blocks * 8) != hipSuccess)
+		if (h->pf_ent.reserve(cr * sizeof(ReadLanes)) || h->pf_tile_first.reserve((ct + 1) * 4) || h->pf_tiles.reserve(ct * sizeof(PrefixTile)) ||
+		    h->pf_bsum.reserve(blocks * 8))
 			return DBGK_ERR_NOMEM;
-		h->pf_cap_reads = cr;
-		h->pf_cap_tiles = ct;
 	}
-	if (!h->pf_tot && hipMalloc(&h->pf_tot, sizeof(PrefixTotals)) != hipSuccess) return DBGK_ERR_NOMEM;
+	if (h->pf_tot.reserve(sizeof(PrefixTotals))) return DBGK_ERR_NOMEM;
 	const uint64_t words = (n_bases + 15) / 16 + 16;
-	if (need_packed && words > h->pf_packed_words) {
+	if (need_packed && words * 4 > h->pf_packed.cap) {
 		HIPCHK(hipStreamSynchronize(h->stream));
-		if (h->pf_packed) (void)hipFree(h->pf_packed);
-		h->pf_packed = nullptr;
-		h->pf_packed_words = 0;
-		const uint64_t cw = std::max(words, h->cap_bases / 16 + 16);
-		if (hipMalloc(&h->pf_packed, cw * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		h->pf_packed_words = cw;
+		if (h->pf_packed.reserve(words * 4, (h->cap_bases / 16 + 16) * 4)) return DBGK_ERR_NOMEM;
 	}
 	return DBGK_OK;
 }
@@ -134,7 +123,7 @@ template <int CC>
 static void launch_prefix_passes(dbgk_handle *h, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases)
 {
 	const uint32_t n_blocks = (uint32_t)((n_reads + kPrefixBlock * kPrefixItems - 1) / (kPrefixBlock * kPrefixItems));
-	const uint32_t tiles_max = (uint32_t)std::min<uint64_t>((n_bases / 15 + n_reads) / kL1Threads + 1, h->pf_cap_tiles);
+	const uint32_t tiles_max = (uint32_t)std::min<uint64_t>((n_bases / 15 + n_reads) / kL1Threads + 1, h->pf_tiles.cap / sizeof(PrefixTile));
 	const uint32_t k = (uint32_t)h->cfg.kmer_size, max_len = (uint32_t)h->cfg.max_read_len;
 	hipLaunchKernelGGL((k_prefix_count<CC>), dim3(n_blocks), dim3(kPrefixBlock), 0, h->stream, d_offsets, n_reads, k, max_len, h->pf_bsum);
 	hipLaunchKernelGGL(k_prefix_blocks, dim3(1), dim3(kPrefixBlock), 0, h->stream, h->pf_bsum, n_blocks, h->pf_tot);
@@ -167,24 +156,24 @@ static int launch_l1(dbgk_handle *h, const L1Plan &plan, const ReadBatch &rb, co
 				r.n_bases = l.n_reads * g.L;
 			}
 			rc = l1_launch(kL1UniformRows, l.form, grid, kL1Threads, h->stream, r, UniformGeom{g.L, g.W, g.Q, g.qmagic, g.n_lanes, g.lq, g.tile_blocks},
-			               d_offsets, h->geom, h->store, h->d_ctr);
+			               d_offsets, h->geom, h->store, h->d_ctr.p);
 			break;
 		}
 		case L1Family::Prefix:
-			rc = l1_launch(kL1PrefixRows, l.form, grid, kL1Threads, h->stream, rb, h->pf_ent, h->pf_tiles, h->pf_tot, h->geom, h->store, h->d_ctr);
+			rc = l1_launch(kL1PrefixRows, l.form, grid, kL1Threads, h->stream, rb, h->pf_ent.p, h->pf_tiles.p, h->pf_tot.p, h->geom, h->store, h->d_ctr.p);
 			break;
 		case L1Family::Flat:
-			rc = l1_launch(kL1FlatRows, l.form, grid, kL1Threads, h->stream, rb, h->geom, h->store, h->d_ctr);
+			rc = l1_launch(kL1FlatRows, l.form, grid, kL1Threads, h->stream, rb, h->geom, h->store, h->d_ctr.p);
 			break;
 		case L1Family::FlatLin:
-			rc = l1_launch(kL1FlatLinRows, l.form, grid, kL1Threads, h->stream, rb, h->geom, h->store, h->d_ctr);
+			rc = l1_launch(kL1FlatLinRows, l.form, grid, kL1Threads, h->stream, rb, h->geom, h->store, h->d_ctr.p);
 			break;
 		case L1Family::WideFlat:
-			rc = l1_launch(kL1WideFlatRows, l.form, grid, kWL1Threads, h->stream, rb, h->wgeom, h->wstore, h->wref(), h->d_ctr);
+			rc = l1_launch(kL1WideFlatRows, l.form, grid, kWL1Threads, h->stream, rb, h->wgeom, h->wstore, h->wref(), h->d_ctr.p);
 			break;
 		case L1Family::WideUniform:
 			rc = l1_launch(kL1WideUniformRows, l.form, grid, kWL1Threads, h->stream, rb, WUniformGeom{g.L, g.W, g.Q, g.qmagic, g.n_lanes}, h->wgeom,
-			               h->wstore, h->wref(), h->d_ctr);
+			               h->wstore, h->wref(), h->d_ctr.p);
 			break;
 		}
 		if (rc) return rc;
@@ -242,14 +231,9 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 	// front of level 1; any other consumer gets the offsets made on the device first.
 	const bool no_offsets = d_offsets == nullptr;
 	auto make_offsets = [&]() -> int {
-		if (n_reads + 1 > h->uni_cap) {
+		if ((n_reads + 1) * 8 > h->uni_offsets.cap) {
 			HIPCHK(hipStreamSynchronize(h->stream));
-			if (h->uni_offsets) (void)hipFree(h->uni_offsets);
-			h->uni_offsets = nullptr;
-			h->uni_cap = 0;
-			const uint64_t cap = std::max(n_reads + 1, h->cap_reads + 1);
-			if (hipMalloc(&h->uni_offsets, cap * 8) != hipSuccess) return DBGK_ERR_NOMEM;
-			h->uni_cap = cap;
+			if (h->uni_offsets.reserve((n_reads + 1) * 8, (h->cap_reads + 1) * 8)) return DBGK_ERR_NOMEM;
 		}
 		hipLaunchKernelGGL(k_iota_offsets, dim3(grid_for(h, n_reads + 1)), dim3(kBlock), 0, h->stream, h->uni_offsets, n_reads, (uint64_t)uniform_len);
 		HIPCHK(hipMemsetAsync(&h->d_ctr->any_dead, 0, 20, h->stream));
@@ -319,9 +303,9 @@ static int launch_batch(dbgk_handle *h, const char *d_bases, const uint64_t *d_o
 			hipLaunchKernelGGL(k_wide_extract_insert<false>, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, h->wref(), h->d_ctr);
 	} else if (h->kfreq && !h->part) {
 		if (has_long)
-			hipLaunchKernelGGL(k_extract_count<true>, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, reinterpret_cast<uint32_t *>(h->counts));
+			hipLaunchKernelGGL(k_extract_count<true>, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, reinterpret_cast<uint32_t *>(h->counts.p));
 		else
-			hipLaunchKernelGGL(k_extract_count<false>, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, reinterpret_cast<uint32_t *>(h->counts));
+			hipLaunchKernelGGL(k_extract_count<false>, dim3(grid_for(h, n_chunks)), dim3(kBlock), 0, h->stream, rb, reinterpret_cast<uint32_t *>(h->counts.p));
 	} else if (h->part) {
 		if (use_prefix) {
 			// lane prefix of the batch (three short kernels over the offsets), the batch itself as 2-bit words, then level 1

@@ -11,20 +11,16 @@ extern "C" int dbgk_add_polyA(dbgk_handle *h, uint32_t l_link, uint32_t r_link)
 	Node nd;
 	nd.kmer = 0;
 	nd.links = (uint64_t)l_link | ((uint64_t)r_link << 32);
-	Node *d = nullptr;
-	if (hipMalloc(&d, sizeof(Node)) != hipSuccess) return DBGK_ERR_NOMEM;
-	hipError_t e = hipMemcpyAsync(d, &nd, sizeof(Node), hipMemcpyHostToDevice, h->stream);
-	if (e == hipSuccess) {
-		if (h->sharded)
-			hipLaunchKernelGGL(k_merge_sharded, dim3(1), dim3(kBlock), 0, h->stream, d, (const unsigned long long *)nullptr, (uint64_t)1, (uint64_t)1, 0,
-			                   0, h->geom, h->store, h->table, h->d_ctr);
-		else
-			hipLaunchKernelGGL(k_merge_nodes, dim3(1), dim3(kBlock), 0, h->stream, d, (uint64_t)1, h->tref(), h->d_ctr);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-	(void)hipFree(d);
-	if (e != hipSuccess) return hip_fail(e, "add_polyA", __LINE__);
+	DevBuf<Node> d;
+	if (d.reserve(sizeof(Node))) return DBGK_ERR_NOMEM;
+	HIPCHK(hipMemcpyAsync(d, &nd, sizeof(Node), hipMemcpyHostToDevice, h->stream));
+	if (h->sharded)
+		hipLaunchKernelGGL(k_merge_sharded, dim3(1), dim3(kBlock), 0, h->stream, d, (const unsigned long long *)nullptr, (uint64_t)1, (uint64_t)1, 0,
+		                   0, h->geom, h->store, h->table, h->d_ctr);
+	else
+		hipLaunchKernelGGL(k_merge_nodes, dim3(1), dim3(kBlock), 0, h->stream, d, (uint64_t)1, h->tref(), h->d_ctr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(h->stream));
 	return DBGK_OK;
 }
 
@@ -195,45 +191,37 @@ static int measure_copy_bandwidth(dbgk_handle *h, size_t bytes, int iters, doubl
 	int rc = use_device(h);
 	if (rc) return rc;
 	bytes &= ~(size_t)65535; // whole tiles of the probe kernels
-	void *a = nullptr, *b = nullptr;
-	if (hipMalloc(&a, bytes) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&b, bytes) != hipSuccess) {
-		(void)hipFree(a);
-		return DBGK_ERR_NOMEM;
-	}
-	hipEvent_t e0, e1;
-	hipError_t e = hipEventCreate(&e0);
-	if (e == hipSuccess) e = hipEventCreate(&e1);
-	if (e == hipSuccess) e = hipMemsetAsync(a, 1, bytes, h->stream);
+	DevBuf<probe_u32x4> src, dst;
+	if (src.reserve(bytes) || dst.reserve(bytes)) return DBGK_ERR_NOMEM;
+	const probe_u32x4 *a = src;
+	probe_u32x4 *b = dst;
+	StageEvent e0, e1;
+	if (e0.create() || e1.create()) return DBGK_ERR_HIP;
+	HIPCHK(hipMemsetAsync(src, 1, bytes, h->stream));
 	double best = 0.0;
-	for (int variant = 0; variant < 5 && e == hipSuccess; variant++) {
+	for (int variant = 0; variant < 5; variant++) {
 		auto run = [&]() -> hipError_t {
 			const size_t n_vec = bytes / 16;
 			switch (variant) {
 			case 0: return hipMemcpyAsync(b, a, bytes, hipMemcpyDeviceToDevice, h->stream);
-			case 1: hipLaunchKernelGGL(k_probe_copy<true>, dim3(h->n_cu), dim3(1024), 0, h->stream, (const probe_u32x4 *)a, (probe_u32x4 *)b, n_vec); break;
-			case 2: hipLaunchKernelGGL(k_probe_copy<true>, dim3(2 * h->n_cu), dim3(1024), 0, h->stream, (const probe_u32x4 *)a, (probe_u32x4 *)b, n_vec); break;
-			case 3: hipLaunchKernelGGL(k_probe_copy<false>, dim3(h->n_cu), dim3(1024), 0, h->stream, (const probe_u32x4 *)a, (probe_u32x4 *)b, n_vec); break;
-			default: hipLaunchKernelGGL(k_probe_copy<false>, dim3(2 * h->n_cu), dim3(1024), 0, h->stream, (const probe_u32x4 *)a, (probe_u32x4 *)b, n_vec); break;
+			case 1: hipLaunchKernelGGL(k_probe_copy<true>, dim3(h->n_cu), dim3(1024), 0, h->stream, a, b, n_vec); break;
+			case 2: hipLaunchKernelGGL(k_probe_copy<true>, dim3(2 * h->n_cu), dim3(1024), 0, h->stream, a, b, n_vec); break;
+			case 3: hipLaunchKernelGGL(k_probe_copy<false>, dim3(h->n_cu), dim3(1024), 0, h->stream, a, b, n_vec); break;
+			default: hipLaunchKernelGGL(k_probe_copy<false>, dim3(2 * h->n_cu), dim3(1024), 0, h->stream, a, b, n_vec); break;
 			}
 			return hipGetLastError();
 		};
-		e = run(); // warm-up
-		if (e == hipSuccess) e = hipEventRecord(e0, h->stream);
-		for (int i = 0; i < iters && e == hipSuccess; i++) e = run();
-		if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-		if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+		HIPCHK(run()); // warm-up
+		HIPCHK(hipEventRecord(e0, h->stream));
+		for (int i = 0; i < iters; i++) HIPCHK(run());
+		HIPCHK(hipEventRecord(e1, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
 		float ms = 0.f;
-		if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-		const double rate = (e == hipSuccess && ms > 0.f) ? (2.0 * (double)bytes * iters) / (ms * 1e-3) / 1e9 : 0.0; // bytes read + bytes written
+		HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+		const double rate = ms > 0.f ? (2.0 * (double)bytes * iters) / (ms * 1e-3) / 1e9 : 0.0; // bytes read + bytes written
 		best = std::max(best, rate);
 		if (variant == 0 && runtime_memcpy) *runtime_memcpy = rate;
 	}
-	(void)hipFree(a);
-	(void)hipFree(b);
-	(void)hipEventDestroy(e0);
-	(void)hipEventDestroy(e1);
-	if (e != hipSuccess) return hip_fail(e, "measure_copy_bandwidth", __LINE__);
 	*gbps = best;
 	return DBGK_OK;
 }
@@ -266,40 +254,26 @@ extern "C" int dbgk_measure_gather_bandwidth(dbgk_handle *h, size_t bytes, uint6
 	if (!h || !gbps || bytes < (1u << 20) || n_accesses < 1024) return DBGK_ERR_ARG;
 	int rc = use_device(h);
 	if (rc) return rc;
-	void *a = nullptr;
-	unsigned long long *sink = nullptr;
-	if (hipMalloc(&a, bytes) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&sink, 8) != hipSuccess) {
-		(void)hipFree(a);
-		return DBGK_ERR_NOMEM;
-	}
+	DevBuf<uint4> a;
+	DevBuf<unsigned long long> sink;
+	if (a.reserve(bytes) || sink.reserve(8)) return DBGK_ERR_NOMEM;
 	const uint32_t per_group = 64;
 	const uint64_t groups = (n_accesses + per_group - 1) / per_group;
 	const uint64_t blocks = (groups * 4 + kBlock - 1) / kBlock;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	hipError_t e = hipEventCreate(&e0);
-	if (e == hipSuccess) e = hipEventCreate(&e1);
-	if (e == hipSuccess) e = hipMemsetAsync(a, 1, bytes, h->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(sink, 0, 8, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_random_gather64, dim3((unsigned)std::min<uint64_t>(blocks, 1u << 20)), dim3(kBlock), 0, h->stream, (const uint4 *)a, (uint64_t)(bytes >> 6), 4u,
-		                   sink); // warm-up (page tables)
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipEventRecord(e0, h->stream);
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_random_gather64, dim3((unsigned)blocks), dim3(kBlock), 0, h->stream, (const uint4 *)a, (uint64_t)(bytes >> 6), per_group, sink);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+	StageEvent e0, e1;
+	if (e0.create() || e1.create()) return DBGK_ERR_HIP;
+	HIPCHK(hipMemsetAsync(a, 1, bytes, h->stream));
+	HIPCHK(hipMemsetAsync(sink, 0, 8, h->stream));
+	hipLaunchKernelGGL(k_random_gather64, dim3((unsigned)std::min<uint64_t>(blocks, 1u << 20)), dim3(kBlock), 0, h->stream, a, (uint64_t)(bytes >> 6), 4u,
+	                   sink); // warm-up (page tables)
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(e0, h->stream));
+	hipLaunchKernelGGL(k_random_gather64, dim3((unsigned)blocks), dim3(kBlock), 0, h->stream, a, (uint64_t)(bytes >> 6), per_group, sink);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(e1, h->stream));
+	HIPCHK(hipStreamSynchronize(h->stream));
 	float ms = 0.f;
-	if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-	(void)hipFree(a);
-	(void)hipFree(sink);
-	if (e0) (void)hipEventDestroy(e0);
-	if (e1) (void)hipEventDestroy(e1);
-	if (e != hipSuccess) return hip_fail(e, "measure_gather_bandwidth", __LINE__);
+	HIPCHK(hipEventElapsedTime(&ms, e0, e1));
 	const double done = (double)(blocks * (kBlock / 4)) * per_group;
 	*gbps = done * 64.0 / (ms * 1e-3) / 1e9;
 	if (gaccesses_per_s) *gaccesses_per_s = done / (ms * 1e-3) / 1e9;

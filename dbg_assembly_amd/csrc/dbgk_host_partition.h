@@ -51,30 +51,30 @@ static int reset_state(dbgk_handle *h)
 	return DBGK_OK;
 }
 
-// Decide whether the PARTITION engine is used and allocate its record stores.
+// Decide whether the PARTITION engine is used, and the geometry of its record stores: host arithmetic on the configuration, the
+// hash modulus `size` and whether the handle counts k-mers (KFREQ, and there in direct blocks).  Nothing of a handle is read or written.
 //   geometry: level-1 bucket = slot >> r, r >= 20 chosen so that n1 = ceil(size / 2^r) <= 1024;
 //   final bucket = slot >> 12 (one 4096-slot region); n2 = 2^(r-12) sub-buckets per level-1 bucket.
 //   An 8-byte record must hold q = hash / size, r slot bits and 6 neighbour bits.
-static int plan_partition(dbgk_handle *h)
+static int plan_partition(const dbgk_config &cfg, uint64_t size, bool kfreq, bool kf_blocks, PartPlan &plan)
 {
-	h->part = false;
-	h->sharded = false;
-	memset(&h->store, 0, sizeof h->store);
-	memset(&h->geom, 0, sizeof h->geom);
-	h->tslots = h->size;
-	if (h->kfreq && h->kf_blocks) { // direct blocks: `size` = 4^k, slot = the key with its block index permuted (kf_slot_of_key)
-		PartGeom &G = h->geom;
-		const uint32_t bits = 2u * (uint32_t)h->cfg.kmer_size; // >= 26
+	plan = PartPlan();
+	memset(&plan.geom, 0, sizeof plan.geom);
+	plan.tslots = size;
+	const ModMagic magic = make_mod_magic(size);
+	if (kfreq && kf_blocks) { // direct blocks: `size` = 4^k, slot = the key with its block index permuted (kf_slot_of_key)
+		PartGeom &G = plan.geom;
+		const uint32_t bits = 2u * (uint32_t)cfg.kmer_size; // >= 26
 		// level-1 bucket = slot >> r: 256 buckets where the table allows (the wave-per-bucket level-1 kernel), level 2 then
 		// splits a bucket into its 2^(r - 16) <= 1024 blocks in one pass
 		const uint32_t r = std::max(20u, std::min(26u, bits - 8u));
-		G.size = h->size;
-		G.magic = h->magic;
-		if (h->size < (1ull << 32)) G.div = make_div32_magic((uint32_t)h->size);
+		G.size = size;
+		G.magic = magic;
+		if (size < (1ull << 32)) G.div = make_div32_magic((uint32_t)size);
 		G.r = r;
-		G.n1 = (uint32_t)(h->size >> r);
+		G.n1 = (uint32_t)(size >> r);
 		G.n2 = 1u << (r - kKfBlockBits);
-		G.n_final = (uint32_t)(h->size >> kKfBlockBits);
+		G.n_final = (uint32_t)(size >> kKfBlockBits);
 		G.n_ranks = 1;
 		G.rank = 0;
 		G.B = G.n1;
@@ -82,9 +82,9 @@ static int plan_partition(dbgk_handle *h)
 		G.b_lo = 0;
 		G.nb_own = G.n1;
 		G.slot_lo = 0;
-		G.slot_hi = h->size;
+		G.slot_hi = size;
 		G.n_regions_own = G.n_final;
-		const double per_slot = (double)h->cfg.expected_kmers / (double)h->size;
+		const double per_slot = (double)cfg.expected_kmers / (double)size;
 		// a level-1 bucket sums 2^(r - 16) blocks of very different weight (canonical k-mers favour small key values): more slack
 		// than the hashed form's 5 %; a single block may hold 2.2 times the average
 		G.cap1 = (uint64_t)(per_slot * (double)(1ull << r) * 1.2 / (double)G.n_sub) + 65536 / G.n_sub + 8192;
@@ -95,31 +95,31 @@ static int plan_partition(dbgk_handle *h)
 		G.l2_records = 16u * (uint32_t)l2_threads((int)G.n2);
 		G.kf_mask = (uint32_t)((1ull << (bits - kKfBlockBits)) - 1ull);
 		if (G.n1 > (uint32_t)kL1MaxB || G.n2 > (uint32_t)kMaxBuckets) return DBGK_OK; // (cannot happen for 13 <= k <= 18)
-		h->shard_rank = 0;
-		h->part = true;
-		h->three = false;
+		plan.shard_rank = 0;
+		plan.part = true;
+		plan.three = false;
 		return DBGK_OK;
 	}
-	const uint32_t n_ranks = h->cfg.shard_count > 1 ? h->cfg.shard_count : 1;
-	const int want = h->cfg.engine == DBGK_ENGINE_SEEDIDX ? DBGK_ENGINE_DIRECT // the seed index uses the plain table
-	                 : h->cfg.engine == DBGK_ENGINE_KFREQ ? DBGK_ENGINE_AUTO   // KFREQ: only if the geometry is feasible
-	                                                      : h->cfg.engine;
-	const bool want_shard = h->cfg.shard_count >= 1; // shard_count == 1: one-rank sharded handle (same protocol, for testing)
-	if (want_shard && h->cfg.shard_index >= n_ranks) return DBGK_ERR_ARG;
+	const uint32_t n_ranks = cfg.shard_count > 1 ? cfg.shard_count : 1;
+	const int want = cfg.engine == DBGK_ENGINE_SEEDIDX ? DBGK_ENGINE_DIRECT // the seed index uses the plain table
+	                 : cfg.engine == DBGK_ENGINE_KFREQ ? DBGK_ENGINE_AUTO   // KFREQ: only if the geometry is feasible
+	                                                      : cfg.engine;
+	const bool want_shard = cfg.shard_count >= 1; // shard_count == 1: one-rank sharded handle (same protocol, for testing)
+	if (want_shard && cfg.shard_index >= n_ranks) return DBGK_ERR_ARG;
 	if (!want_shard) {
 		if (want == DBGK_ENGINE_DIRECT) return DBGK_OK;
-		if (want == DBGK_ENGINE_AUTO && h->cfg.expected_kmers == 0) return DBGK_OK; // streaming use: total unknown
+		if (want == DBGK_ENGINE_AUTO && cfg.expected_kmers == 0) return DBGK_OK; // streaming use: total unknown
 	}
 	uint32_t r = 22; // measured on cfg2 (round 2, profiles/r02_r_sweep.txt): r = 20 / 21 / 22 -> 17.3 / 16.5 / 16.3 ms per step
 	if (const char *e = DBGK_EXPERIMENT_ENV("DBGK_PART_R")) r = (uint32_t)std::max(20, std::min(24, atoi(e))); // tuning knob: level-1 bucket = slot >> r
-	while (((h->size + (1ull << r) - 1) >> r) > (uint64_t)kL1MaxB) r++;
-	const uint64_t qmax = ~0ull / h->size;
+	while (((size + (1ull << r) - 1) >> r) > (uint64_t)kL1MaxB) r++;
+	const uint64_t qmax = ~0ull / size;
 	int qbits = 0;
 	while (qbits < 64 && (qmax >> qbits)) qbits++;
-	while (r > 20 && qbits + (int)r + 6 > 64 && ((h->size + (1ull << (r - 1)) - 1) >> (r - 1)) <= (uint64_t)kL1MaxB) r--; // small tables: q needs the bits
+	while (r > 20 && qbits + (int)r + 6 > 64 && ((size + (1ull << (r - 1)) - 1) >> (r - 1)) <= (uint64_t)kL1MaxB) r--; // small tables: q needs the bits
 	// level 1 fans out to <= 1024 buckets, level 2 to 2^(r-12) <= 4096 final buckets per level-1 bucket: 2^34 slots
-	const bool feasible = (1u << (r - kRegionBits)) <= (uint32_t)kMaxBucketsL2 && (qbits + (int)r + 6) <= 64 && h->size >= (1ull << 26) &&
-	                      h->size < (1ull << 34);
+	const bool feasible = (1u << (r - kRegionBits)) <= (uint32_t)kMaxBucketsL2 && (qbits + (int)r + 6) <= 64 && size >= (1ull << 26) &&
+	                      size < (1ull << 34);
 	if (!feasible || (want_shard && want == DBGK_ENGINE_DIRECT)) {
 		if (want == DBGK_ENGINE_PARTITION || want_shard) {
 			g_last_error = "PARTITION engine (and any sharded handle) needs 2^26 <= table_slots < 2^34";
@@ -133,31 +133,31 @@ static int plan_partition(dbgk_handle *h)
 			return DBGK_ERR_STATE;
 		}
 	}
-	PartGeom &G = h->geom;
-	G.size = h->size;
-	G.magic = h->magic;
-	if (h->size < (1ull << 32)) G.div = make_div32_magic((uint32_t)h->size);
+	PartGeom &G = plan.geom;
+	G.size = size;
+	G.magic = magic;
+	if (size < (1ull << 32)) G.div = make_div32_magic((uint32_t)size);
 	G.r = r;
-	G.n1 = (uint32_t)((h->size + (1ull << r) - 1) >> r);
+	G.n1 = (uint32_t)((size + (1ull << r) - 1) >> r);
 	G.n2 = 1u << (r - kRegionBits);
-	G.n_final = (uint32_t)((h->size + kRegionSlots - 1) >> kRegionBits);
+	G.n_final = (uint32_t)((size + kRegionSlots - 1) >> kRegionBits);
 	G.n_ranks = n_ranks;
-	G.rank = want_shard ? h->cfg.shard_index : 0;
-	h->shard_rank = G.rank;
+	G.rank = want_shard ? cfg.shard_index : 0;
+	plan.shard_rank = G.rank;
 	G.B = (G.n1 + n_ranks - 1) / n_ranks;
 	G.n_sub = kSubStores;
 	G.b_lo = std::min(G.rank * G.B, G.n1);
 	G.nb_own = std::min(G.B, G.n1 - G.b_lo);
 	G.slot_lo = (uint64_t)G.b_lo << r;
-	G.slot_hi = std::min<uint64_t>(h->size, ((uint64_t)G.b_lo + G.nb_own) << r);
+	G.slot_hi = std::min<uint64_t>(size, ((uint64_t)G.b_lo + G.nb_own) << r);
 	G.n_regions_own = (uint32_t)((G.slot_hi - G.slot_lo + kRegionSlots - 1) >> kRegionBits);
 	if (G.nb_own == 0 || (uint64_t)n_ranks * G.B * G.n_sub > (uint64_t)kMaxInboxEntries) {
 		g_last_error = "shard_count too large for this table size";
 		return DBGK_ERR_ARG;
 	}
 	// expected_kmers = occurrences THIS handle extracts; a region receives the global density
-	const uint64_t expected = h->cfg.expected_kmers ? h->cfg.expected_kmers : h->size * 2 / n_ranks;
-	const double per_slot = (double)expected / (double)h->size;
+	const uint64_t expected = cfg.expected_kmers ? cfg.expected_kmers : size * 2 / n_ranks;
+	const double per_slot = (double)expected / (double)size;
 	G.cap1 = (uint64_t)(per_slot * (double)(1ull << r) * 1.05 / (double)G.n_sub) + 65536 / G.n_sub + (G.n_sub > 1 ? 8192 : 0); // per sub-store
 	G.cap2 = (uint64_t)(per_slot * (double)n_ranks * (double)kRegionSlots * 1.15) + 512;
 	// every bucket starts on a 128-byte line (the 16-byte record loads of level 2 and of the build are aligned), and a bucket is an ODD
@@ -169,37 +169,50 @@ static int plan_partition(dbgk_handle *h)
 	G.r_rec = r;
 	G.l2_shift = 0;
 	G.l2_records = 16u * (uint32_t)l2_threads((int)G.n2);
-	h->tslots = G.slot_hi - G.slot_lo;
-	h->sharded = want_shard;
-	h->part = true;
+	plan.tslots = G.slot_hi - G.slot_lo;
+	plan.sharded = want_shard;
+	plan.part = true;
 	static const bool no_three = DBGK_EXPERIMENT_ENV("DBGK_THREE_LEVEL") && atoi(DBGK_EXPERIMENT_ENV("DBGK_THREE_LEVEL")) == 0; // measurements
 	// measured with cfg2's 1.2 G records, level 2 alone: n2 = 4096 (8.6 G slots) 17.6 ms in one pass, 9.7 ms in two;
 	// n2 = 2048 (5 G slots) 6.9 ms in one pass, 9.5 in two -- so only the 4096-way fan-out is split
-	h->three = G.n2 > 2048u && !no_three;
-	if (h->three) {
-		h->fan_mid = G.n2 / 64u; // 64
+	plan.three = G.n2 > 2048u && !no_three;
+	if (plan.three) {
+		plan.fan_mid = G.n2 / 64u; // 64
 		uint32_t lg = 0;
-		while ((1u << lg) < h->fan_mid) lg++;
+		while ((1u << lg) < plan.fan_mid) lg++;
 		const uint64_t cap_mid = ((uint64_t)(per_slot * (double)n_ranks * (double)(1ull << (r - lg)) * 1.08) + 8192 + 15u) & ~15ull;
-		h->g_mid = G;
-		h->g_mid.n2 = h->fan_mid;
-		h->g_mid.l2_records = 16u * (uint32_t)l2_threads((int)h->fan_mid);
-		h->g_mid.l2_shift = 6;      // the low 6 bits of the final-bucket index are left to the final pass
-		h->g_mid.cap2 = cap_mid;
-		h->g_fin = G;
-		h->g_fin.n_ranks = 1;       // its input is this handle's own mid store
-		h->g_fin.rank = 0;
-		h->g_fin.n_sub = 1;
-		h->g_fin.r = r - lg;
-		h->g_fin.n1 = G.n1 * h->fan_mid;
-		h->g_fin.B = G.nb_own * h->fan_mid;
-		h->g_fin.b_lo = G.b_lo * h->fan_mid;
-		h->g_fin.nb_own = G.nb_own * h->fan_mid;
-		h->g_fin.n2 = 64;
-		h->g_fin.l2_records = 16u * (uint32_t)l2_threads(64);
-		h->g_fin.cap1 = cap_mid;
+		plan.g_mid = G;
+		plan.g_mid.n2 = plan.fan_mid;
+		plan.g_mid.l2_records = 16u * (uint32_t)l2_threads((int)plan.fan_mid);
+		plan.g_mid.l2_shift = 6;      // the low 6 bits of the final-bucket index are left to the final pass
+		plan.g_mid.cap2 = cap_mid;
+		plan.g_fin = G;
+		plan.g_fin.n_ranks = 1;       // its input is this handle's own mid store
+		plan.g_fin.rank = 0;
+		plan.g_fin.n_sub = 1;
+		plan.g_fin.r = r - lg;
+		plan.g_fin.n1 = G.n1 * plan.fan_mid;
+		plan.g_fin.B = G.nb_own * plan.fan_mid;
+		plan.g_fin.b_lo = G.b_lo * plan.fan_mid;
+		plan.g_fin.nb_own = G.nb_own * plan.fan_mid;
+		plan.g_fin.n2 = 64;
+		plan.g_fin.l2_records = 16u * (uint32_t)l2_threads(64);
+		plan.g_fin.cap1 = cap_mid;
 	}
 	return DBGK_OK;
+}
+
+static void apply_plan(dbgk_handle *h, const PartPlan &plan)
+{
+	h->part = plan.part;
+	h->sharded = plan.sharded;
+	h->three = plan.three;
+	h->fan_mid = plan.fan_mid;
+	h->tslots = plan.tslots;
+	h->shard_rank = plan.shard_rank;
+	h->geom = plan.geom;
+	h->g_mid = plan.g_mid;
+	h->g_fin = plan.g_fin;
 }
 
 // allocate the record stores of the PARTITION engine (geometry already planned)
@@ -210,6 +223,7 @@ static int setup_partition(dbgk_handle *h)
 	if (!h->part) return DBGK_OK;
 	const PartGeom &G = h->geom;
 	PartStore &P = h->store;
+	memset(&P, 0, sizeof P);
 	const uint64_t expected = h->cfg.expected_kmers ? h->cfg.expected_kmers : h->size * 2 / G.n_ranks;
 	// records that find their bucket full are kept as {key, lb, rb} triples and inserted through the global
 	// path after the build: a key that occurs more often than a final bucket holds (cap2, ~1.15x the mean
@@ -221,52 +235,59 @@ static int setup_partition(dbgk_handle *h)
 	const size_t n_entries = (size_t)G.n_ranks * G.B * G.n_sub;
 	const size_t l1_bytes = n_entries * G.cap1 * 8, l2_bytes = (size_t)G.nb_own * G.n2 * G.cap2 * (G.kf == 2u ? 2 : 8); // (direct blocks: 16-bit records)
 	// (+ 64 bytes: level 2 and the build load their records in pairs, and the second half of a bucket's last pair may lie behind the bucket)
-	bool ok = hipMalloc(&P.l1, l1_bytes + 64) == hipSuccess && hipMalloc(&P.l2, l2_bytes + 64) == hipSuccess &&
-	          hipMalloc(&P.cnt1, n_entries * 4) == hipSuccess && hipMalloc(&P.cnt2, (size_t)G.nb_own * G.n2 * 4) == hipSuccess &&
-	          hipMalloc(&P.ovf, P.ovf_cap * sizeof(Node)) == hipSuccess && hipMalloc(&P.spill, P.spill_cap * sizeof(Node)) == hipSuccess &&
-	          hipMalloc(&P.ovf_n, 16) == hipSuccess && hipMalloc(&h->tile_prefix, (n_entries + 1) * 4) == hipSuccess &&
-	          hipMalloc(&h->region_cursor, ((size_t)kMaxBuildLaunches + 2 + G.n_regions_own) * sizeof(unsigned int)) == hipSuccess && // + redo cursor, count, list
-
-	          hipMalloc(&P.outgoing, P.outgoing_cap * sizeof(Node)) == hipSuccess && hipMalloc(&P.outgoing_n, 8) == hipSuccess;
-	if (ok && h->sharded)
-		ok = hipMalloc(&h->inbox, l1_bytes + 64) == hipSuccess && hipMalloc(&h->inbox_cnt, n_entries * 4) == hipSuccess;
+	PartBufs &O = h->pbuf;
+	bool ok = !O.l1.reserve(l1_bytes + 64) && !O.l2.reserve(l2_bytes + 64) && !O.cnt1.reserve(n_entries * 4) && !O.cnt2.reserve((size_t)G.nb_own * G.n2 * 4) &&
+	          !O.ovf.reserve(P.ovf_cap * sizeof(Node)) && !O.spill.reserve(P.spill_cap * sizeof(Node)) && !O.ovf_n.reserve(16) &&
+	          !O.tile_prefix.reserve((n_entries + 1) * 4) &&
+	          !O.region_cursor.reserve(((size_t)kMaxBuildLaunches + 2 + G.n_regions_own) * sizeof(unsigned int)) && // + redo cursor, count, list
+	          !O.outgoing.reserve(P.outgoing_cap * sizeof(Node)) && !O.outgoing_n.reserve(8);
+	if (ok && h->sharded) ok = !O.inbox.reserve(l1_bytes + 64) && !O.inbox_cnt.reserve(n_entries * 4);
 	if (!ok) {
 		g_last_error = "hipMalloc of the PARTITION record stores failed";
 		return DBGK_ERR_NOMEM;
 	}
 	// side table for the surplus of heavy hitters; on a sharded handle it may hold keys of any shard and is
 	// offered to every rank after the build (dbgk_shard_heavy), like the overflow list
-	if (hipMalloc(&P.hh, kHeavyHitterSlots * sizeof(Node)) != hipSuccess) return DBGK_ERR_NOMEM;
+	if (O.hh.reserve(kHeavyHitterSlots * sizeof(Node))) return DBGK_ERR_NOMEM;
+	P.l1 = O.l1;
+	P.l2 = O.l2;
+	P.cnt1 = O.cnt1;
+	P.cnt2 = O.cnt2;
+	P.ovf = O.ovf;
+	P.spill = O.spill;
+	P.ovf_n = O.ovf_n;
+	P.outgoing = O.outgoing;
+	P.outgoing_n = O.outgoing_n;
+	P.hh = O.hh;
 	HIPCHK(hipMemsetAsync(P.hh, 0, kHeavyHitterSlots * sizeof(Node), h->stream)); // once: afterwards it is zeroed again only when it was used (clear_record_store)
 	P.hh_size = kHeavyHitterSlots;
 	P.hh_magic = make_mod_magic(kHeavyHitterSlots);
-	P.inbox = h->sharded ? h->inbox : P.l1;
-	P.inbox_cnt = h->sharded ? h->inbox_cnt : P.cnt1;
+	P.inbox = h->sharded ? O.inbox.p : O.l1.p;
+	P.inbox_cnt = h->sharded ? O.inbox_cnt.p : O.cnt1.p;
 	// EARLY level 2 (early_l2): a handle that extracts into its own inbox scatters what earlier batches stored while the next
 	// batch is on the link.  Not for shards (their inbox is filled by the exchange), the three-level form, 32-bit KFREQ records
 	const bool no_early = dbgk_hook("early_l2") && atoi(dbgk_hook("early_l2")) == 0; // (read per handle: measurements, and the tests compare the two)
 	P.l2_done = P.l2_upto = nullptr;
 	if (!h->sharded && !h->three && G.kf != 2u && !no_early) {
-		if (hipMalloc(&h->l2_done, 2 * n_entries * 4) != hipSuccess) return DBGK_ERR_NOMEM; // done[] and upto[]
-		HIPCHK(hipMemsetAsync(h->l2_done, 0, 2 * n_entries * 4, h->stream));
-		P.l2_done = h->l2_done;
-		P.l2_upto = h->l2_done + n_entries;
+		if (h->pbuf.l2_done.reserve(2 * n_entries * 4)) return DBGK_ERR_NOMEM; // done[] and upto[]
+		HIPCHK(hipMemsetAsync(h->pbuf.l2_done, 0, 2 * n_entries * 4, h->stream));
+		P.l2_done = h->pbuf.l2_done;
+		P.l2_upto = h->pbuf.l2_done + n_entries;
 	}
 	h->l2_seen_kmers = 0;
 	h->store_capacity = expected;
 	if (h->three) {
 		const size_t n_mid = (size_t)G.nb_own * h->fan_mid;
-		if (hipMalloc(&h->mid, n_mid * h->g_mid.cap2 * 8 + 64) != hipSuccess || hipMalloc(&h->cnt_mid, n_mid * 4) != hipSuccess ||
-		    hipMalloc(&h->tile_prefix2, (n_mid + 1) * 4) != hipSuccess) {
+		if (h->pbuf.mid.reserve(n_mid * h->g_mid.cap2 * 8 + 64) || h->pbuf.cnt_mid.reserve(n_mid * 4) || h->pbuf.tile_prefix2.reserve((n_mid + 1) * 4)) {
 			g_last_error = "hipMalloc of the mid-level record store failed";
 			return DBGK_ERR_NOMEM;
 		}
 		h->s_mid = P;           // reads the inbox like level 2, writes the mid store
-		h->s_mid.l2 = h->mid;
-		h->s_mid.cnt2 = h->cnt_mid;
+		h->s_mid.l2 = h->pbuf.mid;
+		h->s_mid.cnt2 = h->pbuf.cnt_mid;
 		h->s_fin = P;           // reads the mid store, writes the final buckets where level 2 would
-		h->s_fin.inbox = h->mid;
-		h->s_fin.inbox_cnt = h->cnt_mid;
+		h->s_fin.inbox = h->pbuf.mid;
+		h->s_fin.inbox_cnt = h->pbuf.cnt_mid;
 	}
 	int rc = l1_register_lds(false); // every level-1 form of dbgk_l1_form.h's lists
 	if (rc) return rc;

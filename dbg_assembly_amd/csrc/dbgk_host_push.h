@@ -22,7 +22,7 @@ static void staged_copy(char *dst, const char *src, size_t n, std::vector<std::t
 	memcpy(dst, src, std::min(n, per));
 }
 
-// Is the caller's buffer page-locked memory the GPU reads directly (hipHostMalloc / hipHostRegister -- a torch pinned tensor, a
+// Is the caller's buffer page-locked memory the GPU reads directly (allocated pinned or registered -- a torch pinned tensor, a
 // parser's own pinned arena)?  Then dbgk_push_reads copies host-to-device straight out of it: the staging copy, which is what
 // bounds the pageable path (~30 GB/s against the link's 57), does not happen.
 static bool device_readable_host(const char *p, size_t n)
@@ -46,19 +46,30 @@ static bool device_readable_host(const char *p, size_t n)
 	return true;
 }
 
+// room for the start / dead bitmaps of a device batch of n_bases bases.  A grow drains the stream first: a batch queued earlier
+// may still use the old ones.
+static int ensure_dev_bitmaps(dbgk_handle *h, uint64_t n_bases)
+{
+	const uint64_t bytes = bitmap_words(n_bases) * 4;
+	if (bytes <= h->dev_dead.cap) return DBGK_OK;
+	HIPCHK(hipStreamSynchronize(h->stream));
+	if (h->dev_start.reserve(bytes) || h->dev_dead.reserve(bytes)) {
+		h->dev_start.release();
+		h->dev_dead.release();
+		return DBGK_ERR_NOMEM;
+	}
+	return DBGK_OK;
+}
+
 static int ensure_slot(dbgk_handle *h, StageSlot &s)
 {
 	if (s.d_bases) return DBGK_OK;
 	const uint64_t words = bitmap_words(h->cap_bases);
-	if (hipHostMalloc(&s.h_bases, h->cap_bases, hipHostMallocDefault) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipHostMalloc(&s.h_offsets, (h->cap_reads + 1) * 8, hipHostMallocDefault) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&s.d_bases, h->cap_bases + 64) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&s.d_offsets, (h->cap_reads + 1) * 8) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&s.d_start, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-	if (hipMalloc(&s.d_dead, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-	HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-	HIPCHK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-	return DBGK_OK;
+	const bool ok = !s.h_bases.alloc(h->cap_bases) && !s.h_offsets.alloc((h->cap_reads + 1) * 8) && !s.d_bases.reserve(h->cap_bases + 64) &&
+	                !s.d_offsets.reserve((h->cap_reads + 1) * 8) && !s.d_start.reserve(words * 4) && !s.d_dead.reserve(words * 4);
+	const int rc = !ok ? DBGK_ERR_NOMEM : (s.done.create(hipEventDisableTiming) || s.copied.create(hipEventDisableTiming)) ? DBGK_ERR_HIP : DBGK_OK;
+	if (rc) s = StageSlot(); // nothing half-made stays behind
+	return rc;
 }
 
 // The host-to-device copies of a batch (sequences from `src`, offsets from the slot's pinned array) on the handle's COPY stream; the
@@ -67,12 +78,12 @@ static int ensure_slot(dbgk_handle *h, StageSlot &s)
 static int h2d_batch(dbgk_handle *h, StageSlot &s, const char *src, uint64_t nb, uint64_t n_offsets, bool last_of_pinned_source)
 {
 	static const bool serial = DBGK_EXPERIMENT_ENV("DBGK_COPY_ON_COMPUTE_STREAM") && atoi(DBGK_EXPERIMENT_ENV("DBGK_COPY_ON_COMPUTE_STREAM")); // measurements
-	if (!serial && !h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-	hipStream_t cs = serial ? h->stream : h->copy_stream;
+	if (!serial && h->copy_stream.create()) return DBGK_ERR_HIP;
+	hipStream_t cs = serial ? h->stream : h->copy_stream.s;
 	if (nb) HIPCHK(hipMemcpyAsync(s.d_bases, src, nb, hipMemcpyHostToDevice, cs));
 	if (n_offsets) HIPCHK(hipMemcpyAsync(s.d_offsets, s.h_offsets, n_offsets * 8, hipMemcpyHostToDevice, cs)); // (0: reads of one length, no offsets travel)
 	if (last_of_pinned_source) { // the caller's buffer is free again once the LAST copy out of it has run: waited for on return
-		if (!h->source_read) HIPCHK(hipEventCreateWithFlags(&h->source_read, hipEventDisableTiming));
+		if (h->source_read.create(hipEventDisableTiming)) return DBGK_ERR_HIP;
 		HIPCHK(hipEventRecord(h->source_read, cs));
 	}
 	if (!serial) {
@@ -145,7 +156,7 @@ static int push_commit_impl(dbgk_handle *h, uint64_t n_reads, bool packed)
 	rc = h2d_batch(h, s, s.h_bases, packed ? ((nb + 15) >> 4) * 4 : nb, n_reads + 1, false);
 	if (rc) return rc;
 	rc = launch_batch(h, packed ? nullptr : s.d_bases, s.d_offsets, n_reads, nb, s.d_start, s.d_dead, has_long, uniform_len, len_max,
-	                  packed ? reinterpret_cast<const uint32_t *>(s.d_bases) : nullptr);
+	                  packed ? reinterpret_cast<const uint32_t *>(s.d_bases.p) : nullptr);
 	if (rc) return rc;
 	h->pending_kmers += batch_windows;
 	HIPCHK(hipEventRecord(s.done, h->stream));
@@ -258,17 +269,8 @@ extern "C" int dbgk_push_reads_device(dbgk_handle *h, const char *d_bases, const
 	if (h->finalized) return DBGK_ERR_STATE;
 	int rc = use_device(h);
 	if (rc) return rc;
-	const uint64_t words = bitmap_words(n_bases);
-	if (words > h->dev_bits_words) {
-		HIPCHK(hipStreamSynchronize(h->stream));
-		if (h->dev_start) (void)hipFree(h->dev_start);
-		if (h->dev_dead) (void)hipFree(h->dev_dead);
-		h->dev_start = h->dev_dead = nullptr;
-		h->dev_bits_words = 0;
-		if (hipMalloc(&h->dev_start, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		if (hipMalloc(&h->dev_dead, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		h->dev_bits_words = words;
-	}
+	rc = ensure_dev_bitmaps(h, n_bases);
+	if (rc) return rc;
 	// the record store takes what it was sized for; the number of windows of a device batch is only known as
 	// an upper bound here (one per base)
 	if (((h->part && !h->sharded) || (h->wpart && !h->wbuilt)) && h->pending_kmers > 0 && h->pending_kmers + n_bases > h->store_capacity) {
@@ -424,7 +426,7 @@ extern "C" int dbgk_push_reads_packed(dbgk_handle *h, const uint32_t *packed, co
 			~Join() { for (auto &t : w) if (t.joinable()) t.join(); }
 		} join_copiers{copiers};
 		if (n_words && !direct) {
-			uint32_t *dst = reinterpret_cast<uint32_t *>(s.h_bases);
+			uint32_t *dst = reinterpret_cast<uint32_t *>(s.h_bases.p);
 			static const int want = getenv("DBGK_COPY_THREADS") ? atoi(getenv("DBGK_COPY_THREADS")) : 8;
 			const uint64_t min_piece = 1u << 20; // words
 			const uint64_t pieces = want > 1 ? std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)want, n_words / min_piece)) : 1;
@@ -442,7 +444,7 @@ extern "C" int dbgk_push_reads_packed(dbgk_handle *h, const uint32_t *packed, co
 		rc = h2d_batch(h, s, direct ? reinterpret_cast<const char *>(packed + (base0 >> 4)) : s.h_bases, n_words * 4, nr + 1, direct);
 		if (rc) return rc;
 		source_in_flight = source_in_flight || direct;
-		rc = launch_batch(h, nullptr, s.d_offsets, nr, nb, s.d_start, s.d_dead, has_long, uniform_len, len_max, reinterpret_cast<const uint32_t *>(s.d_bases));
+		rc = launch_batch(h, nullptr, s.d_offsets, nr, nb, s.d_start, s.d_dead, has_long, uniform_len, len_max, reinterpret_cast<const uint32_t *>(s.d_bases.p));
 		if (rc) return rc;
 		h->pending_kmers += batch_windows;
 		HIPCHK(hipEventRecord(s.done, h->stream));
@@ -462,17 +464,8 @@ extern "C" int dbgk_push_reads_packed_device(dbgk_handle *h, const uint32_t *d_p
 	if (h->seed) return DBGK_ERR_ARG;
 	int rc = use_device(h);
 	if (rc) return rc;
-	const uint64_t words = bitmap_words(n_bases);
-	if (words > h->dev_bits_words) {
-		HIPCHK(hipStreamSynchronize(h->stream));
-		if (h->dev_start) (void)hipFree(h->dev_start);
-		if (h->dev_dead) (void)hipFree(h->dev_dead);
-		h->dev_start = h->dev_dead = nullptr;
-		h->dev_bits_words = 0;
-		if (hipMalloc(&h->dev_start, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		if (hipMalloc(&h->dev_dead, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		h->dev_bits_words = words;
-	}
+	rc = ensure_dev_bitmaps(h, n_bases);
+	if (rc) return rc;
 	if (((h->part && !h->sharded) || (h->wpart && !h->wbuilt)) && h->pending_kmers > 0 && h->pending_kmers + n_bases > h->store_capacity) {
 		rc = flush_records(h);
 		if (rc) return rc;
@@ -557,7 +550,7 @@ extern "C" int dbgk_push_reads_packed_uniform(dbgk_handle *h, const uint32_t *pa
 		rc = h2d_batch(h, s, pinned_source ? reinterpret_cast<const char *>(src) : s.h_bases, n_words * 4, 0, pinned_source);
 		if (rc) return rc;
 		source_in_flight = source_in_flight || pinned_source;
-		rc = launch_batch(h, nullptr, nullptr, nr, nb, s.d_start, s.d_dead, L > max_len ? 1 : 0, (int64_t)L, L, reinterpret_cast<const uint32_t *>(s.d_bases));
+		rc = launch_batch(h, nullptr, nullptr, nr, nb, s.d_start, s.d_dead, L > max_len ? 1 : 0, (int64_t)L, L, reinterpret_cast<const uint32_t *>(s.d_bases.p));
 		if (rc) return rc;
 		h->pending_kmers += nr * w_read;
 		HIPCHK(hipEventRecord(s.done, h->stream));
@@ -584,17 +577,8 @@ extern "C" int dbgk_push_reads_packed_uniform_device(dbgk_handle *h, const uint3
 	}
 	const uint64_t L = read_len, K = (uint64_t)h->cfg.kmer_size, max_len = (uint64_t)h->cfg.max_read_len, n_bases = n_reads * L;
 	const uint64_t rl = L > max_len ? max_len : L, windows = (rl >= K ? rl - K + 1 : 0ull) * n_reads;
-	const uint64_t words = bitmap_words(n_bases);
-	if (words > h->dev_bits_words) {
-		HIPCHK(hipStreamSynchronize(h->stream));
-		if (h->dev_start) (void)hipFree(h->dev_start);
-		if (h->dev_dead) (void)hipFree(h->dev_dead);
-		h->dev_start = h->dev_dead = nullptr;
-		h->dev_bits_words = 0;
-		if (hipMalloc(&h->dev_start, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		if (hipMalloc(&h->dev_dead, words * 4) != hipSuccess) return DBGK_ERR_NOMEM;
-		h->dev_bits_words = words;
-	}
+	rc = ensure_dev_bitmaps(h, n_bases);
+	if (rc) return rc;
 	if (((h->part && !h->sharded) || (h->wpart && !h->wbuilt)) && h->pending_kmers > 0 && h->pending_kmers + windows > h->store_capacity) {
 		rc = flush_records(h);
 		if (rc) return rc;

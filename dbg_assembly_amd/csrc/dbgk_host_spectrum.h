@@ -8,9 +8,9 @@ static int kfreq_spectrum_add(dbgk_handle *h, uint64_t first, uint64_t n, uint64
 	if (rc) return rc;
 	h->kf_spectrum_ms = 0;
 	if (n == 0) return DBGK_OK;
-	if (!h->kf_bins && hipMalloc(&h->kf_bins, 256 * sizeof(unsigned long long)) != hipSuccess) return DBGK_ERR_NOMEM;
-	for (hipEvent_t &e : h->kf_ev)
-		if (!e) HIPCHK(hipEventCreate(&e));
+	if (h->kf_bins.reserve(256 * sizeof(unsigned long long))) return DBGK_ERR_NOMEM;
+	for (StageEvent &e : h->kf_ev)
+		if (e.create()) return DBGK_ERR_HIP;
 	unsigned long long bins[256];
 	HIPCHK(hipMemsetAsync(h->kf_bins, 0, sizeof bins, h->stream));
 	// a workgroup's 32-bit LDS bins hold what it reads: fewer than 2^31 bytes each, however few CUs there are
@@ -94,39 +94,29 @@ extern "C" int dbgk_corr_mutation_scan(dbgk_corr *c, const char *seq, const uint
 	int rc = corr_use(c);
 	if (rc) return rc;
 	const uint64_t nb = offsets[n_seqs];
-	uint8_t *d_seq = nullptr;
-	uint64_t *d_off = nullptr; // offsets, then site_lo, then the k + 1 bins
+	DevBuf<uint8_t> d_seq;
+	DevBuf<uint64_t> d_off; // offsets, then site_lo, then the k + 1 bins
 	const uint64_t words = 2 * (n_seqs + 1) + (uint64_t)k + 1;
-	hipError_t e = hipSuccess;
-	if (hipMalloc(&d_seq, nb) != hipSuccess || hipMalloc(&d_off, words * 8) != hipSuccess) {
-		(void)hipFree(d_seq);
-		(void)hipFree(d_off);
-		return DBGK_ERR_NOMEM;
-	}
+	if (d_seq.reserve(nb) || d_off.reserve(words * 8)) return DBGK_ERR_NOMEM;
 	uint64_t *d_lo = d_off + (n_seqs + 1);
 	unsigned long long *d_hist = (unsigned long long *)(d_lo + (n_seqs + 1));
-	e = hipMemcpyAsync(d_seq, seq, nb, hipMemcpyHostToDevice, c->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(d_lo, site_lo.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream);
-	if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, (size_t)(k + 1) * 8, c->stream);
+	HIPCHK(hipMemcpyAsync(d_seq, seq, nb, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(d_off, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemcpyAsync(d_lo, site_lo.data(), (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+	HIPCHK(hipMemsetAsync(d_hist, 0, (size_t)(k + 1) * 8, c->stream));
 	float ms = 0;
-	if (e == hipSuccess) {
-		uint32_t steps = 1;
-		while ((n_seqs >> steps) != 0) ++steps; // halvings that bring a range of n_seqs down to one
-		const uint64_t grid = std::min<uint64_t>((n_sites + spec::kThreads - 1) / spec::kThreads, (uint64_t)std::max(c->n_cu, 1) * 16);
-		(void)hipEventRecord(c->ev[0], c->stream);
-		hipLaunchKernelGGL(spec::k_mut_scan, dim3((unsigned)grid), dim3(spec::kThreads), 0, c->stream, (const uint8_t *)d_seq,
-		                   (const uint64_t *)d_off, (const uint64_t *)d_lo, n_seqs, steps, n_sites, skip, k, (const uint32_t *)c->tab,
-		                   c->cp.total, d_hist);
-		e = hipGetLastError();
-		(void)hipEventRecord(c->ev[1], c->stream);
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(hist, d_hist, (size_t)(k + 1) * 8, hipMemcpyDeviceToHost, c->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	if (e == hipSuccess && hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->ms_mut_scan = ms;
-	(void)hipFree(d_seq);
-	(void)hipFree(d_off);
-	if (e != hipSuccess) return hip_fail(e, "mutation_scan", __LINE__);
+	uint32_t steps = 1;
+	while ((n_seqs >> steps) != 0) ++steps; // halvings that bring a range of n_seqs down to one
+	const uint64_t grid = std::min<uint64_t>((n_sites + spec::kThreads - 1) / spec::kThreads, (uint64_t)std::max(c->n_cu, 1) * 16);
+	(void)hipEventRecord(c->ev[0], c->stream);
+	hipLaunchKernelGGL(spec::k_mut_scan, dim3((unsigned)grid), dim3(spec::kThreads), 0, c->stream, (const uint8_t *)d_seq,
+	                   (const uint64_t *)d_off, (const uint64_t *)d_lo, n_seqs, steps, n_sites, skip, k, (const uint32_t *)c->tab,
+	                   c->cp.total, d_hist);
+	HIPCHK(hipGetLastError());
+	(void)hipEventRecord(c->ev[1], c->stream);
+	HIPCHK(hipMemcpyAsync(hist, d_hist, (size_t)(k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	if (hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) c->ms_mut_scan = ms;
 	return DBGK_OK;
 }
 

@@ -1,7 +1,8 @@
-// What every stage handle is built from (CORRECT, MAP, CLEAN, PAIR, PARSE, FORMAT, DEFLATE, INFLATE, LINK, CONTIG, and the buffers of
-// FILL and SUPER): the device it runs on with its stream, buffers that free themselves, events, and the scan's temporary storage.  A
-// handle derives from StageDev, so the stream is made first and destroyed last: it outlives every buffer and event the handle owns.
-// A *_destroy is then: null check, stage_drain, the stage's own waits, delete.
+// What every handle is built from -- the graph handle (dbgk_handle) and the stage handles (CORRECT, MAP, CLEAN, PAIR, PARSE, FORMAT,
+// DEFLATE, INFLATE, LINK, CONTIG, and the buffers of FILL and SUPER): the device it runs on with its stream, device and pinned buffers
+// that free themselves, events, further streams, and the scan's temporary storage.  A handle derives from StageDev, so the stream is
+// made first and destroyed last: it outlives every buffer and event the handle owns.  A *_destroy is then: null check, stage_drain,
+// the handle's own waits, delete.  Host functions hold their temporaries in the same owners: every return path frees them.
 
 // dbgk_sort.hip
 extern "C" int dbgk_internal_scan_lengths(void *tmp, size_t *tmp_bytes, const uint32_t *d_len, uint64_t *d_offsets, uint64_t n_items,
@@ -74,6 +75,46 @@ struct StageEvents {
 	hipEvent_t operator[](int i) const { return e[i]; }
 };
 
+// One event, made when it is first needed.  It moves, so it can live in a std::vector.
+struct StageEvent {
+	hipEvent_t e = nullptr;
+	StageEvent() = default;
+	StageEvent(StageEvent &&o) noexcept : e(o.e) { o.e = nullptr; }
+	StageEvent &operator=(StageEvent &&o) noexcept
+	{
+		std::swap(e, o.e);
+		return *this;
+	}
+	~StageEvent()
+	{
+		if (e) (void)hipEventDestroy(e);
+	}
+	operator hipEvent_t() const { return e; }
+	int create(unsigned flags = hipEventDefault)
+	{
+		if (!e) HIPCHK(hipEventCreateWithFlags(&e, flags));
+		return DBGK_OK;
+	}
+};
+
+// A stream beside the handle's first one, made when it is first needed.  Its owner drains it before the handle goes.
+struct StageStream {
+	hipStream_t s = nullptr;
+	StageStream() = default;
+	StageStream(const StageStream &) = delete;
+	StageStream &operator=(const StageStream &) = delete;
+	~StageStream()
+	{
+		if (s) (void)hipStreamDestroy(s);
+	}
+	operator hipStream_t() const { return s; }
+	int create()
+	{
+		if (!s) HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+		return DBGK_OK;
+	}
+};
+
 // A device buffer and its size in bytes.  It converts to its pointer, so launches, copies and pointer arithmetic read as
 // they do with a plain pointer; where a cast or a `? :` needs the pointer itself, it is `.p`.
 template <class T>
@@ -83,8 +124,15 @@ struct DevBuf {
 	DevBuf() = default;
 	DevBuf(const DevBuf &) = delete;
 	DevBuf &operator=(const DevBuf &) = delete;
+	DevBuf(DevBuf &&o) noexcept { take(o); }
+	DevBuf &operator=(DevBuf &&o) noexcept // (a struct of buffers is emptied by assigning a fresh one)
+	{
+		take(o);
+		return *this;
+	}
 	~DevBuf() { release(); }
 	operator T *() const { return p; }
+	T *operator->() const { return p; }
 	void release()
 	{
 		(void)hipFree(p);
@@ -113,6 +161,31 @@ struct DevBuf {
 		cap = other.cap;
 		other.p = nullptr;
 		other.cap = 0;
+	}
+};
+
+// A page-locked host buffer.  Like DevBuf it converts to its pointer; it moves, so it can live in a std::vector.
+template <class T>
+struct PinBuf {
+	T *p = nullptr;
+	PinBuf() = default;
+	PinBuf(PinBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+	PinBuf &operator=(PinBuf &&o) noexcept
+	{
+		std::swap(p, o.p);
+		return *this;
+	}
+	~PinBuf()
+	{
+		if (p) (void)hipHostFree(p);
+	}
+	operator T *() const { return p; }
+	T *operator->() const { return p; }
+	int alloc(uint64_t bytes) // (an empty buffer only)
+	{
+		if (hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess) return DBGK_OK;
+		p = nullptr;
+		return DBGK_ERR_NOMEM;
 	}
 };
 

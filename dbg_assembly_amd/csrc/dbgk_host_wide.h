@@ -109,22 +109,30 @@ static int setup_wide_partition(dbgk_handle *h)
 	P.spill_cap = (uint64_t)((h->tslots + kWRegionSlots - 1) >> kWRegionBits) * 8 + (1ull << 16);
 	P.outgoing_cap = 1ull << 16;
 	const size_t l1_bytes = (size_t)G.n_l1 * G.cap1 * 16, l2_bytes = (size_t)G.chunk_buckets * G.n2 * G.cap2 * 16;
-	bool ok = hipMalloc(&P.l1, l1_bytes) == hipSuccess && hipMalloc(&P.l2, l2_bytes) == hipSuccess &&
-	          hipMalloc(&P.cnt1, (size_t)G.n_l1 * 4) == hipSuccess && hipMalloc(&P.cnt2, (size_t)G.chunk_buckets * G.n2 * 4) == hipSuccess &&
-	          hipMalloc(&P.ovf, P.ovf_cap * sizeof(dbgk_node32)) == hipSuccess && hipMalloc(&P.spill, P.spill_cap * sizeof(dbgk_node32)) == hipSuccess &&
-	          hipMalloc(&P.ovf_n, 16) == hipSuccess && hipMalloc(&h->w_tile_prefix, ((size_t)G.n_l1 + 1) * 4) == hipSuccess &&
-	          hipMalloc(&h->w_cursor, (3 + (size_t)G.chunk_buckets * G.n2) * 4) == hipSuccess && // fast cursor, redo cursor, redo count, redo list
-	          hipMalloc(&P.outgoing, P.outgoing_cap * sizeof(dbgk_node32)) == hipSuccess &&
-	          hipMalloc(&P.outgoing_n, 8) == hipSuccess && hipMalloc(&h->w_side_out, ((size_t)kWideSideSlots + 1) * sizeof(dbgk_node32)) == hipSuccess &&
-	          hipMalloc(&h->w_side_n, 8) == hipSuccess;
-	if (ok && h->sharded) ok = hipMalloc(&h->winbox, l1_bytes) == hipSuccess && hipMalloc(&h->winbox_cnt, (size_t)G.n_l1 * 4) == hipSuccess;
+	WPartBufs &O = h->wbuf;
+	bool ok = !O.l1.reserve(l1_bytes) && !O.l2.reserve(l2_bytes) && !O.cnt1.reserve((size_t)G.n_l1 * 4) && !O.cnt2.reserve((size_t)G.chunk_buckets * G.n2 * 4) &&
+	          !O.ovf.reserve(P.ovf_cap * sizeof(dbgk_node32)) && !O.spill.reserve(P.spill_cap * sizeof(dbgk_node32)) && !O.ovf_n.reserve(16) &&
+	          !O.tile_prefix.reserve(((size_t)G.n_l1 + 1) * 4) &&
+	          !O.cursor.reserve((3 + (size_t)G.chunk_buckets * G.n2) * 4) && // fast cursor, redo cursor, redo count, redo list
+	          !O.outgoing.reserve(P.outgoing_cap * sizeof(dbgk_node32)) && !O.outgoing_n.reserve(8) &&
+	          !O.side_out.reserve(((size_t)kWideSideSlots + 1) * sizeof(dbgk_node32)) && !O.side_n.reserve(8);
+	if (ok && h->sharded) ok = !O.inbox.reserve(l1_bytes) && !O.inbox_cnt.reserve((size_t)G.n_l1 * 4);
 	if (!ok) {
 		(void)hipGetLastError();
 		g_last_error = "hipMalloc of the wide record stores failed";
 		return DBGK_ERR_NOMEM;
 	}
-	P.inbox = h->sharded ? h->winbox : P.l1;
-	P.inbox_cnt = h->sharded ? h->winbox_cnt : P.cnt1;
+	P.l1 = O.l1;
+	P.l2 = O.l2;
+	P.cnt1 = O.cnt1;
+	P.cnt2 = O.cnt2;
+	P.ovf = O.ovf;
+	P.spill = O.spill;
+	P.ovf_n = O.ovf_n;
+	P.outgoing = O.outgoing;
+	P.outgoing_n = O.outgoing_n;
+	P.inbox = h->sharded ? O.inbox.p : O.l1.p;
+	P.inbox_cnt = h->sharded ? O.inbox_cnt.p : O.cnt1.p;
 	HIPCHK(hipMemsetAsync(P.cnt1, 0, (size_t)G.n_l1 * 4, h->stream));
 	HIPCHK(hipMemsetAsync(P.ovf_n, 0, 16, h->stream));
 	HIPCHK(hipMemsetAsync(P.outgoing_n, 0, 8, h->stream));
@@ -160,7 +168,7 @@ static uint32_t wide_pass_buckets(const dbgk_handle *h)
 static int wide_plan_pass(dbgk_handle *h)
 {
 	if (h->wplanned) return DBGK_OK;
-	hipLaunchKernelGGL(k_wide_l2_plan, dim3(1), dim3(1024), 0, h->stream, h->wgeom, h->wstore.inbox_cnt, h->w_tile_prefix);
+	hipLaunchKernelGGL(k_wide_l2_plan, dim3(1), dim3(1024), 0, h->stream, h->wgeom, h->wstore.inbox_cnt, h->wbuf.tile_prefix);
 	HIPCHK(hipGetLastError());
 	h->wplanned = true;
 	h->wnext = 0;
@@ -181,28 +189,28 @@ static int wide_build_range(dbgk_handle *h, uint32_t j0, uint32_t j1)
 		if (rc) return rc;
 		HIPCHK(hipMemsetAsync(P.cnt2, 0, (size_t)G.chunk_buckets * G.n2 * 4, h->stream));
 		if (G.n2 > 1024u)
-			hipLaunchKernelGGL(k_wide_scatter_l2<2048>, dim3(h->n_cu & ~7), dim3(kWL2Threads), sizeof(WL2Lds<2048>), h->stream, G, P, h->w_tile_prefix, h->d_ctr, c0, c1);
+			hipLaunchKernelGGL(k_wide_scatter_l2<2048>, dim3(h->n_cu & ~7), dim3(kWL2Threads), sizeof(WL2Lds<2048>), h->stream, G, P, h->wbuf.tile_prefix, h->d_ctr, c0, c1);
 		else
-			hipLaunchKernelGGL(k_wide_scatter_l2<1024>, dim3((h->n_cu * 2) & ~7), dim3(kWL2Threads), sizeof(WL2Lds<1024>), h->stream, G, P, h->w_tile_prefix, h->d_ctr, c0, c1);
+			hipLaunchKernelGGL(k_wide_scatter_l2<1024>, dim3((h->n_cu * 2) & ~7), dim3(kWL2Threads), sizeof(WL2Lds<1024>), h->stream, G, P, h->wbuf.tile_prefix, h->d_ctr, c0, c1);
 		HIPCHK(hipGetLastError());
 		rc = span_end(h, sp);
 		if (rc) return rc;
 		const uint32_t n_regions = (c1 - c0) * G.n2;
 		rc = span_begin(h, PH_BUILD, sp);
 		if (rc) return rc;
-		HIPCHK(hipMemsetAsync(h->w_cursor, 0, 12, h->stream)); // both cursors and the redo count
-		const WRedoList redo{h->w_cursor + 3, h->w_cursor + 2, G.chunk_buckets * G.n2};
+		HIPCHK(hipMemsetAsync(h->wbuf.cursor, 0, 12, h->stream)); // both cursors and the redo count
+		const WRedoList redo{h->wbuf.cursor + 3, h->wbuf.cursor + 2, G.chunk_buckets * G.n2};
 		const uint32_t bgrid = std::min<uint32_t>(n_regions, (uint32_t)h->n_cu * 3u);
 		if (dbgk_hook("build_exact") && atoi(dbgk_hook("build_exact")) != 0) {
 			hipLaunchKernelGGL((k_wide_build_regions<false, false>), dim3(bgrid), dim3(kWBuildThreads), sizeof(WBuildLds), h->stream, G, P, h->wnodes, h->d_ctr,
-			                   h->w_cursor, c0, n_regions, redo);
+			                   h->wbuf.cursor, c0, n_regions, redo);
 		} else {
 			// the fast insert, then the exact pass over the regions it flagged (normally none: the kernel finds an empty list and returns);
 			// right here, while the level-2 store still holds this chunk's records
 			hipLaunchKernelGGL((k_wide_build_regions<true, false>), dim3(bgrid), dim3(kWBuildThreads), sizeof(WBuildLds), h->stream, G, P, h->wnodes, h->d_ctr,
-			                   h->w_cursor, c0, n_regions, redo);
+			                   h->wbuf.cursor, c0, n_regions, redo);
 			hipLaunchKernelGGL((k_wide_build_regions<false, true>), dim3(std::min<uint32_t>(bgrid, (uint32_t)h->n_cu)), dim3(kWBuildThreads), sizeof(WBuildLds), h->stream, G, P,
-			                   h->wnodes, h->d_ctr, h->w_cursor + 1, c0, n_regions, redo);
+			                   h->wnodes, h->d_ctr, h->wbuf.cursor + 1, c0, n_regions, redo);
 		}
 		HIPCHK(hipGetLastError());
 		rc = span_end(h, sp);

@@ -6,23 +6,22 @@
 struct WideLinkPass {
 	dbgk_handle *h;
 	uint64_t n_blocks;
-	uint16_t *d_klink = nullptr;
-	uint8_t *d_del = nullptr;
-	unsigned long long *d_stats = nullptr, *d_base = nullptr, *d_tips = nullptr, *d_branches = nullptr;
-	uint32_t *d_counts = nullptr;
+	DevBuf<uint16_t> d_klink;
+	DevBuf<uint8_t> d_del;
+	DevBuf<unsigned long long> d_stats, d_base, d_tips, d_branches;
+	DevBuf<uint32_t> d_counts;
 	std::vector<unsigned long long> base;
 	unsigned long long res[261];
 	uint64_t nt = 0, nb = 0;
 	const bool timing;                // DBGK_TIMINGS, read once per export
 	float kernel_ms[2] = {0.f, 0.f}; // ... the device time of the two launches
-	hipEvent_t ev[2] = {nullptr, nullptr};
+	StageEvent ev[2];
 
 	// around the launch of one PASS: the two events when its device time is wanted
 	int before_launch()
 	{
 		if (!timing) return DBGK_OK;
-		for (hipEvent_t &e : ev)
-			if (!e) HIPCHK(hipEventCreate(&e));
+		if (ev[0].create() || ev[1].create()) return DBGK_ERR_HIP;
 		HIPCHK(hipEventRecord(ev[0], h->stream));
 		return DBGK_OK;
 	}
@@ -39,14 +38,7 @@ struct WideLinkPass {
 	WideLinkPass(dbgk_handle *handle, bool want_timing) : h(handle), n_blocks((handle->tslots + kLinkChunk - 1) / kLinkChunk), timing(want_timing) {}
 	WideLinkPass(const WideLinkPass &) = delete;
 	WideLinkPass &operator=(const WideLinkPass &) = delete;
-	~WideLinkPass()
-	{
-		(void)hipSetDevice(h->device);
-		for (void *p : {(void *)d_klink, (void *)d_del, (void *)d_stats, (void *)d_base, (void *)d_tips, (void *)d_branches, (void *)d_counts})
-			if (p) (void)hipFree(p);
-		for (hipEvent_t e : ev)
-			if (e) (void)hipEventDestroy(e);
-	}
+	~WideLinkPass() { (void)hipSetDevice(h->device); } // (the buffers and events go after this body has run)
 
 	// PASS 0: klink[tslots] and del_flag[tslots / 8 + 1] of the handle's slots, res, nt / nb
 	int count(int32_t cutoff, uint16_t *klink, uint8_t *del_flag)
@@ -54,8 +46,7 @@ struct WideLinkPass {
 		const uint64_t size = h->tslots;
 		int rc = use_device(h);
 		if (rc) return rc;
-		if (hipMalloc(&d_klink, size * 2) != hipSuccess || hipMalloc(&d_del, size / 8 + 1) != hipSuccess || hipMalloc(&d_stats, 261 * 8) != hipSuccess ||
-		    hipMalloc(&d_counts, n_blocks * 8) != hipSuccess || hipMalloc(&d_base, n_blocks * 16) != hipSuccess)
+		if (d_klink.reserve(size * 2) || d_del.reserve(size / 8 + 1) || d_stats.reserve(261 * 8) || d_counts.reserve(n_blocks * 8) || d_base.reserve(n_blocks * 16))
 			return DBGK_ERR_NOMEM;
 		HIPCHK(hipMemsetAsync(d_stats, 0, 261 * 8, h->stream));
 		HIPCHK(hipMemsetAsync(d_del, 0, size / 8 + 1, h->stream));
@@ -85,7 +76,7 @@ struct WideLinkPass {
 		if ((!tips && !branches) || (!nt && !nb)) return DBGK_OK;
 		int rc = use_device(h);
 		if (rc) return rc;
-		if (hipMalloc(&d_tips, (nt ? nt : 1) * 8) != hipSuccess || hipMalloc(&d_branches, (nb ? nb : 1) * 8) != hipSuccess) return DBGK_ERR_NOMEM;
+		if (d_tips.reserve((nt ? nt : 1) * 8) || d_branches.reserve((nb ? nb : 1) * 8)) return DBGK_ERR_NOMEM;
 		HIPCHK(hipMemcpyAsync(d_base, base.data(), n_blocks * 16, hipMemcpyHostToDevice, h->stream));
 		if ((rc = before_launch())) return rc;
 		hipLaunchKernelGGL(k_wide_kmer_links<1>, dim3((unsigned)n_blocks), dim3(kBlock), 0, h->stream, h->wnodes, h->tslots, (int)cutoff, slot_base, d_klink, d_del,
